@@ -113,6 +113,8 @@ LAST_POWER = [None]
 
 
 def timed_region(step_fn, steps, warmup, world, device, flush_fn=None):
+    """Returns (seconds, (what the last timed step returned, what the closing flush returned))."""
+    last = tail = None
     for _ in range(warmup):
         step_fn()
     if flush_fn:
@@ -124,12 +126,13 @@ def timed_region(step_fn, steps, warmup, world, device, flush_fn=None):
         sampler.__enter__()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step_fn()
+        last = None                   # the previous step's outputs are freed before this step allocates, as if never kept
+        last = step_fn()
         if os.environ.get("SQ_BENCH_STEPTIMES"):       # debugging aid: per-step wall time (adds a sync per step)
             torch.cuda.synchronize()
             print(f"step done at {(time.perf_counter() - t0) * 1e3:.1f} ms", file=sys.stderr)
     if flush_fn:                      # streaming workloads: work still in flight belongs to the timed region
-        flush_fn()
+        tail = flush_fn()
     barrier_sync(world)
     dt = time.perf_counter() - t0
     if sampler:
@@ -139,7 +142,38 @@ def timed_region(step_fn, steps, warmup, world, device, flush_fn=None):
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, (last, tail)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMS = 1 << 21         # an output larger than this is written as a fixed seeded sample of its elements
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: write what the timed path computed in its last step as out_dir/<name>.npy, float32 (float64 for
+    64-bit sources), in the output's own shape.  An output of more than DUMP_SAMPLE_ELEMS elements is written flat as its
+    elements at the sorted flat indices numpy's default_rng(DUMP_SAMPLE_SEED).choice(numel, DUMP_SAMPLE_ELEMS, replace=False)
+    draws -- the same indices in every run of the same arguments.  Nothing is written when the total would exceed
+    DUMP_LIMIT_BYTES."""
+    arrays = {}
+    for name, a in outputs.items():
+        if a is None:
+            continue
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        flat = t.reshape(-1)
+        sampled = flat.numel() > DUMP_SAMPLE_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.numel(), DUMP_SAMPLE_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.to(torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32).cpu().numpy()
+        arrays[name] = arr if sampled else arr.reshape(tuple(t.shape))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed {DUMP_LIMIT_BYTES >> 20} MB; nothing written")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def roofline_from_profile(step_fn, steps, dtype_name, workload_name=""):
@@ -272,7 +306,8 @@ def measure_traffic(roof, args, recs=()):
                    os.path.abspath(__file__), "--workload", args.workload, "--dtype", args.dtype, "--slides", "1", "--steps", "1", "--warmup", "0",
                    "--patches", str(args.patches), "--patch-size", str(args.patch_size), "--sub-batch", str(args.sub_batch),
                    "--no-secondary", "--no-cpu-baseline", "--no-accuracy", "--no-measure-traffic"]
-            subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=900)
+            # no power sampler in the profiled child: rocm-smi started there would inherit the profiler's preload
+            subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", SQ_BENCH_NO_POWER="1"), capture_output=True, text=True, timeout=900)
             rows = []
             for f in glob.glob(out + "/**/*_counter_collection.csv", recursive=True):
                 rows += [r for r in csv.DictReader(open(f)) if r["Counter_Name"] == counter]
@@ -413,7 +448,7 @@ def workload_vis_fwd(args, rank, world, device):
 
     def step():
         with torch.no_grad():
-            model(x)
+            return model(x)
 
     def cpu_baseline():
         from oracle import vis_oracle
@@ -428,7 +463,7 @@ def workload_vis_fwd(args, rank, world, device):
         return {"value": round(rate, 3), "unit": "slides/s", "cores": threads, "kind": "port",
                 "sample": f"oracle.vis_oracle.vis_forward (torch-CPU fp32), {reps} x batch {nb} of the same tokens"}
 
-    return dict(step=step, slides_per_step=B, cpu_baseline=cpu_baseline,
+    return dict(step=step, slides_per_step=B, cpu_baseline=cpu_baseline, outputs=lambda pred, _: {"pred": pred},
                 config={"workload": "vis_fwd: ViS(D=1024, depth 6, 16 heads, G=20820) forward on 100 cluster tokens/slide",
                         "batch_per_gpu": B, "parallelism": f"slide-sharded x{world}"})
 
@@ -443,7 +478,11 @@ def workload_vis_train(args, rank, world, device):
     stepper = sq_train.FusedTrainStep(model, lr=1e-3, world_size=world)
 
     def step():
-        stepper.step(x, y)
+        return stepper.step(x, y)
+
+    def outputs(last, _):
+        loss, pred, mets = last
+        return {"loss": loss, "pred": pred, "metrics": mets, "params": model.flat}
 
     def cpu_baseline():
         from oracle import vis_oracle
@@ -462,7 +501,7 @@ def workload_vis_train(args, rank, world, device):
         return {"value": round(rate, 3), "unit": "slides/s", "cores": threads, "kind": "port",
                 "sample": f"oracle ViS fwd+bwd+AdamW (torch-CPU fp32 autograd), {reps} steps x batch {nb}"}
 
-    return dict(step=step, slides_per_step=B, cpu_baseline=cpu_baseline,
+    return dict(step=step, slides_per_step=B, cpu_baseline=cpu_baseline, outputs=outputs,
                 config={"workload": "vis_train: ViS(D=1024 UNI-dim, depth 6, 16 heads, G=20820) fwd+bwd+AdamW on "
                                     "100 cluster tokens/slide (BASELINE config 2)",
                         "batch_per_gpu": B, "global_batch": B * world,
@@ -523,15 +562,25 @@ def workload_pipeline(args, rank, world, device):
                     ev = torch.cuda.Event()
                     ev.record(copy_stream)
                     evs.append(ev)
-            run(list(zip(staging[k], evs)))      # the pipeline waits for slide i's upload right before embedding it
+            res = run(list(zip(staging[k], evs)))      # the pipeline waits for slide i's upload right before embedding it
             done = torch.cuda.Event()
             done.record(main)                    # (streaming form: the set's last slide may still be in flight -- see flush)
             consumed[k] = done
+            return res
     else:
         slides = [h.to(device) for h in host]
 
         def step():
-            run(slides)
+            return run(slides)
+
+    def outputs(res, tail):
+        """The last step's slides: streaming, its submit() returned the previous step's last slide and all but its own last
+        slide, which the closing flush() returned."""
+        parts = [r for r in (res, tail) if r is not None]
+        return {"pred": torch.cat([r["pred"] for r in parts])[-nslides:],
+                "cluster_features": torch.cat([r["cluster_features"] for r in parts])[-nslides:],
+                "labels": torch.stack([l for r in parts for l in r["labels"]][-nslides:]),
+                "features": torch.stack([f for r in parts for f in r["features"]][-nslides:])}
 
     def cpu_baseline():
         """BASELINE config 1 on this host's cores, bounded: the literal batch-1 patch loop of
@@ -569,7 +618,7 @@ def workload_pipeline(args, rank, world, device):
                           f"each extrapolated to {npatch} patches, + one oracle k-Means(100) + cluster means + ViS forward "
                           f"({t_rest:.2f} s); value = literal, batched_value = batched"}
 
-    return dict(step=step, flush=None if args.no_stream else pipe.flush, slides_per_step=nslides, cpu_baseline=cpu_baseline,
+    return dict(step=step, flush=None if args.no_stream else pipe.flush, slides_per_step=nslides, cpu_baseline=cpu_baseline, outputs=outputs,
                 config={"workload": f"pipeline: {npatch} x {S}x{S} uint8 patches/slide -> " +
                                     ("UNI ViT-L/16 embed -> k-Means(100) -> ViS(D=1024, depth 6, 16 heads, G=20820) forward (the metric's UNI-dim variant), "
                                      if uni else "ResNet-50 embed -> k-Means(100) -> ViS(D=2048, depth 6, 16 heads, G=20820) forward (BASELINE config 3), ") +
@@ -600,8 +649,11 @@ def workload_spatial(args, rank, world, device):
         bw = min(bw, max(256, -(-n_windows // (2 * world) // 256) * 256))
 
     def step():
-        out, _, _ = sliding_window_all_genes_sharded(xtf, ytf, feats, vis, 1, batch_windows=bw, shard=shard)
-        return out
+        return sliding_window_all_genes_sharded(xtf, ytf, feats, vis, 1, batch_windows=bw, shard=shard)
+
+    def outputs(last, _):
+        tile_pred, tile_ids, votes = last
+        return {"tile_pred": tile_pred, "tile_ids": tile_ids, "votes": votes}
 
     def cpu_baseline():
         from oracle import vis_oracle
@@ -616,7 +668,7 @@ def workload_spatial(args, rank, world, device):
                 "sample": f"oracle ViS forward on {reps} x 16 windows ({rate:.1f} windows/s) extrapolated to {n_windows} windows; "
                           "feature cache assumed (the reference re-embeds every tile per window), voting not timed"}
 
-    return dict(step=step, slides_per_step=1.0 / world, cpu_baseline=cpu_baseline, scaling="strong" if world > 1 else "weak",
+    return dict(step=step, slides_per_step=1.0 / world, cpu_baseline=cpu_baseline, outputs=outputs, scaling="strong" if world > 1 else "weak",
                 config={"workload": f"spatial: {nx * ny} tiles ({nx} x {ny} grid), {n_windows} windows of 100 tokens at stride 1, "
                                     "ViS(D=1024, depth 6, 16 heads, G=20820) forward per window + per-tile mean vote (BASELINE config 5)",
                         "windows_per_slide": n_windows, "batch_windows": bw,
@@ -662,13 +714,19 @@ def workload_train_kfold(args, rank, world, device):
 
     def step():
         state["folds_run"] = 0
+        test_preds = []
         for i, (tr, va, te) in enumerate(folds):
             with torch.no_grad():
                 model.flat.copy_(init)                       # main.py:165: a new model per fold (bumps the version: bf16 shadow refreshed)
             sq_train.train(model, {"train": loader(tr), "val": loader(va)}, None, num_epochs=E, save_dir=None,
                            verbose=False, split=i, lr=1e-3, grad_exchange="bf16" if args.dtype == "bf16" else "fp32")     # config 4 states bf16
-            sq_train.evaluate(model, loader(te), verbose=False)
+            test_preds.append(sq_train.evaluate(model, loader(te), verbose=False)[0])
             state["folds_run"] += 1
+        return test_preds
+
+    def outputs(test_preds, _):
+        """Every fold's test predictions (this rank's rows, fold by fold) and the parameters the last fold ends with."""
+        return {"test_pred": np.concatenate(test_preds), "params": model.flat}
 
     def check():
         """After the timed region: what a reader (and tests/test_gpu_ddp.py) needs to see that the ranks did one job --
@@ -706,7 +764,7 @@ def workload_train_kfold(args, rank, world, device):
         return {"value": round(rate, 3), "unit": "slides/s", "cores": threads, "kind": "port",
                 "sample": f"oracle ViS fwd+bwd+AdamW (torch-CPU fp32 autograd), {reps} steps x batch {nb}; host-side metrics not included"}
 
-    return dict(step=step, slides_per_step=per_gpu * (4 * E + 1), cpu_baseline=cpu_baseline, check=check,
+    return dict(step=step, slides_per_step=per_gpu * (4 * E + 1), cpu_baseline=cpu_baseline, check=check, outputs=outputs,
                 config={"workload": f"train_kfold: {n} synthetic slides ({per_gpu}/GPU), patient_kfold 5 folds, {E} epochs per fold "
                                     "(train + val) + test evaluation, ViS(D=1024, depth 6, 16 heads, G=20820) (BASELINE config 4)",
                         "slides": n, "epochs_per_fold": E,
@@ -846,7 +904,10 @@ def measure(name, args, rank, world, device, want_roofline=True, want_cpu=True):
             torch.distributed.all_reduce(est, op=torch.distributed.ReduceOp.MAX)
         steps = int(min(2000, max(5, math.ceil(2.5 / max(float(est.item()), 1e-4)))))
         warmup = 0 if warmup is None else max(0, warmup - 1)
-    dt = timed_region(wl["step"], steps, warmup, world, device, wl.get("flush"))
+    dt, last = timed_region(wl["step"], steps, warmup, world, device, wl.get("flush"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl["outputs"](*last), args.dump_outputs)       # before the instrumented steps below overwrite any workspace
+    del last
     value = wl["slides_per_step"] * world * steps / dt
     out = {"value": round(value, 3), "unit": "slides/s", "steps": steps, "warmup": args.warmup,
            "ms_per_step": round(dt / steps * 1e3, 4), "timed_region_s": round(dt, 3), "dtype": args.dtype, "config": wl["config"],
@@ -931,7 +992,14 @@ def main():
     ap.add_argument("--no-accuracy", action="store_true", help="pipeline workload: skip the accuracy_vs_reference checker leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="default workload only: skip the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (rank 0's share with --gpus > 1; "
+                         "at most 64 MB, larger outputs as a fixed seeded sample) for output-by-output comparison of two builds.  Give "
+                         "--steps (and --warmup) explicitly: without --steps the step count comes from a timing estimate, and the outputs "
+                         "of the training workloads depend on how many optimizer steps ran")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.from_host = not args.resident
     if args.dtype is None:
         args.dtype = "f16x3" if (args.workload == "pipeline" and args.embedder == "resnet") else "bf16"

@@ -17,13 +17,13 @@ from sequoia_pub_amd.vis import ViS  # noqa: E402
 CFG = dict(num_outputs=50, input_dim=128, depth=2, nheads=2, dimensions_f=64, dimensions_s=64, dimensions_c=64)
 
 
-def model():
+def model(device="cuda:0"):
     torch.manual_seed(7)
-    return ViS(**CFG, device="cuda:0", compute_dtype="fp32").to("cuda:0")
+    return ViS(**CFG, device=device, compute_dtype="fp32").to(device)
 
 
 def trajectory(rank, world, ok_path, steps=12):
-    """`world` ranks (8 in the test), two slides each, `steps` optimizer steps: the bf16 wire format against the fp32 wire format
+    """`world` ranks (4 and 8 in the tests), two slides each, `steps` optimizer steps: the bf16 wire format against the fp32 wire format
     and against ONE rank on the concatenated batch -- the full-batch loss after every step and the parameters at the end.  Rounding
     on the wire grows with the ring length (world - 1 partial sums), which two ranks for two steps do not show."""
     g = torch.Generator().manual_seed(11)
@@ -31,9 +31,10 @@ def trajectory(rank, world, ok_path, steps=12):
     x = torch.randn(n, 100, 128, generator=g).cuda()
     y = (torch.rand(n, 50, generator=g) * 8).cuda()
     rows = slice(2 * rank, 2 * rank + 2)
+    dev = f"cuda:{torch.cuda.current_device()}"
 
     def run(wire, ranks):
-        m = model()
+        m = model(dev)
         st = sq_train.FusedTrainStep(m, lr=1e-3, world_size=ranks, grad_exchange=wire)
         losses = []
         for _ in range(steps):
@@ -71,9 +72,11 @@ def trajectory(rank, world, ok_path, steps=12):
 
 def main():
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    torch.cuda.set_device(0)
+    traj = len(sys.argv) > 2 and sys.argv[2] == "trajectory"
+    # trajectory: ranks dealt over the visible GPUs (all on cuda:0 on a 1-GPU box)
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count() if traj else 0)
     dist.init_process_group("gloo")
-    if len(sys.argv) > 2 and sys.argv[2] == "trajectory":
+    if traj:
         return trajectory(rank, world, sys.argv[1])
     g = torch.Generator().manual_seed(3)
     x = torch.randn(6, 100, 128, generator=g).cuda()

@@ -28,19 +28,41 @@ def test_two_rank_fused_step_equals_one_rank_step(tmp_path, wire):
     assert ok.read_text() == "ok"
 
 
-def test_eight_rank_bf16_wire_follows_the_one_rank_trajectory(tmp_path):
-    """The opt-in bf16 wire format at the largest world size of one node (8 ranks on the shared GPU over gloo), 12 optimizer steps:
-    the full-batch loss after every step stays within 5e-3 of the one-rank run on the concatenated batch (fp32 wire: 1e-4), the
+# A shared card admits CARD_PROCESS_LIMIT processes with it open at once.  The pytest process and the torch.distributed launcher
+# (its torch.cuda.is_available() opens the device) are two of them, so at most RANKS_PER_CARD ranks share one card.
+CARD_PROCESS_LIMIT = 6
+RANKS_PER_CARD = CARD_PROCESS_LIMIT - 2
+
+
+def _bf16_wire_trajectory(tmp_path, ranks, port_salt):
+    """`ranks` ranks of ddp_worker.py's trajectory mode (rank r on cuda:r % visible GPUs, gloo), 12 optimizer steps: the full-batch
+    loss after every step stays within 5e-3 of the one-rank run on the concatenated batch with the bf16 wire (fp32 wire: 1e-4), the
     ranks end bit-identical.  Bounds the growth of the wire rounding with ring length."""
     ok = tmp_path / "ok"
-    port = 29500 + (os.getpid() + 977) % 2000
+    port = 29500 + (os.getpid() + port_salt) % 2000
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(HERE, "ddp_worker.py"), str(ok), "trajectory"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     print(r.stdout[-2000:], r.stderr[-3000:])
     assert r.returncode == 0
     assert ok.read_text() == "ok"
+
+
+def test_four_rank_bf16_wire_follows_the_one_rank_trajectory(tmp_path):
+    """The opt-in bf16 wire format over a ring of 4 ranks sharing ONE GPU (the most one card takes): three partial sums per
+    element on the wire where the two-rank tests have one."""
+    _bf16_wire_trajectory(tmp_path, RANKS_PER_CARD, 1301)
+
+
+def test_eight_rank_bf16_wire_follows_the_one_rank_trajectory(tmp_path):
+    """The opt-in bf16 wire format at the largest world size of one node: 8 ranks dealt over the visible GPUs (rank r on
+    cuda:r % n), at most RANKS_PER_CARD per card -- two cards or more."""
+    import torch
+    have = torch.cuda.device_count()
+    if -(-8 // max(have, 1)) > RANKS_PER_CARD:
+        pytest.skip(f"needs 2 GPUs (8 ranks, at most {RANKS_PER_CARD} per card), found {have}")
+    _bf16_wire_trajectory(tmp_path, 8, 977)
 
 
 def test_more_ranks_than_gpus_is_refused_not_hung():
