@@ -325,6 +325,16 @@ int sq_linear_weight_grad_group(int dtype, int n_members, const void* const* dY,
  * the same layout whose attn.proj / mlp.fc2 BIASES carry the gains.  Give EITHER patches_u8 (uint8 NHWC [n, S, S, 3]:
  * ToTensor + Normalize of compute_features_hdf5.py:53-56 are fused in; S must equal img_size) OR patches_f32_nchw
  * (normalised, the reference's tensor).  out: f32 [n, dim].
+ * Modes: SQ_DTYPE_F32 (exact), SQ_DTYPE_BF16 (fast), SQ_DTYPE_F16X3 (split fp16, the fast parity mode); SQ_DTYPE_BF16X3 is
+ * refused.  SQ_DTYPE_F16X3 keeps the residual stream (patch embedding, token rows) in fp32 and carries the operands of every
+ * product as fp16 hi / lo planes:
+ *   params_exec: the fp16 hi plane [total] followed by the lo plane [total] of the folded weights w'[r, :] = w[r, :] s[r] of
+ *                each GEMM (patch_w, qkv_w, proj_w, fc1_w, fc2_w): LayerScale is folded into proj / fc2 FIRST, then s[r] is the
+ *                power of two that lifts the row's max |w'| into (128, 256] (s = 1 for a zero row);
+ *   bias_exec:   fp32 [2 total]: the first half holds the folded biases as in the other modes, the second half the factors
+ *                1 / s[r] at each GEMM's bias offset (patch_b, qkv_b, proj_b, fc1_b, fc2_b).
+ * An fp16 overflow is not clamped: use sq_uni_forward_checked.  Launch groups: <= 1330 patches of ViT-L/16 at 224 in bf16 and
+ * f16x3, <= 665 in fp32 (2 GiB buffer descriptors).
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_UNI_MAX_DEPTH 32
 typedef struct sq_uni_config { int32_t dim, depth, heads, mlp_dim, img_size; } sq_uni_config;
@@ -340,6 +350,13 @@ size_t sq_uni_workspace_bytes(const sq_uni_config* cfg, int dtype, int n_patches
 int sq_uni_forward(const sq_uni_config* cfg, int dtype, const float* params, const void* params_exec, const float* bias_exec,
                    const uint8_t* patches_u8, const float* patches_f32_nchw, int n_patches, float* out, void* workspace,
                    size_t workspace_bytes, sq_stream_t stream);
+/* The same, with a guard for the reduced range of SQ_DTYPE_F16X3: nonfinite_flag (device word, caller-zeroed, may be NULL)
+ * gets 1 ORed into it when any output feature is not finite.  Nothing saturates: an fp16 plane that overflowed anywhere
+ * upstream (an activation >= 65504) reaches the class token as inf / NaN; the caller re-runs those patches in SQ_DTYPE_F32
+ * (uni.py does). */
+int sq_uni_forward_checked(const sq_uni_config* cfg, int dtype, const float* params, const void* params_exec, const float* bias_exec,
+                           const uint8_t* patches_u8, const float* patches_f32_nchw, int n_patches, float* out, void* workspace,
+                           size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * HE2RNA comparator (/root/reference/src/he2rna.py:42-106, built by src/pretrain_gtex.py:102-105).

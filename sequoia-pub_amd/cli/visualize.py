@@ -139,7 +139,7 @@ def main(argv=None):
     p.add_argument('--resize_factor', type=float, default=None, help='level-0 pixels per 20x pixel (default: aperio.AppMag / 20)')
     p.add_argument('--tile_chunk', type=int, default=TILE_CHUNK, help='tiles per read -> upload -> embed round (and the unit dealt over the ranks under torchrun)')
     p.add_argument('--compute_dtype', default='bf16', choices=['fp32', 'bf16', 'f16x3', 'bf16x3'],
-                   help='f16x3 / bf16x3: the ResNet-50 extractor on split planes (fp32-class features); the aggregator then runs in fp32')
+                   help='f16x3 / bf16x3: the extractor on split planes (fp32-class features; uni: f16x3 only); the aggregator then runs in fp32')
     args = p.parse_args(argv)
     assert args.feat_type in ['resnet', 'uni'] and args.model_type in ['vit', 'vis', 'he2rna']
     # under torchrun: ONE slide over the ranks -- tile chunks for the feature cache, window batches and tile chunks for the
@@ -169,9 +169,9 @@ def main(argv=None):
 
     # ---- feature cache: every valid tile embedded once
     input_dim = 2048 if args.feat_type == 'resnet' else 1024
-    split = args.compute_dtype in ('f16x3', 'bf16x3')          # the ResNet-50 extractor's modes; everything else then runs in fp32
-    if split and args.feat_type != 'resnet':
-        raise SystemExit('--compute_dtype f16x3 / bf16x3 are the ResNet-50 extractor\'s modes; --feat_type uni runs in fp32 or bf16')
+    split = args.compute_dtype in ('f16x3', 'bf16x3')          # the extractor's split modes; everything else then runs in fp32
+    if args.compute_dtype == 'bf16x3' and args.feat_type != 'resnet':
+        raise SystemExit('--compute_dtype bf16x3 is the ResNet-50 extractor\'s mode; --feat_type uni runs in fp32, bf16 or f16x3')
     agg_dtype = 'fp32' if split else args.compute_dtype
     if args.feat_type == 'resnet':
         from ..resnet import resnet50

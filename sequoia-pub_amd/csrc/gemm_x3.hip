@@ -16,6 +16,8 @@
 // Per staged byte a stage carries 1.5x the MFMA work of the plain bf16 ring (both planes are staged once, used twice /
 // once), which is what the load-path-bound shapes of this network want.
 // Epilogue: acc -> LDS (fp32 tile) -> bias + residual (hi + lo) + ReLU -> split -> two 16-byte stores per 8 columns.
+// The UNI form (template flag UNI, fp16 planes, plain products) has the epilogues of a ViT block instead: an fp32 residual
+// (the transformer's residual stream never travels as planes) and the exact-erf GELU of the fp32 mode.
 #include "gemm.h"
 #include "x3_fmt.h"
 
@@ -66,9 +68,10 @@ template <int BM_, int WTN> struct X3Cfg {
     static constexpr int LOADS = 4 + RB;                               // LDS-DMA instructions per thread per stage
 };
 
-template <int BM_, int WTN, bool CONV, bool F16, bool PP, bool DUAL = false>
+template <int BM_, int WTN, bool CONV, bool F16, bool PP, bool DUAL = false, bool UNI = false>
 __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(const GemmArgs p) {
     static_assert(!DUAL || (BM_ == 128 && !CONV && !PP), "the dual form lives in the 128-row two-stage shape");
+    static_assert(!UNI || (F16 && !CONV && !DUAL), "the UNI epilogues are fp16-plane plain products");
     using Cfg = X3Cfg<BM_, WTN>;
     using Fmt = X3Fmt<F16>;
     constexpr int BM = Cfg::BM, NT = Cfg::NT, A_BYTES = Cfg::A_BYTES, ROUND = Cfg::ROUND;
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
 
     // 128-row shape: the identity rows of the epilogue (HBM, the launch's largest read for an expand 1x1) are requested
     // when the last K-tile's loads have been waited for, not when the epilogue needs them
-    const bool res_pre = BM_ == 128 && p.res != nullptr && e_live && !(p.dbg & 64);
+    const bool res_pre = BM_ == 128 && !UNI && p.res != nullptr && e_live && !(p.dbg & 64);
     constexpr int NPRE = BM_ == 128 ? ITER / 2 : 1;      // the first half of the rows (all of them spills)
     u32x4 rpre_h[NPRE], rpre_l[NPRE];
     auto prefetch_res = [&]() {
@@ -480,7 +483,8 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
     __syncthreads();
     if (!e_live) return;
 
-    const bf16_t* resh = p.res ? reinterpret_cast<const bf16_t*>(p.res) : nullptr;
+    const bf16_t* resh = (!UNI && p.res) ? reinterpret_cast<const bf16_t*>(p.res) : nullptr;
+    const float* res32 = (UNI && p.res) ? reinterpret_cast<const float*>(p.res) : nullptr;
     bf16_t* ch = p.out_dtype != SQ_F32 ? reinterpret_cast<bf16_t*>(p.C) : nullptr;
     float* c32 = p.out_dtype == SQ_F32 ? reinterpret_cast<float*>(p.C) : nullptr;
     constexpr int U = 4;
@@ -528,6 +532,18 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
                 x3_join8<F16>(rh[u], rl[u], idn);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += idn[e];
+            }
+            if constexpr (UNI) {
+                if (res32) {
+                    const float* r = res32 + (long long)m * p.ldres + e_n;
+                    const f32x4 r0 = *reinterpret_cast<const f32x4*>(r), r1 = *reinterpret_cast<const f32x4*>(r + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { v[e] += r0[e]; v[4 + e] += r1[e]; }
+                }
+                if (p.act == SQ_ACT_GELU) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = sq_gelu<false>(v[e]);
+                }
             }
             if (p.act == SQ_ACT_RELU) {
 #pragma unroll
@@ -581,6 +597,26 @@ int launch_x3_dual(const GemmArgs& a, hipStream_t stream) {
     return SQ_OK;
 }
 
+// the UNI epilogues (fp32 residual, GELU): fp16 planes, plain products
+template <int BM_, int WTN, bool PP>
+int launch_x3_uni(const GemmArgs& a, hipStream_t stream) {
+    using Cfg = X3Cfg<BM_, WTN>;
+    static SqDevOnce attr;       // hipFuncSetAttribute is per device
+    if (attr.needed()) {
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_x3_kernel<BM_, WTN, false, true, PP, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
+        attr.done();
+    }
+    const int tiles = ((a.M + BM_ - 1) / BM_) * ((a.N + Cfg::BN - 1) / Cfg::BN);
+    hipLaunchKernelGGL((gemm_x3_kernel<BM_, WTN, false, true, PP, false, true>), dim3(tiles), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, a);
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
+}
+
+template <int BM_, bool PP>
+int launch_x3_uni_fmt(const GemmArgs& a, hipStream_t stream) {
+    return a.N % 128 == 0 ? launch_x3_uni<BM_, 2, PP>(a, stream) : launch_x3_uni<BM_, 1, PP>(a, stream);
+}
+
 template <int BM_, bool PP>
 int launch_x3_fmt(const GemmArgs& a, hipStream_t stream) {
     if (a.x3_f16) return a.N % 128 == 0 ? launch_x3<BM_, 2, true, PP>(a, stream) : launch_x3<BM_, 1, true, PP>(a, stream);
@@ -591,6 +627,7 @@ int launch_x3_fmt(const GemmArgs& a, hipStream_t stream) {
 
 // C = act(alpha * A.B^T + bias + res): A, B (and res, and C unless out_dtype == SQ_F32) as hi / lo bf16 planes;
 // a.A / a.B / a.res / a.C point at the hi plane, the lo plane sits plA / plB / plRes / plC ELEMENTS behind it.
+// UNI epilogues (fp16 planes, plain products only): res_dtype == SQ_F32 (an fp32 residual, ldres % 4 == 0) and / or act == GELU.
 int sq_launch_gemm_x3(const GemmArgs& a_in, hipStream_t stream) {
     GemmArgs a = a_in;
     a.dbg |= g_dbg;
@@ -601,10 +638,14 @@ int sq_launch_gemm_x3(const GemmArgs& a_in, hipStream_t stream) {
     SQ_REQUIRE(a.a_bytes > 0 && a.a_bytes < (1ull << 31) && a.b_bytes > 0 && a.b_bytes < (1ull << 31),
                "gemm_x3: operand plane extents must be in (0, 2 GiB): %zu %zu", a.a_bytes, a.b_bytes);
     SQ_REQUIRE(a.out_dtype == SQ_F32 || ((a.out_dtype == SQ_BF16X3 || a.out_dtype == SQ_F16X3) && a.plC != 0 && (a.plC & 7) == 0), "gemm_x3: output is fp32 or hi/lo planes (plC)");
-    SQ_REQUIRE(a.ldc % 8 == 0 && (!a.res || ((a.res_dtype == SQ_BF16X3 || a.res_dtype == SQ_F16X3) && a.ldres % 8 == 0 && a.plRes != 0 && (a.plRes & 7) == 0 && ((uintptr_t)a.res & 15) == 0)),
-               "gemm_x3: ldc / residual planes must allow 16-byte accesses");
-    SQ_REQUIRE(!a.rowbias && !a.Cpre && !a.gelu_grad_of && !a.ln64_g && !a.C2 && (a.act == SQ_ACT_NONE || a.act == SQ_ACT_RELU),
-               "gemm_x3: only bias / residual / ReLU epilogues");
+    const bool uni = a.act == SQ_ACT_GELU || (a.res && a.res_dtype == SQ_F32);
+    SQ_REQUIRE(a.ldc % 8 == 0 && (!a.res || (a.res_dtype == SQ_F32 ? a.ldres % 4 == 0 && ((uintptr_t)a.res & 15) == 0
+                                                                     : ((a.res_dtype == SQ_BF16X3 || a.res_dtype == SQ_F16X3) && a.ldres % 8 == 0 && a.plRes != 0 && (a.plRes & 7) == 0 && ((uintptr_t)a.res & 15) == 0))),
+               "gemm_x3: ldc / residual must allow 16-byte accesses");
+    SQ_REQUIRE(!a.rowbias && !a.Cpre && !a.gelu_grad_of && !a.ln64_g && !a.C2 && (a.act == SQ_ACT_NONE || a.act == SQ_ACT_RELU || a.act == SQ_ACT_GELU),
+               "gemm_x3: only bias / residual / ReLU / GELU epilogues");
+    SQ_REQUIRE(!uni || (a.x3_f16 && !a.conv && !a.A2 && a.act != SQ_ACT_RELU),
+               "gemm_x3: the fp32-residual / GELU epilogues are for fp16-plane plain products without ReLU");
     SQ_REQUIRE((!a.bias || ((uintptr_t)a.bias & 15) == 0) && (!a.colscale || ((uintptr_t)a.colscale & 15) == 0), "gemm_x3: bias / colscale must be 16-byte aligned");
     SQ_REQUIRE(!a.b_tiled || a.K % BK == 0, "gemm_x3: K-tile-major weights need K %% %d == 0 (K=%d)", BK, a.K);
     if (a.conv) SQ_REQUIRE(a.Cin % BK == 0, "conv_x3: Cin=%d must be a multiple of the K-tile (%d)", a.Cin, BK);
@@ -633,7 +674,9 @@ int sq_launch_gemm_x3(const GemmArgs& a_in, hipStream_t stream) {
     }
     // products with K up to this take the 128-row, two-blocks-per-CU shape (sq_dbg_set key 7 overrides: probes; 512 ... 2048 measured level in the pipeline)
     const int small_max_k = g_x3_small_max_k >= 0 ? g_x3_small_max_k : 256;
-    const int rc = dual ? (a.x3_f16 ? launch_x3_dual<true>(a, stream) : launch_x3_dual<false>(a, stream))
+    const bool small = a.K <= small_max_k || (a.N <= 64 && small_max_k > 0);
+    const int rc = uni ? (small ? launch_x3_uni_fmt<128, false>(a, stream) : launch_x3_uni_fmt<256, true>(a, stream))
+                 : dual ? (a.x3_f16 ? launch_x3_dual<true>(a, stream) : launch_x3_dual<false>(a, stream))
                  : (g_x3_halo != 0 && sq_conv_halo_x3_eligible(a)) ? sq_launch_conv_halo_x3(a, stream)
                  : (a.K <= small_max_k || (a.N <= 64 && small_max_k > 0)) ? launch_x3_fmt<128, false>(a, stream)
                  : launch_x3_fmt<256, true>(a, stream);

@@ -18,6 +18,7 @@
 #include "../../include/sequoia_hip.h"
 #include "gemm.h"
 #include "vis.h"
+#include "x3_fmt.h"
 
 namespace {
 
@@ -142,6 +143,102 @@ __global__ __launch_bounds__(256) void uni_ln8_kernel(const float* __restrict__ 
             *reinterpret_cast<f32x4*>(d + 4) = f32x4{o[4], o[5], o[6], o[7]};
         }
     }
+}
+
+// ---- split-fp16 mode (f16x3): the operands of every product travel as fp16 hi / lo planes (x3_fmt.h), the lo plane `pl`
+// ELEMENTS behind the hi plane; the residual stream (E, X, X1) stays fp32.
+
+// the im2col above with its 8 values split into planes: one 16-byte store per plane
+__global__ __launch_bounds__(256) void uni_im2col_x3_kernel(const uint8_t* __restrict__ u8, const float* __restrict__ f32, bf16_t* __restrict__ out,
+                                                            size_t pl, int n, int S) {
+    const int G = S / PS;
+    const uint32_t total = (uint32_t)n * G * G * (KP / 8);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const uint32_t ch = i % (KP / 8), row = i / (KP / 8);
+        const int k0 = ch * 8, c = k0 / (PS * PS), kh = (k0 / PS) % PS, kw0 = k0 % PS;
+        const int px = row % G, py = (row / G) % G, img = row / (G * G);
+        const int y = py * PS + kh, x0 = px * PS + kw0;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (u8) v[e] = ((float)u8[(((size_t)img * S + y) * S + x0 + e) * 3 + c] / 255.0f - MEAN[c]) / STD[c];
+            else v[e] = f32[(((size_t)img * 3 + c) * S + y) * S + x0 + e];
+        }
+        u32x4 hi, lo;
+        x3_split8<true>(v, hi, lo);
+        *reinterpret_cast<u32x4*>(out + (size_t)row * KP + k0) = hi;
+        *reinterpret_cast<u32x4*>(out + pl + (size_t)row * KP + k0) = lo;
+    }
+}
+
+// uni_ln8_kernel writing fp16 planes (the same fp32 statistics and affine, then the split): two 16-byte stores per plane
+template <int NI>
+__global__ __launch_bounds__(256) void uni_ln8_x3_kernel(const float* __restrict__ x, size_t row_stride, const float* __restrict__ g,
+                                                         const float* __restrict__ b, bf16_t* __restrict__ y, size_t pl, int R, float eps) {
+    constexpr int D = 512 * NI;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R) return;
+    const float* xr = x + (size_t)row * row_stride + lane * 8;
+    float v[NI][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const f32x4 t0 = *reinterpret_cast<const f32x4*>(xr + i * 512), t1 = *reinterpret_cast<const f32x4*>(xr + i * 512 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[i][e] = t0[e]; v[i][4 + e] = t1[e]; }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += v[i][e];
+    }
+    const float mean = wave_sum(s) * (1.0f / (float)D);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[i][e] -= mean; q += v[i][e] * v[i][e]; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / (float)D) + eps);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int c = i * 512 + lane * 8;
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(g + c), g1 = *reinterpret_cast<const f32x4*>(g + c + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(b + c), b1 = *reinterpret_cast<const f32x4*>(b + c + 4);
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o[e] = v[i][e] * rstd * g0[e] + b0[e]; o[4 + e] = v[i][4 + e] * rstd * g1[e] + b1[e]; }
+        u32x4 hi, lo;
+        x3_split8<true>(o, hi, lo);
+        *reinterpret_cast<u32x4*>(y + (size_t)row * D + c) = hi;
+        *reinterpret_cast<u32x4*>(y + pl + (size_t)row * D + c) = lo;
+    }
+}
+
+// any D (the small test configurations): the row is read three times from global memory (L1 / L2 hits) instead of being held
+// in a run-time-indexed register array, which would live in scratch
+__global__ __launch_bounds__(256) void uni_ln_x3_kernel(const float* __restrict__ x, size_t row_stride, const float* __restrict__ g,
+                                                        const float* __restrict__ b, bf16_t* __restrict__ y, size_t pl, int R, int D, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R) return;
+    const float* xr = x + (size_t)row * row_stride;
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) s += xr[c];
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+    for (int c = lane; c < D; c += 64) { const float t = xr[c] - mean; q += t * t; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    for (int c = lane; c < D; c += 64) {
+        const float o = (xr[c] - mean) * rstd * g[c] + b[c];
+        const _Float16 h = (_Float16)o;
+        const _Float16 l = (_Float16)(o - (float)h);
+        y[(size_t)row * D + c] = __builtin_bit_cast(bf16_t, h);
+        y[pl + (size_t)row * D + c] = __builtin_bit_cast(bf16_t, l);
+    }
+}
+
+// features non-finite (an fp16 plane overflowed upstream and the inf / NaN reached the class token) -> *flag |= 1
+__global__ void uni_nonfinite_kernel(const float* __restrict__ x, uint32_t total, uint32_t* __restrict__ flag) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        if (!(fabsf(x[i]) <= 3.0e38f)) atomicOr(flag, 1u);
 }
 
 // softmax(q k^T * scale) v for one (image, head): q / k / v rows of this head staged in LDS as fp32,
@@ -356,6 +453,163 @@ __global__ __launch_bounds__(256, 2) void uni_attn_mfma_kernel(const bf16_t* __r
     }
 }
 
+// ---- f16x3 mode: the same core on split-fp16 operands -------------------------------------------------------------
+// The layout of uni_attn_mfma_kernel with every operand as fp16 hi / lo planes (x3_fmt.h) and every product as three fp16
+// MFMAs (hi.hi + hi.lo + lo.hi, fp32 accumulation): K and V of the head, both planes, sit in LDS ([Tp][128 B] each, 4 Tp 128 B
+// <= 128 KiB -- one workgroup per CU), Q comes from global memory as the B operand.  S^T = K Q^T in fp32 accumulators; the softmax
+// is fp32 and max-subtracted; P = exp(S - max) 2^12 (<= 4096: the lo plane of every probability that matters stays a normal
+// fp16 number; the power of two cancels in the division) is split into planes in registers and O^T = V^T P^T is formed the same
+// way, divided by the row sum in fp32 and split into the O planes the proj GEMM reads.  Eight waves: the 7 query tiles of the
+// 224 px grid run side by side (two waves per SIMD), the K / V images are staged once per (image, head).
+constexpr int ATT_X3_WAVES = 8;
+__global__ __launch_bounds__(ATT_X3_WAVES * 64, 1) void uni_attn_x3_kernel(const bf16_t* __restrict__ qkv, size_t plq, bf16_t* __restrict__ o,
+                                                                          size_t plo, int Ttok, int H, float scale) {
+    using F = X3Fmt<true>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int ntile = (Ttok + 31) / 32, Tp = ntile * 32;
+    char* sKh = smem;                                  // [Tp][128 B], 16-byte chunks swizzled by (row >> 1) & 7
+    char* sKl = smem + Tp * 128;
+    char* sVh = smem + 2 * Tp * 128;
+    char* sVl = smem + 3 * Tp * 128;
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int I = H * DH, ldq = 3 * I;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, lh = lane >> 5;
+    const bf16_t* base = qkv + (size_t)b * Ttok * ldq + h * DH;
+    for (int i = tid; i < Tp * 8; i += ATT_X3_WAVES * 64) {     // K / V rows of both planes (zero beyond T)
+        const int r = i >> 3, c = i & 7;
+        u32x4 kh = {0, 0, 0, 0}, kl = kh, vh = kh, vl = kh;
+        if (r < Ttok) {
+            const bf16_t* src = base + (size_t)r * ldq + c * 8;
+            kh = *reinterpret_cast<const u32x4*>(src + I);
+            kl = *reinterpret_cast<const u32x4*>(src + plq + I);
+            vh = *reinterpret_cast<const u32x4*>(src + 2 * I);
+            vl = *reinterpret_cast<const u32x4*>(src + plq + 2 * I);
+        }
+        const int off = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
+        *reinterpret_cast<u32x4*>(sKh + off) = kh;
+        *reinterpret_cast<u32x4*>(sKl + off) = kl;
+        *reinterpret_cast<u32x4*>(sVh + off) = vh;
+        *reinterpret_cast<u32x4*>(sVl + off) = vl;
+    }
+    const int tr_j = (lane >> 2) & 3, tr_c = lane & 3, tr_G = lane >> 4;     // transposing-read geometry (uni_attn_mfma_kernel)
+    const int tr_chunk0 = (tr_G & 1) * 2 + (tr_c >> 1);
+    const int tr_sub = (tr_c & 1) << 3;
+    __syncthreads();
+    for (int qb = wave; qb < ntile; qb += ATT_X3_WAVES) {
+        const int q = qb * 32 + l31;
+        const bf16_t* qrow = base + (size_t)(q < Ttok ? q : Ttok - 1) * ldq;
+        u32x4 qh[4], ql[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            qh[ks] = *reinterpret_cast<const u32x4*>(qrow + ks * 16 + lh * 8);
+            ql[ks] = *reinterpret_cast<const u32x4*>(qrow + plq + ks * 16 + lh * 8);
+        }
+        f32x16 acc[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+            if (t < ntile) {
+                const int kr = t * 32 + l31;
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const int off = kr * 128 + (((2 * ks + lh) ^ ((kr >> 1) & 7)) << 4);
+                    const u32x4 kh = *reinterpret_cast<const u32x4*>(sKh + off), kl = *reinterpret_cast<const u32x4*>(sKl + off);
+                    F::mma(kl, qh[ks], acc[t]);             // the correction terms first, the leading term last
+                    F::mma(kh, ql[ks], acc[t]);
+                    F::mma(kh, qh[ks], acc[t]);
+                }
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (t < ntile) {
+                if (t == ntile - 1) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        if (key >= Ttok) acc[t][r] = -INFINITY;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[t][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        // exp(scale (s - max)) 2^12 = 2^(s c - max c + 12), c = scale log2(e): one fma into v_exp_f32
+        const float cexp = scale * 1.44269504088896340736f, moff = 12.0f - mx * cexp;
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (t < ntile) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float e = __builtin_amdgcn_exp2f(fmaf(acc[t][r], cexp, moff));
+                    acc[t][r] = e;
+                    sum += e;
+                }
+            }
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+        f32x16 ot[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) ot[nt][e] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            if (t < ntile) {
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {           // 16 keys per MFMA k-step: 32t + 16hf ..
+                    const int r0 = 8 * hf;
+                    uint32_t xh[2], xl[2], yh[2], yl[2];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        xh[u] = F::pack2(acc[t][r0 + 2 * u], acc[t][r0 + 2 * u + 1]);
+                        xl[u] = F::rest2(acc[t][r0 + 2 * u], acc[t][r0 + 2 * u + 1], xh[u]);
+                        yh[u] = F::pack2(acc[t][r0 + 4 + 2 * u], acc[t][r0 + 5 + 2 * u]);
+                        yl[u] = F::rest2(acc[t][r0 + 4 + 2 * u], acc[t][r0 + 5 + 2 * u], yh[u]);
+                    }
+                    auto h0 = __builtin_amdgcn_permlane32_swap(xh[0], yh[0], false, false);
+                    auto h1 = __builtin_amdgcn_permlane32_swap(xh[1], yh[1], false, false);
+                    auto g0 = __builtin_amdgcn_permlane32_swap(xl[0], yl[0], false, false);
+                    auto g1 = __builtin_amdgcn_permlane32_swap(xl[1], yl[1], false, false);
+                    const u32x4 ph = {(uint32_t)h0[0], (uint32_t)h1[0], (uint32_t)h0[1], (uint32_t)h1[1]};   // keys base + 8*lh .. +7
+                    const u32x4 pl = {(uint32_t)g0[0], (uint32_t)g1[0], (uint32_t)g0[1], (uint32_t)g1[1]};
+                    const int key0 = t * 32 + hf * 16 + (tr_G >> 1) * 8 + tr_j;
+                    const int key1 = key0 + 4;
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        const int ch = nt * 4 + tr_chunk0;
+                        const int o0 = key0 * 128 + ((ch ^ ((key0 >> 1) & 7)) << 4) + tr_sub;
+                        const int o1 = key1 * 128 + ((ch ^ ((key1 >> 1) & 7)) << 4) + tr_sub;
+                        const u32x2 vh0 = uni_tr_read(sVh + o0), vh1 = uni_tr_read(sVh + o1);
+                        const u32x2 vl0 = uni_tr_read(sVl + o0), vl1 = uni_tr_read(sVl + o1);
+                        const u32x4 vh = {vh0[0], vh0[1], vh1[0], vh1[1]}, vl = {vl0[0], vl0[1], vl1[0], vl1[1]};
+                        F::mma(vl, ph, ot[nt]);
+                        F::mma(vh, pl, ot[nt]);
+                        F::mma(vh, ph, ot[nt]);
+                    }
+                }
+            }
+        // lane = query l31, channels nt*32 + 8g + 4lh .. +3: 8-byte stores per plane
+        if (q < Ttok) {
+            bf16_t* orow = o + ((size_t)b * Ttok + q) * I + h * DH;
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int d0 = nt * 32 + 8 * g + 4 * lh;
+                    const float a0 = ot[nt][4 * g + 0] * inv, a1 = ot[nt][4 * g + 1] * inv, a2 = ot[nt][4 * g + 2] * inv, a3 = ot[nt][4 * g + 3] * inv;
+                    const uint32_t h01 = F::pack2(a0, a1), h23 = F::pack2(a2, a3);
+                    *reinterpret_cast<u32x2*>(orow + d0) = u32x2{h01, h23};
+                    *reinterpret_cast<u32x2*>(orow + plo + d0) = u32x2{F::rest2(a0, a1, h01), F::rest2(a2, a3, h23)};
+                }
+        }
+    }
+}
+
 struct UniBufs {
     void* col; float* E; float* X; float* X1; void* Xn; void* QKV; void* O; void* Hid; float* cls; size_t bytes;
 };
@@ -417,16 +671,100 @@ extern "C" size_t sq_uni_workspace_bytes(const sq_uni_config* c, int dtype, int 
     return b.bytes;
 }
 
-// params: fp32 flat buffer (sq_uni_layout) -- biases, LayerNorm and embeddings are read from it;
-// params_exec: the GEMM weights in the compute dtype with LayerScale folded into proj / fc2 (same layout; fp32 mode may
-// pass a folded fp32 copy, bf16 mode a folded bf16 copy).  bias_exec: fp32 copy of the flat buffer whose proj / fc2
-// biases are folded likewise (may equal params when every ls == 1).
-extern "C" int sq_uni_forward(const sq_uni_config* c, int dtype, const float* params, const void* params_exec, const float* bias_exec,
-                              const uint8_t* patches_u8, const float* patches_f32_nchw, int n, float* out, void* workspace,
-                              size_t workspace_bytes, sq_stream_t stream_) {
-    if (int e = check_cfg(c)) return e;
-    hipStream_t s = (hipStream_t)stream_;
-    SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16, "uni_forward: dtype %d", dtype);
+namespace {
+
+// f16x3: the block structure of the fp32 / bf16 path below with every product on gemm_x3's UNI epilogues.  Planes: col, Xn, QKV,
+// O and Hid hold a hi plane followed by a lo plane of the same extent; params_exec the hi plane [total] then the lo plane [total]
+// of the folded, row-scaled weights; bias_exec the folded biases [total] then the factors 1 / s [total] (include/sequoia_hip.h).
+int uni_forward_x3(const sq_uni_config* c, const float* params, const void* params_exec, const float* bias_exec, const uint8_t* patches_u8,
+                   const float* patches_f32_nchw, int n, float* out, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const int D = c->dim, H = c->heads, Mh = c->mlp_dim, S = c->img_size, G = S / PS, NP = G * G, T = NP + 1;
+    const size_t Mt = (size_t)n * T;
+    // every plane is addressed through a 31-bit buffer descriptor: the widest is [n * tokens, max(3 dim, mlp_dim)] fp16
+    SQ_REQUIRE(Mt * (size_t)(Mh > 3 * D ? Mh : 3 * D) * 2 < (1ull << 31) && (size_t)n * NP * KP * 2 < (1ull << 31),
+               "uni_forward: a launch group of %d patches exceeds the 2 GiB buffer-descriptor limit of one fp16 plane (ViT-L/16 at 224: <= 1330 patches in f16x3)", n);
+    sq_uni_layout lay;
+    if (int e = sq_uni_layout_init(c, &lay)) return e;
+    UniBufs w;
+    uni_bufs(*c, SQ_F16X3, n, (char*)workspace, &w);
+    if (w.bytes > workspace_bytes) {
+        sq_set_error("uni_forward: workspace %zu < required %zu", workspace_bytes, w.bytes);
+        return SQ_ERR_WORKSPACE;
+    }
+    const size_t plW = (size_t)lay.total;
+    const bf16_t* Wh = reinterpret_cast<const bf16_t*>(params_exec);
+    auto Pf = [&](int64_t off) { return params + off; };
+    auto grid_for = [](size_t work) { size_t nb = (work + 255) / 256; return (int)(nb > 65535 ? 65535 : (nb ? nb : 1)); };
+    bf16_t* col = (bf16_t*)w.col; bf16_t* Xn = (bf16_t*)w.Xn; bf16_t* QKV = (bf16_t*)w.QKV; bf16_t* O = (bf16_t*)w.O; bf16_t* Hid = (bf16_t*)w.Hid;
+    const size_t plCol = (size_t)n * NP * KP, plXn = Mt * D, plQKV = Mt * 3 * D, plO = Mt * D, plHid = Mt * Mh;
+    // one product: A planes [M, K] (lda) x the weight rows at w_off [N, K] (ldb = K) -> colscale 1 / s, folded bias at b_off
+    auto gemm = [&](const bf16_t* A, size_t plA, int lda, size_t a_elems, int64_t w_off, int64_t b_off, int M, int N, int K, int act,
+                    const float* res, int ldres, void* C, size_t plC, int ldc) -> int {
+        GemmArgs g;
+        g.x3_f16 = 1;
+        g.A = A; g.plA = (long long)plA; g.lda = lda; g.a_bytes = a_elems * 2;
+        g.B = Wh + w_off; g.plB = (long long)plW; g.ldb = K; g.b_bytes = (plW - (size_t)w_off) * 2;
+        g.bias = bias_exec + b_off; g.colscale = bias_exec + plW + b_off; g.act = act;
+        if (res) { g.res = res; g.res_dtype = SQ_F32; g.ldres = ldres; }
+        g.C = C; g.ldc = ldc;
+        if (plC) { g.out_dtype = SQ_F16X3; g.plC = (long long)plC; } else g.out_dtype = SQ_F32;
+        g.M = M; g.N = N; g.K = K;
+        return sq_launch_gemm_x3(g, s);
+    };
+    auto ln = [&](const float* x, size_t stride, int64_t gg, int64_t bb, int R) -> int {
+        const bool v8 = D == 1024 && stride % 4 == 0 && (((uintptr_t)x | (uintptr_t)Xn | (uintptr_t)Pf(gg) | (uintptr_t)Pf(bb)) & 15) == 0;
+        if (v8) hipLaunchKernelGGL((uni_ln8_x3_kernel<2>), dim3((R + 3) / 4), dim3(256), 0, s, x, stride, Pf(gg), Pf(bb), Xn, plXn, R, 1e-6f);
+        else hipLaunchKernelGGL(uni_ln_x3_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, stride, Pf(gg), Pf(bb), Xn, plXn, R, D, 1e-6f);
+        SQ_LAUNCH_CHECK();
+        return SQ_OK;
+    };
+
+    hipLaunchKernelGGL(uni_im2col_x3_kernel, dim3(grid_for((size_t)n * NP * (KP / 8))), dim3(256), 0, s, patches_u8, patches_f32_nchw, col, plCol, n, S);
+    SQ_LAUNCH_CHECK();
+    if (int e = gemm(col, plCol, KP, plCol, lay.patch_w, lay.patch_b, n * NP, D, KP, SQ_ACT_NONE, nullptr, 0, w.E, 0, D)) return e;
+    hipLaunchKernelGGL(uni_tokens_kernel, dim3(grid_for(Mt * D / 4)), dim3(256), 0, s, (const float4*)w.E, (const float4*)Pf(lay.cls),
+                       (const float4*)Pf(lay.pos), (float4*)w.X, n, T, D / 4);
+    SQ_LAUNCH_CHECK();
+
+    const int Tp = (T + 31) / 32 * 32;
+    const size_t att_lds = (size_t)4 * Tp * 128;          // K and V, both planes: <= 128 KiB (T <= 256, check_cfg)
+    static SqDevOnce attr;       // hipFuncSetAttribute is per device
+    if (attr.needed()) {
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * ATT_MAXT * 128));
+        attr.done();
+    }
+    float* X = w.X;
+    float* X1 = w.X1;
+    for (int l = 0; l < c->depth; ++l) {
+        const sq_uni_layer_offsets& L = lay.layer[l];
+        if (int e = ln(X, (size_t)D, L.ln1_g, L.ln1_b, (int)Mt)) return e;
+        if (int e = gemm(Xn, plXn, D, plXn, L.qkv_w, L.qkv_b, (int)Mt, 3 * D, D, SQ_ACT_NONE, nullptr, 0, QKV, plQKV, 3 * D)) return e;
+        hipLaunchKernelGGL(uni_attn_x3_kernel, dim3(n * H), dim3(ATT_X3_WAVES * 64), att_lds, s, (const bf16_t*)QKV, plQKV, O, plO, T, H, 0.125f);
+        SQ_LAUNCH_CHECK();
+        // the last block: projection, LayerNorm and MLP on the n class rows only (as in the fp32 / bf16 path)
+        const bool cls_only = l == c->depth - 1;
+        const int R = cls_only ? n : (int)Mt;
+        const int ldr = cls_only ? T * D : D;
+        if (int e = gemm(O, plO, ldr, plO, L.proj_w, L.proj_b, R, D, D, SQ_ACT_NONE, X, ldr, X1, 0, D)) return e;     // x1 = x + ls1 (o Wp^T + bp)
+        if (int e = ln(X1, (size_t)D, L.ln2_g, L.ln2_b, R)) return e;
+        if (int e = gemm(Xn, plXn, D, plXn, L.fc1_w, L.fc1_b, R, Mh, D, SQ_ACT_GELU, nullptr, 0, Hid, plHid, Mh)) return e;
+        if (int e = gemm(Hid, plHid, Mh, plHid, L.fc2_w, L.fc2_b, R, D, Mh, SQ_ACT_NONE, X1, D, X, 0, D)) return e;      // x = x1 + ls2 (h W2^T + b2)
+    }
+    // features = LN(x)[cls] in fp32, as in the other modes
+    const bool v8 = D == 1024 && (((uintptr_t)X | (uintptr_t)out | (uintptr_t)Pf(lay.norm_g) | (uintptr_t)Pf(lay.norm_b)) & 15) == 0;
+    if (v8) hipLaunchKernelGGL((uni_ln8_kernel<float, 2>), dim3((n + 3) / 4), dim3(256), 0, s, X, (size_t)D, Pf(lay.norm_g), Pf(lay.norm_b), out, n, 1e-6f);
+    else hipLaunchKernelGGL(uni_ln_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, s, X, (size_t)D, Pf(lay.norm_g), Pf(lay.norm_b), out, n, D, 1e-6f);
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
+}
+
+}  // namespace
+
+namespace {
+
+int uni_forward_f32_bf16(const sq_uni_config* c, int dtype, const float* params, const void* params_exec, const float* bias_exec,
+                         const uint8_t* patches_u8, const float* patches_f32_nchw, int n, float* out, void* workspace,
+                         size_t workspace_bytes, hipStream_t s) {
     SQ_REQUIRE(params && params_exec && bias_exec && out && workspace, "uni_forward: null pointer");
     SQ_REQUIRE((patches_u8 != nullptr) != (patches_f32_nchw != nullptr), "uni_forward: give exactly one of patches_u8 / patches_f32_nchw");
     SQ_REQUIRE(n >= 1, "uni_forward: n=%d", n);
@@ -532,4 +870,38 @@ extern "C" int sq_uni_forward(const sq_uni_config* c, int dtype, const float* pa
     }
     // features = LN(x)[cls] (forward_head with global_pool='token', num_classes=0): the class rows, packed by the last block
     return ln(X, (size_t)D, lay.norm_g, lay.norm_b, out, SQ_F32, n);
+}
+
+}  // namespace
+
+extern "C" int sq_uni_forward_checked(const sq_uni_config* c, int dtype, const float* params, const void* params_exec, const float* bias_exec,
+                                      const uint8_t* patches_u8, const float* patches_f32_nchw, int n, float* out, void* workspace,
+                                      size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream_) {
+    if (int e = check_cfg(c)) return e;
+    SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16 || dtype == SQ_F16X3,
+               "uni_forward: dtype %d (UNI runs f32, bf16 or f16x3; the bf16 planes of SQ_DTYPE_BF16X3 are the ResNet-50 embedder's)", dtype);
+    SQ_REQUIRE(params && params_exec && bias_exec && out && workspace, "uni_forward: null pointer");
+    SQ_REQUIRE((patches_u8 != nullptr) != (patches_f32_nchw != nullptr), "uni_forward: give exactly one of patches_u8 / patches_f32_nchw");
+    SQ_REQUIRE(n >= 1, "uni_forward: n=%d", n);
+    hipStream_t s = (hipStream_t)stream_;
+    const int e = dtype == SQ_F16X3 ? uni_forward_x3(c, params, params_exec, bias_exec, patches_u8, patches_f32_nchw, n, out, workspace, workspace_bytes, s)
+                                    : uni_forward_f32_bf16(c, dtype, params, params_exec, bias_exec, patches_u8, patches_f32_nchw, n, out, workspace, workspace_bytes, s);
+    if (e) return e;
+    if (nonfinite_flag) {
+        const uint32_t total = (uint32_t)n * (uint32_t)c->dim;
+        hipLaunchKernelGGL(uni_nonfinite_kernel, dim3((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256), dim3(256), 0, s, out, total, nonfinite_flag);
+        SQ_LAUNCH_CHECK();
+    }
+    return SQ_OK;
+}
+
+// params: fp32 flat buffer (sq_uni_layout) -- biases, LayerNorm and embeddings are read from it;
+// params_exec: the GEMM weights in the compute dtype with LayerScale folded into proj / fc2 (same layout; fp32 mode may
+// pass a folded fp32 copy, bf16 mode a folded bf16 copy, f16x3 mode the row-scaled fp16 planes).  bias_exec: fp32 copy of the
+// flat buffer whose proj / fc2 biases are folded likewise (may equal params when every ls == 1); f16x3: followed by the 1 / s factors.
+extern "C" int sq_uni_forward(const sq_uni_config* c, int dtype, const float* params, const void* params_exec, const float* bias_exec,
+                              const uint8_t* patches_u8, const float* patches_f32_nchw, int n, float* out, void* workspace,
+                              size_t workspace_bytes, sq_stream_t stream_) {
+    return sq_uni_forward_checked(c, dtype, params, params_exec, bias_exec, patches_u8, patches_f32_nchw, n, out, workspace, workspace_bytes,
+                                  nullptr, stream_);
 }

@@ -38,6 +38,7 @@ vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 _lib.register_signature("sq_uni_layout_init", i32, [ctypes.POINTER(UniConfig), ctypes.POINTER(UniLayout)])
 _lib.register_signature("sq_uni_workspace_bytes", sz, [ctypes.POINTER(UniConfig), i32, i32])
 _lib.register_signature("sq_uni_forward", i32, [ctypes.POINTER(UniConfig), i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp])
+_lib.register_signature("sq_uni_forward_checked", i32, [ctypes.POINTER(UniConfig), i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp, vp])
 
 
 def tensor_map(cfg, lay):
@@ -69,6 +70,55 @@ def _numel(shape):
     return n
 
 
+def _gemm_blocks(cfg, lay):
+    """(weight offset, rows, row length, bias offset) of every product of the network, in launch order."""
+    D, M = cfg.dim, cfg.mlp_dim
+    out = [(lay.patch_w, D, 3 * 16 * 16, lay.patch_b)]
+    for i in range(cfg.depth):
+        L = lay.layer[i]
+        out += [(L.qkv_w, 3 * D, D, L.qkv_b), (L.proj_w, D, D, L.proj_b), (L.fc1_w, M, D, L.fc1_b), (L.fc2_w, D, M, L.fc2_b)]
+    return out
+
+
+def fold_layer_scale(flat, lay, cfg):
+    """A copy of the flat buffer with the LayerScale gains folded into attn.proj / mlp.fc2 (weight rows and biases)."""
+    w = flat.detach().clone()
+    D, M = cfg.dim, cfg.mlp_dim
+    for i in range(cfg.depth):
+        L = lay.layer[i]
+        for w_off, b_off, g_off, k in ((L.proj_w, L.proj_b, L.ls1, D), (L.fc2_w, L.fc2_b, L.ls2, M)):
+            gam = w[g_off:g_off + D]
+            w[w_off:w_off + D * k] = (w[w_off:w_off + D * k].view(D, k) * gam[:, None]).reshape(-1)
+            w[b_off:b_off + D] = w[b_off:b_off + D] * gam
+    return w
+
+
+def split_exec_planes(flat, lay, cfg):
+    """fp32 flat buffer -> (params_exec, bias_exec) of the split-fp16 mode (include/sequoia_hip.h, sq_uni_forward):
+    LayerScale folded into proj / fc2 first; every GEMM weight row then scaled by s, the power of two that lifts its max |w'|
+    into (128, 256] (1 for a zero row), so that the lo plane (<= 2^-11 of the value) stays a normal fp16 number for every weight
+    that matters in the row; params_exec = fp16 hi plane [total] then lo plane [total] (as int16); bias_exec = the folded fp32
+    buffer [total] then the factors 1 / s at each GEMM's bias offset [total] (1 elsewhere).  Pure tensor code: runs on CPU too."""
+    w = fold_layer_scale(flat, lay, cfg)
+    bias = w.clone()
+    factor = torch.ones_like(w)
+    for w_off, rows, k, b_off in _gemm_blocks(cfg, lay):
+        blk = w[w_off:w_off + rows * k].view(rows, k)
+        amax = blk.abs().amax(dim=1).double()
+        s = torch.where(amax > 0, torch.exp2(torch.floor(torch.log2(256.0 / amax.clamp_min(1e-30)))), torch.ones_like(amax))
+        s = s.clamp(2.0 ** -20, 2.0 ** 20).to(w.dtype)
+        blk.mul_(s[:, None])                             # exact: powers of two
+        factor[b_off:b_off + rows] = 1.0 / s
+    # the planes of everything outside the GEMM weights are never read: zero there (no fp16 overflow of embeddings)
+    mask = torch.zeros_like(w, dtype=torch.bool)
+    for w_off, rows, k, _ in _gemm_blocks(cfg, lay):
+        mask[w_off:w_off + rows * k] = True
+    w = torch.where(mask, w, torch.zeros_like(w))
+    hi = w.to(torch.float16)
+    lo = (w - hi.float()).to(torch.float16)
+    return torch.cat([hi, lo]).view(torch.int16), torch.cat([bias, factor])
+
+
 class UniViT(nn.Module):
     """timm VisionTransformer subset: ViT with class token, learned position embedding, LayerScale, token pooling,
     no classifier head.  ``forward(x f32 [B, 3, S, S]) -> f32 [B, dim]``."""
@@ -83,6 +133,9 @@ class UniViT(nn.Module):
         _lib.check(_lib.lib().sq_uni_layout_init(ctypes.byref(self.cfg), ctypes.byref(self.layout)))
         self._tmap = tensor_map(self.cfg, self.layout)
         self.compute_dtype = _lib.DTYPES[compute_dtype]
+        if self.compute_dtype == _lib.SQ_BF16X3:
+            raise ValueError("UniViT: compute_dtype 'bf16x3' is the ResNet-50 embedder's split mode; UNI's split mode is 'f16x3'")
+        self._init_values = init_values
         flat = torch.zeros(self.layout.total, dtype=torch.float32)
         # timm's init: trunc_normal(std .02) embeddings / Linear weights, zero biases, LayerNorm 1 / 0, LayerScale init_values
         g = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 31))
@@ -134,20 +187,53 @@ class UniViT(nn.Module):
         key = (dev, self.compute_dtype, self.flat._version)
         if self._exec_key == key:
             return self._exec
-        w = self.flat.detach().clone()
-        D, M = self.cfg.dim, self.cfg.mlp_dim
-        for i in range(self.cfg.depth):
-            L = self.layout.layer[i]
-            for w_off, b_off, g_off, k in ((L.proj_w, L.proj_b, L.ls1, D), (L.fc2_w, L.fc2_b, L.ls2, M)):
-                gam = w[g_off:g_off + D]
-                w[w_off:w_off + D * k] = (w[w_off:w_off + D * k].view(D, k) * gam[:, None]).reshape(-1)
-                w[b_off:b_off + D] = w[b_off:b_off + D] * gam
+        if self.compute_dtype == _lib.SQ_F16X3:
+            weights_exec, bias_exec = split_exec_planes(self.flat, self.layout, self.cfg)
+            self._exec, self._exec_key = (weights_exec, bias_exec), key
+            return self._exec
+        w = fold_layer_scale(self.flat, self.layout, self.cfg)
         bias_exec = w                                                   # fp32, folded biases (weights in it are unused)
         weights_exec = w.to(torch.bfloat16) if self.compute_dtype == _lib.SQ_BF16 else w
         self._exec, self._exec_key = (weights_exec, bias_exec), key
         return self._exec
 
-    def _run(self, patches_u8=None, x_f32=None, slot=0):
+    # ---- the reduced range of the split-fp16 mode ----------------------------------------------------------------
+    def exact_twin(self):
+        """The same network in the exact fp32 mode (a copy of the parameters, refreshed only when they changed): what a launch
+        group is re-run in when the split-fp16 mode overflowed (an activation >= 65504; sq_uni_forward_checked)."""
+        key = (self.flat.device, self.flat._version)
+        tw = self.__dict__.get("_twin")
+        if tw is None:
+            c = self.cfg
+            tw = UniViT(embed_dim=c.dim, depth=c.depth, num_heads=c.heads, mlp_ratio=c.mlp_dim / c.dim, img_size=c.img_size,
+                        init_values=self._init_values, compute_dtype="fp32")
+            self.__dict__["_twin"] = tw                  # not a registered submodule: state_dict() keeps timm's keys
+            self.__dict__["_twin_key"] = None
+        if self.__dict__.get("_twin_key") != key or tw.flat.device != self.flat.device:
+            with torch.no_grad():
+                tw.flat = nn.Parameter(self.flat.detach().clone(), requires_grad=False)
+            tw._exec_key = None                          # a fresh tensor restarts its version counter: drop the twin's folded copy
+            self.__dict__["_twin_key"] = key
+        return tw
+
+    def new_flag(self):
+        """A zeroed device word for sq_uni_forward_checked's non-finite flag."""
+        return torch.zeros(1, dtype=torch.int32, device=self.flat.device)
+
+    def _resolve_nonfinite(self, feats, flag, on_nonfinite, rerun):
+        """Read the flag (host sync); overflowed -> raise, or re-run in fp32 (`rerun()` returns the exact features)."""
+        if flag is None or int(flag.item()) == 0:
+            return feats
+        msg = ("UniViT in split-fp16 mode (f16x3): an activation left fp16's range (>= 65504) and the features are not finite"
+               " -- unusual weights")
+        if on_nonfinite == "raise":
+            raise _lib.SequoiaHipError(msg + "; use compute_dtype='fp32' for this checkpoint")
+        import warnings
+        warnings.warn(msg + "; this launch group is re-run in exact fp32", RuntimeWarning, stacklevel=3)
+        self.last_nonfinite_reruns = getattr(self, "last_nonfinite_reruns", 0) + 1
+        return rerun()
+
+    def _run(self, patches_u8=None, x_f32=None, slot=0, flag=None):
         _lib.require_gpu()
         if not self.flat.is_cuda:
             raise _lib.SequoiaHipError("UniViT parameters are on the CPU: call .to('cuda') first (no CPU fallback)")
@@ -165,35 +251,54 @@ class UniViT(nn.Module):
         if ws is None or ws.numel() < need or ws.device != dev:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sq_uni_forward(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(wx), _lib.ptr(bx),
-                                                 _lib.ptr(patches_u8), _lib.ptr(x_f32), n, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream_ptr(dev)))
+            _lib.check(_lib.lib().sq_uni_forward_checked(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(wx),
+                                                         _lib.ptr(bx), _lib.ptr(patches_u8), _lib.ptr(x_f32), n, _lib.ptr(out), _lib.ptr(ws),
+                                                         ws.numel(), _lib.ptr(flag) if flag is not None else None, _lib.stream_ptr(dev)))
         return out
 
     @torch.no_grad()
-    def forward(self, x):
-        """timm's ``model(image)`` with num_classes=0: f32 [B, 3, S, S] (normalised) -> f32 [B, dim]."""
-        return self._run(x_f32=x.to(self.flat.device, torch.float32).contiguous())
+    def forward(self, x, on_nonfinite="rerun"):
+        """timm's ``model(image)`` with num_classes=0: f32 [B, 3, S, S] (normalised) -> f32 [B, dim].  Split-fp16 mode: an
+        overflow is handled per `on_nonfinite` ("rerun" / "raise", as in extract_patches_u8)."""
+        x = x.to(self.flat.device, torch.float32).contiguous()
+        if self.compute_dtype != _lib.SQ_F16X3:
+            return self._run(x_f32=x)
+        flag = self.new_flag()
+        feats = self._run(x_f32=x, flag=flag)
+        return self._resolve_nonfinite(feats, flag, on_nonfinite, lambda: self.exact_twin()._run(x_f32=x))
 
     def max_sub_batch(self, S=None):
         """Largest launch group the 2 GiB buffer-descriptor limit allows (sq_uni_forward's check): the widest activation is
         [n * tokens, max(3 dim, mlp_dim)] in the compute dtype."""
         S = S or self.cfg.img_size
         tokens = (S // 16) ** 2 + 1
-        es = 2 if self.compute_dtype == _lib.SQ_BF16 else 4
+        es = 4 if self.compute_dtype == _lib.SQ_F32 else 2          # f16x3: per fp16 plane
         return max(1, ((1 << 31) - 1) // (tokens * max(3 * self.cfg.dim, self.cfg.mlp_dim) * es))
 
     @torch.no_grad()
-    def extract_patches_u8(self, patches, sub_batch=128):
+    def extract_patches_u8(self, patches, sub_batch=128, on_nonfinite="rerun", flag=None):
         """uint8 HWC patches [n, S, S, 3] -> f32 [n, dim]; fuses the ToTensor + Normalize of compute_features_hdf5.py:53-56.
         Launch groups of <= sub_batch patches (clamped to the descriptor limit); larger groups are faster -- the 256 x 256 GEMM
-        tiles then fill more rounds (bench: 6.09 / 6.38 / 6.58 slides/s at 256 / 500 / 1000)."""
+        tiles then fill more rounds (bench: 6.09 / 6.38 / 6.58 slides/s at 256 / 500 / 1000).
+        Split-fp16 mode: features that came out non-finite (an activation beyond fp16's range) are, per `on_nonfinite`, re-run
+        in exact fp32 with a warning ("rerun", one host sync per call), reported by an exception ("raise"), or left to the
+        caller ("defer": no sync; pass `flag`, a zeroed int32 device word from new_flag(), and check it later -- SlidePipeline
+        does)."""
         dev = self.flat.device
         patches = torch.as_tensor(patches)
         if patches.shape[0] == 0:
             return torch.empty(0, self.cfg.dim, dtype=torch.float32, device=dev)
+        if on_nonfinite not in ("rerun", "raise", "defer"):
+            raise ValueError(f"on_nonfinite={on_nonfinite!r}: 'rerun', 'raise' or 'defer'")
         sub_batch = max(1, min(int(sub_batch), self.max_sub_batch(patches.shape[1])))
-        return torch.cat([self._run(patches_u8=patches[i:i + sub_batch].to(dev).contiguous())
+        if self.compute_dtype == _lib.SQ_F16X3:
+            if on_nonfinite != "defer":
+                flag = self.new_flag()
+                feats = self.extract_patches_u8(patches, sub_batch, "defer", flag)
+                return self._resolve_nonfinite(feats, flag, on_nonfinite, lambda: self.exact_twin().extract_patches_u8(patches, sub_batch))
+        else:
+            flag = None
+        return torch.cat([self._run(patches_u8=patches[i:i + sub_batch].to(dev).contiguous(), flag=flag)
                           for i in range(0, patches.shape[0], sub_batch)], 0)
 
 
