@@ -1,25 +1,31 @@
 #!/usr/bin/env python
 """bench.py -- slides/sec of the SEQUOIA hot path on MI355X (driver contract in the task brief).
 
-    python bench.py --gpus N --steps K --warmup W [--workload pipeline|vis_train|vis_fwd|train_kfold|spatial] [--dtype bf16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--workload pipeline|vis_train|vis_fwd|train_kfold|spatial] [--dtype bf16|fp32] [--full]
 
 Default workload = the headline configuration of BASELINE.json's metric (config 3) AS STATED: 1000 x 224 x 224 uint8
 patches per slide, streamed from pinned host memory every step -> ResNet-50 embed -> k-Means(100) -> ViS forward, in the
 parity-grade mode (``f16x3``: fp16 hi/lo planes, three MFMAs per product, fp32 accumulation -- the reference's fp32
-results to ~1e-6, cluster labels bit-equal).  The line carries ``accuracy_vs_reference`` (the golden slide of
-tests/golden/pipeline_slide.npz through the same pipeline in the same mode) and ``secondary``: the resident twin (upload
-outside the timed region), the plain-bf16 throughput mode with ITS accuracy figures, the exact-fp32 mode, BASELINE
-config 2 (``vis_train``), the UNI embedder and config 5, each timed the same way in a fresh process.
+results to ~1e-6, cluster labels bit-equal).
 
 One process per GPU: with --gpus N > 1 and no WORLD_SIZE in the environment bench.py starts the N ranks itself
 (torch.distributed.run); slides are independent units, so ranks shard them with no data-path collective.  Only the
 training workloads have an exchange step: the RCCL all-reduce of the flat gradient buffer.
 
-Prints ONE JSON line on rank 0 with the headline value plus:
+A plain run sets the workload up, warms up, times the steps, writes --dump-outputs if asked and prints ONE JSON line on
+rank 0 with the headline value (and nothing else that costs time).  --full adds (all but `power` after the timed region):
   roofline     -- dominant kernel, algorithmic FLOP (or bytes) per launch / HIP-event duration,
-                  measured on the launch stream in extra instrumented steps after the timed region
+                  measured on the launch stream in extra instrumented steps after the timed region; ``traffic`` from
+                  rocprofv3 --pmc passes in child processes (default workload, --measure-traffic for the others)
+  power        -- package power and shader clock sampled during the timed region
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference's torch-CPU path) timed on
                   this host's cores on a bounded sample of the same workload (rank 0, N=1 only)
+  check        -- train_kfold: folds run, parameters identical on every rank, their sums
+  accuracy_vs_reference -- pipeline: the golden slides of tests/golden/pipeline_slide*.npz through the same pipeline
+                  in the same mode
+  secondary    -- default workload: the resident twin (upload outside the timed region), the plain-bf16 throughput mode
+                  with ITS accuracy figures, the exact-fp32 mode, 256 px patches, BASELINE configs 2 and 4, the UNI
+                  embedder and config 5, each timed the same way in a fresh process (itself run with --full)
 """
 import argparse
 import json
@@ -112,8 +118,9 @@ class PowerSampler:
 LAST_POWER = [None]
 
 
-def timed_region(step_fn, steps, warmup, world, device, flush_fn=None):
-    """Returns (seconds, (what the last timed step returned, what the closing flush returned))."""
+def timed_region(step_fn, steps, warmup, world, device, flush_fn=None, power=False):
+    """Returns (seconds, (what the last timed step returned, what the closing flush returned)).  power: sample package power
+    and clock during the timed steps (rank 0, --full)."""
     last = tail = None
     for _ in range(warmup):
         step_fn()
@@ -121,7 +128,8 @@ def timed_region(step_fn, steps, warmup, world, device, flush_fn=None):
         flush_fn()
     barrier_sync(world)
     rank = int(os.environ.get("RANK", "0"))
-    sampler = PowerSampler(device.index if hasattr(device, "index") and device.index is not None else 0) if rank == 0 and not os.environ.get("SQ_BENCH_NO_POWER") else None
+    sampler = PowerSampler(device.index if hasattr(device, "index") and device.index is not None else 0) \
+        if power and rank == 0 and not os.environ.get("SQ_BENCH_NO_POWER") else None
     if sampler:
         sampler.__enter__()
     t0 = time.perf_counter()
@@ -279,7 +287,8 @@ def measure_traffic(roof, args, recs=()):
     (FETCH_SIZE counts 64 B per 128-byte request on gfx950: doubled; KiB units).  `roofline.traffic` = the dominant class;
     `roofline.traffic_by_class` = every split-mode class whose launch geometry follows from its name (plain and dual products,
     halo-staged 3x3, the 56x56 tails, the 28x28 / 14x14 chains, the stem) with its algorithmic bytes and the wasted-traffic ratio.
-    Runs by default for the default workload when rocprofv3 is on the box (--no-measure-traffic: the committed pass instead)."""
+    Runs by default in a --full run of the default workload when rocprofv3 is on the box (--no-measure-traffic: the committed
+    pass instead)."""
     import csv
     import glob
     import shutil
@@ -305,7 +314,7 @@ def measure_traffic(roof, args, recs=()):
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable,
                    os.path.abspath(__file__), "--workload", args.workload, "--dtype", args.dtype, "--slides", "1", "--steps", "1", "--warmup", "0",
                    "--patches", str(args.patches), "--patch-size", str(args.patch_size), "--sub-batch", str(args.sub_batch),
-                   "--no-secondary", "--no-cpu-baseline", "--no-accuracy", "--no-measure-traffic"]
+                   "--full", "--no-secondary", "--no-cpu-baseline", "--no-accuracy", "--no-measure-traffic"]
             # no power sampler in the profiled child: rocm-smi started there would inherit the profiler's preload
             subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", SQ_BENCH_NO_POWER="1"), capture_output=True, text=True, timeout=900)
             rows = []
@@ -364,7 +373,7 @@ def measure_traffic_marked(roof, args, recs=()):
                    "--batch", str(args.batch), "--epochs", str(args.epochs), "--slides", str(1 if args.workload == "pipeline" else args.slides),
                    "--patches", str(args.patches), "--patch-size", str(args.patch_size), "--sub-batch", str(args.sub_batch),
                    "--uni-sub-batch", str(args.uni_sub_batch), "--grid", str(args.grid[0]), str(args.grid[1]), "--batch-windows", str(args.batch_windows),
-                   "--embedder", args.embedder, "--no-secondary", "--no-cpu-baseline", "--no-accuracy", "--no-measure-traffic"]
+                   "--embedder", args.embedder, "--full", "--no-secondary", "--no-cpu-baseline", "--no-accuracy", "--no-measure-traffic"]
             subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", SQ_PROF_MARKERS=names_file, SQ_BENCH_NO_POWER="1"),
                            capture_output=True, text=True, timeout=900)
             if not os.path.exists(names_file):
@@ -882,9 +891,10 @@ def spawn_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
-def measure(name, args, rank, world, device, want_roofline=True, want_cpu=True):
-    """Build workload `name`, time it (barrier + synchronize on both sides, max over ranks), optionally profile the
-    dominant kernel and the CPU baseline.  Returns the fields of a bench line for this workload."""
+def measure(name, args, rank, world, device, full=False):
+    """Build workload `name`, time it (barrier + synchronize on both sides, max over ranks); with `full` also sample power
+    during the timed steps, then profile the dominant kernel, time the CPU baseline and run the workload's check.  Returns
+    the fields of a bench line for this workload."""
     wl = WORKLOADS[name](args, rank, world, device)
     steps, warmup = args.steps, args.warmup
     if steps is None:
@@ -904,7 +914,7 @@ def measure(name, args, rank, world, device, want_roofline=True, want_cpu=True):
             torch.distributed.all_reduce(est, op=torch.distributed.ReduceOp.MAX)
         steps = int(min(2000, max(5, math.ceil(2.5 / max(float(est.item()), 1e-4)))))
         warmup = 0 if warmup is None else max(0, warmup - 1)
-    dt, last = timed_region(wl["step"], steps, warmup, world, device, wl.get("flush"))
+    dt, last = timed_region(wl["step"], steps, warmup, world, device, wl.get("flush"), power=full)
     if args.dump_outputs and rank == 0:
         dump_outputs(wl["outputs"](*last), args.dump_outputs)       # before the instrumented steps below overwrite any workspace
     del last
@@ -919,7 +929,7 @@ def measure(name, args, rank, world, device, want_roofline=True, want_cpu=True):
             # the headline workload runs at the package power cap: joules per slide is what a change has to lower
             out["power"]["energy_j_per_slide"] = round(out["power"]["package_w"] * world / value, 3)
     recs = []
-    if want_roofline:
+    if full:
         roof, recs = roofline_from_profile(wl["step"], min(steps, 3), args.dtype, name)
         if roof is not None and out.get("power") and roof.get("bound") == "mfma":
             # the same fraction against the matrix peak AT THE CLOCK THE CHIP SUSTAINED in the timed region
@@ -952,10 +962,10 @@ def measure(name, args, rank, world, device, want_roofline=True, want_cpu=True):
             # the dominant class is one kernel of many (11 % of the headline step): the whole step against the same peak
             roof["frac_end_to_end"] = roof["end_to_end"]["frac_of_mfma_peak"]
         out["roofline"] = roof
-    if want_cpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = wl["cpu_baseline"]()
     out["_recs"] = recs
-    if wl.get("check"):
+    if full and wl.get("check"):
         out["check"] = wl["check"]()
     del wl
     import gc
@@ -986,12 +996,15 @@ def main():
     ap.add_argument("--no-stream", action="store_true", help="pipeline workload: finish every step's slides before the next step starts")
     ap.add_argument("--resident", action="store_true", help="pipeline workload: patches already in HBM when the timed region starts "
                     "(default: uploaded from pinned host memory every step, as BASELINE config 3 states)")
-    ap.add_argument("--measure-traffic", action="store_true", help="collect roofline.traffic with two rocprofv3 --pmc passes of this build "
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure as well: power during the timed steps, "
+                    "then roofline (extra instrumented steps), measured traffic, CPU baseline, the workload's check, accuracy_vs_reference "
+                    "and the secondary measurements.  Off: set up, warm up, time the steps, --dump-outputs, print the line")
+    ap.add_argument("--measure-traffic", action="store_true", help="--full: collect roofline.traffic with two rocprofv3 --pmc passes of this build "
                     "(the default for the default workload when rocprofv3 is on the box)")
-    ap.add_argument("--no-measure-traffic", action="store_true", help="keep the figure of the committed pass under profiles/ (traffic_measured false)")
-    ap.add_argument("--no-accuracy", action="store_true", help="pipeline workload: skip the accuracy_vs_reference checker leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="default workload only: skip the secondary measurements")
+    ap.add_argument("--no-measure-traffic", action="store_true", help="--full: keep the figure of the committed pass under profiles/ (traffic_measured false)")
+    ap.add_argument("--no-accuracy", action="store_true", help="--full, pipeline workload: skip the accuracy_vs_reference checker leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, default workload only: skip the secondary measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last timed step as DIR/<name>.npy (rank 0's share with --gpus > 1; "
                          "at most 64 MB, larger outputs as a fixed seeded sample) for output-by-output comparison of two builds.  Give "
@@ -1000,6 +1013,11 @@ def main():
     args = ap.parse_args()
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:              # what needs the instrumented steps or the check: refused rather than silently left out
+        for flag, why in ((args.measure_traffic, "--measure-traffic"), (os.environ.get("SQ_BENCH_KERNELS"), "SQ_BENCH_KERNELS"),
+                          (os.environ.get("SQ_BENCH_DUMP_PARAMS"), "SQ_BENCH_DUMP_PARAMS"), (os.environ.get("SQ_PROF_MARKERS"), "SQ_PROF_MARKERS")):
+            if flag:
+                ap.error(f"{why} needs --full")
     args.from_host = not args.resident
     if args.dtype is None:
         args.dtype = "f16x3" if (args.workload == "pipeline" and args.embedder == "resnet") else "bf16"
@@ -1037,33 +1055,34 @@ def main():
         if rank == 0:
             print(f"bench: {got} ranks joined the {'gloo (shared GPU)' if share else 'RCCL'} process group", file=sys.stderr)
 
-    res = measure(args.workload, args, rank, world, device)
+    res = measure(args.workload, args, rank, world, device, full=args.full)
     line = {"metric": METRIC, "value": res["value"], "unit": "slides/s", "n_gpus": world, "steps": res["steps"],
             "warmup": res["warmup"], "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": res.get("scaling", "weak"),
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "config": res["config"],
-            "roofline": res.get("roofline"), "cpu_baseline": res.get("cpu_baseline"), "timed_region_s": res["timed_region_s"],
-            "host_numa_binding": numa, "power": res.get("power"),
-            "ranks": torch.distributed.get_world_size() if world > 1 else 1,
-            "backend": (torch.distributed.get_backend() if world > 1 else None)}
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "config": res["config"], "timed_region_s": res["timed_region_s"],
+            "host_numa_binding": numa, "ranks": torch.distributed.get_world_size() if world > 1 else 1,
+            "backend": (torch.distributed.get_backend() if world > 1 else None), "full": args.full}
+    if args.full:
+        line.update(roofline=res.get("roofline"), cpu_baseline=res.get("cpu_baseline"), power=res.get("power"))
     default_wl = args.workload == "pipeline" and args.dtype == "f16x3" and args.embedder == "resnet"
-    if (args.measure_traffic or (default_wl and not args.no_measure_traffic)) and rank == 0 and world == 1 and line.get("roofline"):
+    if args.full and (args.measure_traffic or (default_wl and not args.no_measure_traffic)) and rank == 0 and world == 1 and line.get("roofline"):
         try:
             (measure_traffic if default_wl else measure_traffic_marked)(line["roofline"], args, res.get("_recs") or ())
         except Exception as e:                          # a profiler problem must not cost the line
             line["roofline"]["traffic_error"] = f"{type(e).__name__}: {e}"
     if "check" in res:
         line["check"] = res["check"]
-    if args.workload == "pipeline" and args.embedder == "resnet" and rank == 0 and world == 1 and not args.no_accuracy:
+    if args.full and args.workload == "pipeline" and args.embedder == "resnet" and rank == 0 and world == 1 and not args.no_accuracy:
         try:
             line["accuracy_vs_reference"] = accuracy_vs_reference(args.dtype, device, tuple(GOLDEN_SLIDES) if args.dtype == "f16x3" else ("noise224",))
         except Exception as e:                          # the checker leg must not cost the line
             line["accuracy_vs_reference"] = {"error": f"{type(e).__name__}: {e}"}
 
-    # secondary measurements of the default run (N = 1): the PCIe-inclusive twin, BASELINE config 2, the fp32 parity
+    # secondary measurements of the default --full run (N = 1): the PCIe-inclusive twin, BASELINE config 2, the fp32 parity
     # mode.  Each runs in a fresh process (same script, same timing rules): a process that has already created one
     # workload's helper streams maps later streams onto the same few hardware queues, which serialises what the
     # next workload wants to overlap (measured: from-host 41 instead of 53 slides/s, vis_train 10.5 instead of 3.6 ms).
-    if args.workload == "pipeline" and args.dtype == "f16x3" and args.from_host and args.embedder == "resnet" and world == 1 and not args.no_secondary:
+    if args.full and args.workload == "pipeline" and args.dtype == "f16x3" and args.from_host and args.embedder == "resnet" and world == 1 \
+            and not args.no_secondary:
         import subprocess
         sec = {}
         for key, extra in (("pipeline_resident_in_hbm", ["--workload", "pipeline", "--resident", "--no-accuracy"]),
@@ -1075,7 +1094,8 @@ def main():
                            ("pipeline_uni_vit_l16_embedder", ["--workload", "pipeline", "--embedder", "uni", "--slides", "2"]),
                            ("spatial_50k_tiles", ["--workload", "spatial"])):
             in_run = key in ("vis_train_bf16", "pipeline_uni_vit_l16_embedder", "spatial_50k_tiles")      # one marker-attributed --pmc pass pair each
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-secondary", "--no-cpu-baseline", "--measure-traffic" if in_run else "--no-measure-traffic",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-secondary", "--no-cpu-baseline",
+                   "--measure-traffic" if in_run else "--no-measure-traffic",
                    "--warmup", str(args.warmup)] + extra
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)

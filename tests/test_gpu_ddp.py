@@ -84,7 +84,7 @@ def _bench_kfold(tmp_path, gpus, batch, tag):
     dump = tmp_path / f"params_{tag}.pt"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SQ_BENCH_SHARE_GPU="1", SQ_BENCH_DUMP_PARAMS=str(dump))
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(gpus), "--workload", "train_kfold", "--batch", str(batch),
-           "--epochs", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary"]
+           "--epochs", "1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-secondary"]      # --full: the `check` block
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])

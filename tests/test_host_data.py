@@ -181,3 +181,18 @@ def test_bench_kernel_class_geometry():
     assert k("dual_f16x3_M196000_N1024_K256_K512")[1] == 1532 * 8 * 256
     assert k("gemm_f16x3_M196000_N256_K1024") == ("gemm_x3_kernel<256", 766 * 2 * 512)
     assert k("gemm_f32_M800_N2048_K2048_b1") is None
+
+
+@pytest.mark.parametrize("extra, env", [(["--measure-traffic"], {}), ([], {"SQ_BENCH_KERNELS": "kernels.json"}),
+                                        ([], {"SQ_BENCH_DUMP_PARAMS": "params.pt"})],
+                         ids=["measure_traffic", "kernel_table", "dump_params"])
+def test_bench_refuses_full_only_requests_without_full(tmp_path, extra, env):
+    """What only a --full run produces (PMC traffic, the per-kernel table of the instrumented steps, the train_kfold check's
+    parameter dump) is refused in a plain run before any GPU work, not silently left out."""
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--steps", "1", "--warmup", "0"] + extra, cwd=tmp_path, env=dict(os.environ, **env),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "needs --full" in r.stderr, (r.returncode, r.stderr[-1500:])
+    assert not os.listdir(tmp_path)

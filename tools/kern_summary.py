@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Print a bench line's value and the per-kernel table written by SQ_BENCH_KERNELS (bench.py)."""
+"""Print a bench line's value and the per-kernel table written by SQ_BENCH_KERNELS (bench.py --full)."""
 import json, sys
 bench, kern = sys.argv[1], sys.argv[2]
 slides = float(sys.argv[3]) if len(sys.argv) > 3 else 24.0

@@ -56,9 +56,10 @@ json.dump({"note": "SQ counters as fractions of SQ_WAVE_CYCLES per kernel symbol
           open('gpurun_out/profiles_r03/r03_pipeline_f16x3_sq_counters.json', 'w'), indent=1)
 print("sq kernels", len(out))
 PY
-SQ_BENCH_KERNELS=gpurun_out/profiles_r03/r03_pipeline_f16x3_bench_kernels.json python bench.py --no-secondary --no-cpu-baseline --no-accuracy > gpurun_out/profiles_r03/r03_pipeline_f16x3_bench_line.json 2>/dev/null
-python bench.py > gpurun_out/profiles_r03/r03_bench_final.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r03/r03_vis_train_bf16_bench_kernels.json python bench.py --workload vis_train --no-secondary --no-cpu-baseline > gpurun_out/profiles_r03/r03_vis_train_bf16_bench_line.json 2>/dev/null
+S=$(dirname $O)/profiles_r03          # the summaries' folder beside $O; bench lines read from the instrumented steps need --full
+SQ_BENCH_KERNELS=$S/r03_pipeline_f16x3_bench_kernels.json python bench.py --full --no-secondary --no-cpu-baseline --no-accuracy > $S/r03_pipeline_f16x3_bench_line.json 2>/dev/null
+python bench.py --full > $S/r03_bench_final.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r03_vis_train_bf16_bench_kernels.json python bench.py --full --workload vis_train --no-secondary --no-cpu-baseline > $S/r03_vis_train_bf16_bench_line.json 2>/dev/null
 ls -la gpurun_out/profiles_r03
 find $O -name "*.csv" -size +5M -delete
 du -sh $O

@@ -56,10 +56,11 @@ json.dump({"note": "SQ counters as fractions of SQ_WAVE_CYCLES per kernel symbol
           open('gpurun_out/profiles_r04/r04_pipeline_f16x3_sq_counters.json', 'w'), indent=1)
 print("sq kernels", len(out))
 PY
-SQ_BENCH_KERNELS=gpurun_out/profiles_r04/r04_pipeline_f16x3_bench_kernels.json python bench.py --no-secondary --no-cpu-baseline --no-accuracy > gpurun_out/profiles_r04/r04_pipeline_f16x3_bench_line.json 2>/dev/null
-python bench.py > gpurun_out/profiles_r04/r04_bench_final.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r04/r04_pipeline_uni_bf16_bench_kernels.json python bench.py --workload pipeline --embedder uni --slides 2 --no-secondary --no-cpu-baseline > gpurun_out/profiles_r04/r04_pipeline_uni_bf16_bench_line.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r04/r04_spatial_bf16_bench_kernels.json python bench.py --workload spatial --no-secondary --no-cpu-baseline > gpurun_out/profiles_r04/r04_spatial_bf16_bench_line.json 2>/dev/null
+S=$(dirname $O)/profiles_r04          # the summaries' folder beside $O; bench lines read from the instrumented steps need --full
+SQ_BENCH_KERNELS=$S/r04_pipeline_f16x3_bench_kernels.json python bench.py --full --no-secondary --no-cpu-baseline --no-accuracy > $S/r04_pipeline_f16x3_bench_line.json 2>/dev/null
+python bench.py --full > $S/r04_bench_final.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r04_pipeline_uni_bf16_bench_kernels.json python bench.py --full --workload pipeline --embedder uni --slides 2 --no-secondary --no-cpu-baseline > $S/r04_pipeline_uni_bf16_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r04_spatial_bf16_bench_kernels.json python bench.py --full --workload spatial --no-secondary --no-cpu-baseline > $S/r04_spatial_bf16_bench_line.json 2>/dev/null
 cd /tmp; for w in "uni:--workload pipeline --embedder uni --slides 1 --steps 2 --warmup 1" "spatial:--workload spatial --steps 1 --warmup 1"; do
   t=${w%%:*}; a=${w#*:}
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$t -- python $R/bench.py --no-secondary --no-cpu-baseline $a > $O/$t.log 2>&1
@@ -69,7 +70,7 @@ cd $R
 bash tools/r4_tnpmc.sh > /dev/null 2>&1; cp gpurun_out/r4_tn_sq_counters.txt gpurun_out/profiles_r04/r04_tn_sq_counters.txt
 python tools/tn_probe.py group 2>&1 | grep -v amdgpu.ids > gpurun_out/profiles_r04/r04_tn_probe_ring.txt
 python tools/nt_small.py 2>&1 | grep -v amdgpu.ids > gpurun_out/profiles_r04/r04_nt_small_cold_operands.txt
-SQ_BENCH_KERNELS=gpurun_out/profiles_r04/r04_vis_train_bf16_bench_kernels.json python bench.py --workload vis_train --no-secondary --no-cpu-baseline > gpurun_out/profiles_r04/r04_vis_train_bf16_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r04_vis_train_bf16_bench_kernels.json python bench.py --full --workload vis_train --no-secondary --no-cpu-baseline > $S/r04_vis_train_bf16_bench_line.json 2>/dev/null
 ls -la gpurun_out/profiles_r04
 find $O -name "*.csv" -size +5M -delete
 du -sh $O

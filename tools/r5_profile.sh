@@ -30,8 +30,9 @@ python tools/pmc_summary.py r05_pipeline_f16x3 gpurun_out/profiles_r05/r05_pipel
   "dual_f16x3_M784000_N512_K128_K256=gemm_x3_kernel<128, 2, false, true, false, true>:6272000" \
   "dual_f16x3_M196000_N1024_K256_K512=gemm_x3_kernel<128, 2, false, true, false, true>:3137536" \
   "conv1_pool_reduce_f16x3=conv1_pool_x3_kernel<true>:131072"
-SQ_BENCH_KERNELS=gpurun_out/profiles_r05/r05_pipeline_f16x3_bench_kernels.json python bench.py --no-secondary --no-cpu-baseline --no-accuracy > gpurun_out/profiles_r05/r05_pipeline_f16x3_bench_line.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r05/r05_vis_train_bf16_bench_kernels.json python bench.py --workload vis_train --no-secondary --no-cpu-baseline > gpurun_out/profiles_r05/r05_vis_train_bf16_bench_line.json 2>/dev/null
-python bench.py > gpurun_out/profiles_r05/r05_bench_final.json 2> gpurun_out/profiles_r05/r05_bench_final.err
+S=$(dirname $O)/profiles_r05          # the summaries' folder beside $O; bench lines read from the instrumented steps need --full
+SQ_BENCH_KERNELS=$S/r05_pipeline_f16x3_bench_kernels.json python bench.py --full --no-secondary --no-cpu-baseline --no-accuracy > $S/r05_pipeline_f16x3_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r05_vis_train_bf16_bench_kernels.json python bench.py --full --workload vis_train --no-secondary --no-cpu-baseline > $S/r05_vis_train_bf16_bench_line.json 2>/dev/null
+python bench.py --full > $S/r05_bench_final.json 2> $S/r05_bench_final.err
 ls -la gpurun_out/profiles_r05
 find $O -name "*.csv" -size +5M -delete

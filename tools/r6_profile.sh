@@ -31,10 +31,11 @@ python tools/pmc_summary.py r06_pipeline_f16x3 gpurun_out/profiles_r06/r06_pipel
   "dual_f16x3_M196000_N1024_K256_K512=gemm_x3_kernel<128, 2, false, true, false, true>:3137536" \
   "dual_f16x3_M49000_N2048_K512_K1024=gemm_x3_kernel<128, 2, false, true, false, true>:1568768" \
   "conv1_pool_reduce_f16x3=conv1_pool_x3_kernel<true>:131072"
-SQ_BENCH_KERNELS=gpurun_out/profiles_r06/r06_pipeline_f16x3_bench_kernels.json python bench.py --no-secondary --no-cpu-baseline --no-accuracy > gpurun_out/profiles_r06/r06_pipeline_f16x3_bench_line.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r06/r06_vis_train_bf16_bench_kernels.json python bench.py --workload vis_train --measure-traffic --no-secondary --no-cpu-baseline > gpurun_out/profiles_r06/r06_vis_train_bf16_bench_line.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r06/r06_spatial_bf16_bench_kernels.json python bench.py --workload spatial --measure-traffic --no-secondary --no-cpu-baseline > gpurun_out/profiles_r06/r06_spatial_bf16_bench_line.json 2>/dev/null
-SQ_BENCH_KERNELS=gpurun_out/profiles_r06/r06_pipeline_uni_bf16_bench_kernels.json python bench.py --workload pipeline --embedder uni --slides 2 --measure-traffic --no-secondary --no-cpu-baseline > gpurun_out/profiles_r06/r06_pipeline_uni_bf16_bench_line.json 2>/dev/null
-python bench.py > gpurun_out/profiles_r06/r06_bench_final.json 2> gpurun_out/profiles_r06/r06_bench_final.err
+S=$(dirname $O)/profiles_r06          # the summaries' folder beside $O; bench lines read from the instrumented steps need --full
+SQ_BENCH_KERNELS=$S/r06_pipeline_f16x3_bench_kernels.json python bench.py --full --no-secondary --no-cpu-baseline --no-accuracy > $S/r06_pipeline_f16x3_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r06_vis_train_bf16_bench_kernels.json python bench.py --full --workload vis_train --measure-traffic --no-secondary --no-cpu-baseline > $S/r06_vis_train_bf16_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r06_spatial_bf16_bench_kernels.json python bench.py --full --workload spatial --measure-traffic --no-secondary --no-cpu-baseline > $S/r06_spatial_bf16_bench_line.json 2>/dev/null
+SQ_BENCH_KERNELS=$S/r06_pipeline_uni_bf16_bench_kernels.json python bench.py --full --workload pipeline --embedder uni --slides 2 --measure-traffic --no-secondary --no-cpu-baseline > $S/r06_pipeline_uni_bf16_bench_line.json 2>/dev/null
+python bench.py --full > $S/r06_bench_final.json 2> $S/r06_bench_final.err
 ls -la gpurun_out/profiles_r06
 find $O -name "*.csv" -size +5M -delete
