@@ -166,6 +166,17 @@ size_t sq_vit_workspace_bytes(const sq_vit_config* cfg, int dtype, int batch, in
 int sq_vit_forward(const sq_vit_config* cfg, int dtype, const float* params, const void* params_lp, const float* x,
                    float* out, int batch, int save_for_backward, void* workspace, size_t workspace_bytes,
                    sq_stream_t stream);
+/* sq_vit_forward with the two options of sq_vis_forward_ex, for the window loop of spatial_vis/visualize.py:46-82 with
+ * --model_type vit (the model: src/vit.py:105-115):
+ *  - gather: instead of x, give gather_src f32 [gather_rows, D] (the tile-feature cache) and gather_idx int32 [B, num_clusters];
+ *    token (b, t) is row gather_idx[b, t] of the cache plus pos_emb1D[t] (vit.py:109).  An index outside [0, gather_rows) -- a
+ *    negative one in particular -- is a zero row (the zero padding of visualize.py:72-75); the window batch is never materialised;
+ *  - head_in: instead of out, receive the linear head's INPUT LayerNorm(mean_tokens X) (vit.py:113-115) as f32 [B, D] in both
+ *    dtypes; the [B, G] head product is skipped (the head is linear: the caller votes these vectors per tile, then applies it).
+ * Exactly one of (x | gather_src + gather_idx) and exactly one of (out | head_in) must be given. */
+int sq_vit_forward_ex(const sq_vit_config* cfg, int dtype, const float* params, const void* params_lp, const float* x,
+                      const float* gather_src, const int32_t* gather_idx, int gather_rows, float* out, float* head_in,
+                      int batch, int save_for_backward, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 size_t sq_vit_backward_workspace_bytes(const sq_vit_config* cfg, int dtype, int batch);
 int sq_vit_backward(const sq_vit_config* cfg, int dtype, const float* params, const void* params_lp,
                     const float* grad_out, float* grad_params, float* grad_x, int batch, void* fwd_workspace,
@@ -369,6 +380,13 @@ int sq_uni_forward_checked(const sq_uni_config* cfg, int dtype, const float* par
  *                         scores f32 [B, N, ld_scores >= G] token-major, N <= 128 tiles, 1 <= k_i <= N, out f32 [B, G].
  *                         0/0 (the first k tiles of a slide all masked) is NaN, as in the reference.
  *   sq_he2rna_topk_mean_bwd : grad_scores f32 [B, N, ld_grad >= G] from grad_out f32 [B, G] (columns >= G untouched).
+ *   sq_he2rna_window_topk_mean : the top-k mean of sliding windows over a slide (spatial_vis/visualize.py:46-82 with
+ *                         --model_type he2rna, :79-81): the MLP is per tile (1x1 convolutions, he2rna.py:101-106) and so is the mask
+ *                         (:94-95), so both are computed ONCE per tile -- scores f32 [gather_rows, ld_scores >= G], mask f32
+ *                         [gather_rows] -- and window w's tile n is row gather_idx[w, n] (int32 [n_windows, N]); an index outside
+ *                         [0, gather_rows) is the zero padding of visualize.py:72-75 (score 0, mask 0).  out f32 [n_windows, G].
+ *                         Same rank / tie rule, first-k-positions mask, fp64 sums and 0/0 = NaN as sq_he2rna_topk_mean: a
+ *                         window's row is bit-identical to sq_he2rna_topk_mean on the materialised [n_windows, N, G] scores.
  * ---------------------------------------------------------------------------------------------------------- */
 int sq_he2rna_tile_mask(const float* x_tokens, int n_rows, int n_channels, float* mask, sq_stream_t stream);
 int sq_he2rna_topk_mean(const float* scores, int ld_scores, const float* mask, const int32_t* ks, int n_ks, float scale,
@@ -376,6 +394,9 @@ int sq_he2rna_topk_mean(const float* scores, int ld_scores, const float* mask, c
 int sq_he2rna_topk_mean_bwd(const float* scores, int ld_scores, const float* mask, const int32_t* ks, int n_ks, float scale,
                             const float* grad_out, float* grad_scores, int ld_grad, int batch, int n_tiles, int n_genes,
                             sq_stream_t stream);
+int sq_he2rna_window_topk_mean(const float* scores, int ld_scores, const float* mask, int gather_rows, const int32_t* gather_idx,
+                               const int32_t* ks, int n_ks, float scale, float* out, int n_windows, int n_tiles, int n_genes,
+                               sq_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,8 @@ def _declare(lib):
     lib.sq_vit_workspace_bytes.argtypes = [ctypes.POINTER(VitConfig), i32, i32, i32]
     lib.sq_vit_forward.restype = i32
     lib.sq_vit_forward.argtypes = [ctypes.POINTER(VitConfig), i32, vp, vp, vp, vp, i32, i32, vp, sz, vp]
+    lib.sq_vit_forward_ex.restype = i32
+    lib.sq_vit_forward_ex.argtypes = [ctypes.POINTER(VitConfig), i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, sz, vp]
     lib.sq_vit_backward_workspace_bytes.restype = sz
     lib.sq_vit_backward_workspace_bytes.argtypes = [ctypes.POINTER(VitConfig), i32, i32]
     lib.sq_vit_backward.restype = i32
@@ -151,6 +153,8 @@ def _declare(lib):
     lib.sq_he2rna_tile_mask.argtypes = [vp, i32, i32, vp, vp]
     lib.sq_he2rna_topk_mean.restype = i32
     lib.sq_he2rna_topk_mean.argtypes = [vp, i32, vp, vp, i32, f32, vp, i32, i32, i32, vp]
+    lib.sq_he2rna_window_topk_mean.restype = i32
+    lib.sq_he2rna_window_topk_mean.argtypes = [vp, i32, vp, i32, vp, vp, i32, f32, vp, i32, i32, i32, vp]
     lib.sq_he2rna_topk_mean_bwd.restype = i32
     lib.sq_he2rna_topk_mean_bwd.argtypes = [vp, i32, vp, vp, i32, f32, vp, vp, i32, i32, i32, i32, vp]
     lib.sq_linear_weight_grad.restype = i32

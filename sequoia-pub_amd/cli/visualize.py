@@ -2,9 +2,9 @@
 output ``<out_root>/<project>/<save_folder>/<wsi>/stride-1.csv`` with one column per gene and fold plus the fold mean).
 
 What differs in HOW: every valid tile is embedded ONCE into a feature cache and the windows are gathered from it
-(the reference re-reads and re-embeds a tile in every window that holds it); ViS windows run through
-``spatial.sliding_window_method`` (gather + vote before the linear head), 'vit' / 'he2rna' through
-``spatial.sliding_window_any_model``.  The reference hard-codes its data locations per project; here they are the
+(the reference re-reads and re-embeds a tile in every window that holds it); the windows of all three models run through
+``spatial.sliding_window_method`` -- ViS / ViT: gather + vote before the linear head; HE2RNA: per-tile scores once, top-k
+mean per window, vote on the window predictions -- and under torchrun the slide is dealt over the ranks for each of them.  The reference hard-codes its data locations per project; here they are the
 defaults of ``--slide_path`` / ``--mask_path`` / ``--checkpoint`` and can be overridden.  Slides are opened with
 openslide when it is installed, or given as an ``.npy`` RGB array (``patchgen.ArraySlide``, 20x).  ResNet tiles are
 resized to 256 x 256 (the reference's ``Resize((256, 265))`` is not a size the convolution engine takes); UNI tiles to
@@ -19,7 +19,7 @@ import torch
 from scipy.ndimage import binary_dilation
 
 from ..patchgen import ArraySlide
-from ..spatial import sliding_window_any_model, sliding_window_method
+from ..spatial import sliding_window_method
 from .common import init_distributed
 
 BACKGROUND_THRESHOLD = .5
@@ -208,10 +208,7 @@ def main(argv=None):
         else:
             model.load_state_dict(torch.load(fold_ckpt, map_location='cpu'))
         model = model.to(device).eval()
-        if args.model_type == 'vis':
-            preds = sliding_window_method(df, tile_features, model, inds, stride, shard=shard)
-        else:
-            preds = sliding_window_any_model(df, tile_features, model, inds, stride, args.model_type)
+        preds = sliding_window_method(df, tile_features, model, inds, stride, shard=shard)
         for ind_gene in inds:
             res_df[gene_ids[ind_gene] + '_' + str(fold)] = res_df.index.map(preds[ind_gene])
     for ind_gene in inds:
@@ -221,6 +218,7 @@ def main(argv=None):
         res_df.to_csv(save_name)
     if world > 1:
         torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
     print('Done')
     return res_df, save_name
 

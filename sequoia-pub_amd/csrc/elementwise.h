@@ -6,6 +6,9 @@
 int sq_k_add_pos(const float* x, const float* pos, float* X, bf16_t* Xh, int B, int N, int D, hipStream_t s);
 // out[b,:] = mean_n X[b,n,:]       (tformer_lin.py:22 via s(mean x), :103); optional bf16 copy
 int sq_k_add_pos_gather(const float* src, const int32_t* idx, const float* pos, float* X, bf16_t* Xh, int B, int N, int D, hipStream_t s);
+// the same with the source's row count: an index outside [0, rows) is a zero row as a negative one is (ViT / HE2RNA window entries)
+int sq_k_add_pos_gather_rows(const float* src, const int32_t* idx, int rows, const float* pos, float* X, bf16_t* Xh, int B, int N, int D,
+                             hipStream_t s);
 int sq_k_token_mean(const float* X, float* out, bf16_t* outh, int B, int N, int D, hipStream_t s);
 int sq_k_token_mean_any(const void* X, int in_dtype, float* out, bf16_t* outh, int B, int N, int D, hipStream_t s);   // X fp32 or bf16
 // y = LayerNorm_D(x) * g + b       (rows of length D <= 4096, eps 1e-5); out f32 or bf16; optional mean/rstd save

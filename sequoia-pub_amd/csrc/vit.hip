@@ -262,10 +262,22 @@ extern "C" size_t sq_vit_backward_workspace_bytes(const sq_vit_config* c, int dt
 
 extern "C" int sq_vit_forward(const sq_vit_config* c, int dtype, const float* params, const void* params_lp, const float* x,
                               float* out, int B, int save, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+    SQ_REQUIRE(x && out, "vit_forward: null pointer");
+    return sq_vit_forward_ex(c, dtype, params, params_lp, x, nullptr, nullptr, 0, out, nullptr, B, save, workspace, workspace_bytes, stream_);
+}
+
+// The window gather (token (b, t) = row gather_idx[b, t] of the tile-feature cache, + pos_emb1D[t]) happens in the first kernel; with
+// head_in the forward stops at the linear head's input LayerNorm(mean_tokens X), written in fp32 whatever the compute dtype.
+extern "C" int sq_vit_forward_ex(const sq_vit_config* c, int dtype, const float* params, const void* params_lp, const float* x,
+                                 const float* gather_src, const int32_t* gather_idx, int gather_rows, float* out, float* head_in,
+                                 int B, int save, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
     if (int e = check_vit(c)) return e;
     hipStream_t st = (hipStream_t)stream_;
     SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16, "vit_forward: dtype %d", dtype);
-    SQ_REQUIRE(params && x && out && workspace && B >= 1, "vit_forward: bad arguments");
+    SQ_REQUIRE(params && workspace && B >= 1, "vit_forward: bad arguments");
+    SQ_REQUIRE((x != nullptr) != (gather_src != nullptr && gather_idx != nullptr), "vit_forward: give either x or (gather_src, gather_idx)");
+    SQ_REQUIRE(x || gather_rows >= 1, "vit_forward: gather_rows=%d", gather_rows);
+    SQ_REQUIRE((out != nullptr) != (head_in != nullptr), "vit_forward: give either out (predictions) or head_in (the head's input)");
     SQ_REQUIRE(dtype == SQ_F32 || params_lp, "vit_forward: bf16 mode needs the bf16 parameter shadow");
     sq_vit_layout lay;
     RUN(sq_vit_layout_init(c, &lay));
@@ -281,7 +293,8 @@ extern "C" int sq_vit_forward(const sq_vit_config* c, int dtype, const float* pa
     auto Pf = [&](int64_t off) { return params + off; };
     SQ_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     SQ_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RUN(sq_k_add_pos(x, Pf(lay.pos), w.Xin[0], lp ? (bf16_t*)w.Xin_lp[0] : nullptr, B, N, D, st));
+    if (x) RUN(sq_k_add_pos(x, Pf(lay.pos), w.Xin[0], lp ? (bf16_t*)w.Xin_lp[0] : nullptr, B, N, D, st));
+    else RUN(sq_k_add_pos_gather_rows(gather_src, gather_idx, gather_rows, Pf(lay.pos), w.Xin[0], lp ? (bf16_t*)w.Xin_lp[0] : nullptr, B, N, D, st));
     for (int l = 0; l < c->depth; ++l) {
         const sq_vit_layer_offsets& L = lay.layer[l];
         const int s = save ? l : 0;
@@ -322,6 +335,8 @@ extern "C" int sq_vit_forward(const sq_vit_config* c, int dtype, const float* pa
     }
     const float* Xfin = w.Xin[save ? c->depth : 0];
     RUN(sq_k_token_mean(Xfin, w.xm, nullptr, B, N, D, st));
+    if (head_in)        // the caller applies the (linear) head itself, after the per-tile vote over windows: LN output in fp32
+        return sq_k_ln_rows(w.xm, Pf(lay.head_ln_g), Pf(lay.head_ln_b), head_in, SQ_F32, B, D, nullptr, nullptr, st);
     RUN(sq_k_ln_rows(w.xm, Pf(lay.head_ln_g), Pf(lay.head_ln_b), w.xn, dtype, B, D, nullptr, nullptr, st));
     {
         GemmArgs g; g.A = w.xn; g.lda = D; g.a_bytes = (size_t)B * D * es;

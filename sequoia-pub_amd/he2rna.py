@@ -176,6 +176,72 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
     def forward_fixed_k(self, x, k):
         return self._run(x, [int(k)], 1.0, self.training)
 
+    TILE_ROWS = 16384      # rows per launch of tile_scores: 16 384 x 20 824 x 4 B stays below the 2 GiB buffer-descriptor limit
+
+    @torch.no_grad()
+    def tile_scores(self, cache):
+        """The per-tile half of forward_fixed_k (he2rna.py:93-96, :101-106) for a tile-feature cache f32 [n_tiles, C] on the
+        device: the MLP is a stack of 1x1 convolutions and the mask a max over a tile's channels, so neither depends on the
+        window (slide) a tile sits in.  Returns (scores f32 [n_tiles, ld >= G] -- the last layer's output on the
+        ``x[:, C - input_dim:]`` channel slice of :102, columns >= G unspecified --, mask f32 [n_tiles] = max_c cache[t, c] > 0).
+        Rows go through in launches of TILE_ROWS on a fixed grid (the same launches on every rank: the same bits)."""
+        _lib.require_gpu()
+        if not cache.is_cuda or cache.dim() != 2 or cache.shape[1] < self.input_dim:
+            raise ValueError(f"HE2RNA.tile_scores: expected a device cache [n_tiles, channels >= {self.input_dim}], got {tuple(cache.shape)}")
+        lib = _lib.lib()
+        dev = cache.device
+        st = _lib.stream_ptr(dev)
+        x = cache.to(torch.float32).contiguous()
+        n, C = x.shape
+        mask = torch.empty(n, dtype=torch.float32, device=dev)
+        G = self.output_dim
+        ld = _up(G, 8)
+        scores = torch.empty(n, ld, dtype=torch.float32, device=dev)
+        if n == 0:
+            return scores, mask
+        ws = self._workspace(dev)
+        params = self._params()
+        layers, k = [], _up(self.input_dim, 8)
+        for i in range(self.n_layers):                    # weights zero-padded to the activations' 8-column rows, as in _He2rnaFn
+            w, b = params[2 * i], params[2 * i + 1]
+            n_out, k_in = w.shape[0], w.shape[1]
+            wp = torch.zeros(n_out, k, dtype=torch.float32, device=dev)
+            wp[:, :k_in] = w.detach().view(n_out, k_in)
+            layers.append((wp, b.detach().float().contiguous(), n_out))
+            k = _up(n_out, 8)
+        with torch.cuda.device(dev):
+            _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(x), n, C, _lib.ptr(mask), st))
+            for r0 in range(0, n, self.TILE_ROWS):
+                r1 = min(n, r0 + self.TILE_ROWS)
+                a = torch.zeros(r1 - r0, _up(self.input_dim, 8), dtype=torch.float32, device=dev)
+                a[:, :self.input_dim] = x[r0:r1, C - self.input_dim:]
+                for i, (wp, bias, n_out) in enumerate(layers):
+                    last = i + 1 == self.n_layers
+                    out = scores[r0:r1] if last else torch.zeros(r1 - r0, _up(n_out, 8), dtype=torch.float32, device=dev)
+                    _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(a), a.shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias), None, 0, _lib.SQ_F32,
+                                             0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], r1 - r0, n_out, wp.shape[1],
+                                             _lib.ptr(ws), ws.numel(), st))
+                    a = out
+        return scores, mask
+
+    def window_predictions(self, scores, mask, members):
+        """Eval-mode predictions (the mean over ``ks``, he2rna.py:88-91) of windows whose tile n is row members[w, n] of a
+        ``tile_scores`` table (int32 [W, N], -1 = zero padding): sq_he2rna_window_topk_mean.  Returns f32 [W, G]."""
+        _lib.require_gpu()
+        W, N = members.shape
+        G = self.output_dim
+        if members.dtype != torch.int32 or not members.is_contiguous() or scores.shape[1] < G or mask.shape[0] != scores.shape[0]:
+            raise ValueError("window_predictions: members must be contiguous int32 [W, N] and scores / mask a tile_scores table")
+        ks = np.asarray(self.ks, dtype=np.int32)
+        out = torch.empty(W, G, dtype=torch.float32, device=scores.device)
+        if W == 0:
+            return out
+        with torch.cuda.device(scores.device):
+            _lib.check(_lib.lib().sq_he2rna_window_topk_mean(_lib.ptr(scores), scores.shape[1], _lib.ptr(mask), scores.shape[0], _lib.ptr(members),
+                                                             ks.ctypes.data, len(ks), 1.0 / len(ks), _lib.ptr(out), W, N, G,
+                                                             _lib.stream_ptr(scores.device)))
+        return out
+
     def conv(self, x):
         """Per-tile scores [B, G, N] (he2rna.py:101-106); the fused forward never materialises this layout."""
         eye = _ScoresFn.apply(x, self.p_drop if self.training else 0.0, self.input_dim, self._workspace(x.device), *self._params())

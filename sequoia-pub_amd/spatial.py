@@ -7,7 +7,11 @@ Differences in HOW (not what): every tile is embedded ONCE into a feature cache 
 in every window that contains it, up to 100 times); windows are enumerated with tensor ops and run through the
 model in large batches (BASELINE config 5: ~47k windows of 100 tokens) that are gathered from the cache on the fly;
 the linear head is applied once per tile, after the vote.  ``literal_2d=True`` reproduces the
-reference's 2-D input quirk (the prediction depends only on the window's first tile)."""
+reference's 2-D input quirk (the prediction depends only on the window's first tile).
+
+The three ``--model_type`` aggregators share that entry: ViS and ViT stop in front of their linear head (the vote runs on
+D-vectors); HE2RNA's per-tile MLP and mask are computed once per tile (HE2RNA.tile_scores) and only its top-k mean runs per
+window (sq_he2rna_window_topk_mean) -- the top-k mean is not linear, so HE2RNA votes on window predictions."""
 import os
 
 import numpy as np
@@ -129,8 +133,8 @@ def window_batch_owner(n_windows, batch_windows, world):
 def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d=False, batch_windows=1024, shard=None,
                                      tile_projection=True):
     """visualize.py:35-102 for ONE slide over `world` ranks (BASELINE config 5's multi-GPU form; SURVEY 8e "Config 5": the
-    windows of a slide are independent, visualize.py:46-52).  Every rank holds the tile-feature cache and enumerates the
-    same window list; then
+    windows of a slide are independent, visualize.py:46-52).  `model`: a ViS, a ViT or an HE2RNA on the device (HE2RNA: see
+    _he2rna_all_genes_sharded).  Every rank holds the tile-feature cache and enumerates the same window list; then
 
       1. window batches (the fixed grid of `batch_windows`) are dealt round-robin: rank r runs batches r, r + world, ...
          through the model up to the head's input -- a [batch, D] block per batch;
@@ -146,6 +150,8 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
     the rows a rank returns are BIT-IDENTICAL to the one-rank result.  Returns (tile_pred f32 [n_local, G], tile_ids int64
     [n_local] -- the df positions of those rows, ascending --, votes int64 [n_tiles] for the whole slide)."""
     _lib.require_gpu()
+    if _is_he2rna(model):
+        return _he2rna_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d, shard)
     rank, world, group = _shard_info(shard)
     dev = model.flat.device
     mem = enumerate_windows_device(xtf, ytf, stride, dev)           # nothing below waits for the device before the result is read
@@ -174,7 +180,8 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
     model._params_lp()                              # refresh the bf16 shadow on the main stream BEFORE the hand-over event:
     # bf16 mode: layer 0's local projection once per TILE (linear in tile feature + position), gathered per window token
     # (sq_vis_forward_tiles) -- n_tiles rows through the product instead of 100 x n_windows
-    tile_proj = model.tile_projections(feats) if (tile_projection and model.compute_dtype == _lib.SQ_BF16 and W * mem.shape[1] > n_tiles) else None
+    tile_proj = model.tile_projections(feats) if (tile_projection and model._C_FWD == "sq_vis_forward" and model.compute_dtype == _lib.SQ_BF16
+                                                  and W * mem.shape[1] > n_tiles) else None
     start = torch.cuda.Event()                      # the window streams wait on `start` only and must see the finished cast
     start.record(main)
     for i, b in enumerate(range(rank, nb, world)):
@@ -207,6 +214,67 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
     return model.apply_head(tile_vec, chunk=HEAD_CHUNK), tile_ids, counts
 
 
+def _is_he2rna(model):
+    from .he2rna import HE2RNA
+    return isinstance(model, HE2RNA)
+
+
+WINDOW_PRED_BYTES = 2 << 30   # bound of one HE2RNA [windows, G] prediction block (a tile chunk whose windows exceed it is split)
+
+
+def _he2rna_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d, shard):
+    """sliding_window_all_genes_sharded for HE2RNA (visualize.py:79-82 feeds it the window as channels x tiles).  The MLP and the
+    mask are per tile, so every rank builds the whole [n_tiles, G] score table once, on the same launch grid (HE2RNA.tile_scores);
+    the top-k mean is per window and not linear, so the vote runs on window predictions.  Sharded by TILE chunk (chunk c of
+    HEAD_CHUNK tiles to rank c % world), not by window batch -- no [W, G] all-gather: for each of its chunks a rank computes the
+    windows its tiles lie in (windows at chunk borders are computed by both neighbouring ranks) and votes those tiles.  A window's
+    row is the same thread arithmetic in whatever block it is computed and a tile's vote reads its windows in visiting order, so
+    the rows are BIT-IDENTICAL to the one-rank result."""
+    if literal_2d:
+        raise ValueError("literal_2d is the ViS / ViT 2-D input quirk; the reference feeds HE2RNA a 3-D tensor (visualize.py:79-81)")
+    rank, world, _ = _shard_info(shard)
+    dev = next(model.parameters()).device
+    mem = enumerate_windows_device(xtf, ytf, stride, dev)
+    feats = tile_features.to(dev, torch.float32).contiguous()
+    n_tiles = feats.shape[0]
+    G = model.output_dim
+    chunks = range(rank, -(-n_tiles // HEAD_CHUNK), world)
+    tile_ids = torch.cat([torch.arange(c * HEAD_CHUNK, min(n_tiles, (c + 1) * HEAD_CHUNK), device=dev) for c in chunks]) if len(chunks) \
+        else torch.zeros(0, dtype=torch.int64, device=dev)
+    if mem.shape[0] == 0:
+        return torch.full((tile_ids.numel(), G), float("nan"), device=dev), tile_ids, torch.zeros(n_tiles, dtype=torch.int64, device=dev)
+    gather = mem.to(torch.int32).contiguous()
+    V = max_votes_per_tile(stride)
+    lists, counts = tile_window_lists(mem, n_tiles, dev, max_votes=V)
+    out = torch.empty(tile_ids.numel(), G, dtype=torch.float32, device=dev)
+    if tile_ids.numel() == 0:
+        return out, tile_ids, counts
+    scores, mask = model.tile_scores(feats)
+    max_wins = max(1, WINDOW_PRED_BYTES // (4 * G))
+    o = 0
+    for c in chunks:
+        todo = [(c * HEAD_CHUNK, min(n_tiles, (c + 1) * HEAD_CHUNK))]
+        while todo:
+            t0, t1 = todo.pop(0)
+            cl = lists[t0:t1]
+            wins = torch.unique(cl[cl >= 0])                           # ascending window ids: visiting order is kept below
+            if wins.numel() > max_wins and t1 - t0 > 1:                # a per-tile result: any split of the chunk gives the same rows
+                h = (t0 + t1) // 2
+                todo[:0] = [(t0, h), (h, t1)]
+                continue
+            dst = out[o:o + t1 - t0]
+            o += t1 - t0
+            if wins.numel() == 0:
+                dst.fill_(float("nan"))
+                continue
+            pred = model.window_predictions(scores, mask, gather[wins.long()])
+            local = torch.where(cl >= 0, torch.searchsorted(wins, cl.clamp(min=0).to(wins.dtype)), -1).to(torch.int32).contiguous()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().sq_window_vote(_lib.ptr(pred), pred.shape[0], G, _lib.ptr(local), t1 - t0, V, 1 if stride == WINDOW else 0,
+                                                     float("nan"), _lib.ptr(dst), _lib.stream_ptr(dev)))
+    return out, tile_ids, counts
+
+
 @torch.no_grad()
 def sliding_window_all_genes(xtf, ytf, tile_features, model, stride, literal_2d=False, batch_windows=1024):
     """All-gene form of visualize.py:35-102 (BASELINE config 5: per-tile 20 820-gene regression): returns
@@ -216,8 +284,8 @@ def sliding_window_all_genes(xtf, ytf, tile_features, model, stride, literal_2d=
     inside the model's first kernel (member indices, -1 = the zero padding of :72-75), the model stops in front of
     its linear head, the per-tile mean / last-writer rule (:87-100) is applied to those D-vectors (sq_window_vote),
     and the head runs ONCE per tile -- mean_w(head(v_w)) = head(mean_w v_w) for a linear head, so HBM sees the
-    [n_tiles, G] result once and 100x fewer head products are computed.  (The one-rank case of
-    sliding_window_all_genes_sharded.)"""
+    [n_tiles, G] result once and 100x fewer head products are computed (ViS, ViT).  HE2RNA: its MLP runs once per tile,
+    windows exist as [windows in a tile chunk, G] blocks only.  (The one-rank case of sliding_window_all_genes_sharded.)"""
     out, _, counts = sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d=literal_2d,
                                                      batch_windows=batch_windows, shard=None)
     return out, counts
@@ -233,7 +301,7 @@ def gathered_row_of_window(w, batch_windows, world, slots):
 @torch.no_grad()
 def sliding_window_method(df, tile_features, model, inds_gene_of_interest, stride, literal_2d=False, batch_windows=512, shard=None):
     """visualize.py:35-102.  df: DataFrame with integer columns xcoord_tf / ycoord_tf (tile grid); tile_features:
-    [n_tiles, D] tensor (row i = features of df.iloc[i], i.e. the feature cache); model: ViS on the GPU.
+    [n_tiles, D] tensor (row i = features of df.iloc[i], i.e. the feature cache); model: ViS, ViT or HE2RNA on the GPU.
     Returns {gene_index: {tile_index: prediction}} exactly like the reference (stride 10: last writer wins;
     stride < 10: mean over the windows containing the tile).  With ``shard=(rank, world[, group])`` the slide's windows and
     tiles are dealt over the ranks (sliding_window_all_genes_sharded); the requested gene columns of every rank's tiles are
@@ -270,8 +338,9 @@ def sliding_window_method(df, tile_features, model, inds_gene_of_interest, strid
 
 @torch.no_grad()
 def sliding_window_any_model(df, tile_features, model, inds_gene_of_interest, stride, model_type, batch_windows=256):
-    """visualize.py:35-102 for the comparator models (``model_type`` 'vit' or 'he2rna'; ViS takes the gather/vote path
-    above): window batches [w, 100, D] are built from the feature cache (zero padding, :72-75), HE2RNA gets them as
+    """visualize.py:35-102 for the comparator models (``model_type`` 'vit' or 'he2rna'), window by window -- the literal form
+    (sliding_window_method is the production path for all three models): window batches [w, 100, D] are built from the feature
+    cache (zero padding, :72-75), HE2RNA gets them as
     channels x tiles (:80-81), and the window predictions of the requested genes are combined per tile with the same
     rule (stride 10: last writer; stride < 10: mean over the windows containing the tile, in visiting order)."""
     genes = list(inds_gene_of_interest)

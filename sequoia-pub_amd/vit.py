@@ -1,7 +1,8 @@
 """ViT -- host-side mirror of /root/reference/src/vit.py:91-115 (softmax-attention baseline, ``--model_type vit``):
 ``ViT(*, num_outputs, dim, depth, heads, mlp_dim, dim_head=64, num_clusters=100, device='cuda')`` with the
 reference's ``state_dict`` keys; arithmetic in ``sq_vit_forward`` / ``sq_vit_backward`` (csrc/vit.hip).
-Shares the flat-parameter plumbing of :class:`sequoia_pub_amd.vis.ViS`."""
+Shares the flat-parameter plumbing of :class:`sequoia_pub_amd.vis.ViS`, and its sliding-window form (``_run_head_inputs`` on
+``sq_vit_forward_ex``, ``apply_head``) so spatial.py runs the ViT the way it runs the ViS."""
 import ctypes
 from collections import OrderedDict
 
@@ -86,6 +87,28 @@ class ViT(ViS):
         self._lp, self._lp_version, self._ws, self._ws_key = None, -1, None, None
         self._register_state_dict_hook(ViS._sd_hook)
         self._register_load_state_dict_pre_hook(self._load_hook)
+
+    def _run_head_inputs(self, cache, members, slot=0, tile_proj=None):
+        """Sliding-window form (sq_vit_forward_ex): cache f32 [n_rows, D] on the device, members int32 [B, 100] rows of the cache
+        per window (-1 = zero padding).  Returns the linear head's input LayerNorm(mean_tokens X) f32 [B, D] (vit.py:113-115) --
+        the window batch is gathered inside the first kernel and the head is left to the caller (``apply_head``).  The first op of
+        a ViT layer is LayerNorm(x + pos), not linear in the tile feature, so there is no per-tile projection (``tile_proj``)."""
+        _lib.require_gpu()
+        if tile_proj is not None:
+            raise NotImplementedError("tile projections are the bf16 ViS sliding-window path's")
+        B, N = members.shape
+        if N != self.cfg.num_clusters or cache.shape[1] != self._dim():
+            raise ValueError(f"expected members [B, {self.cfg.num_clusters}] and a [rows, {self._dim()}] cache")
+        if members.dtype != torch.int32 or not members.is_contiguous() or cache.dtype != torch.float32 or not cache.is_contiguous():
+            raise ValueError("members must be contiguous int32 and the cache contiguous float32")
+        out = torch.empty(B, self._dim(), dtype=torch.float32, device=cache.device)
+        ws = self._workspace(B, False, slot)
+        lp = self._params_lp()
+        with torch.cuda.device(cache.device):
+            _lib.check(_lib.lib().sq_vit_forward_ex(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(lp), None,
+                                                    _lib.ptr(cache), _lib.ptr(members), cache.shape[0], None, _lib.ptr(out), B, 0,
+                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
+        return out
 
     def replace_head(self, head):
         ln, lin = head[0], head[1]
