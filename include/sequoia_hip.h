@@ -236,6 +236,21 @@ int sq_kmeans_fit(const float* X, int n_slides, int n_samples, int dim, int n_cl
                   float* cluster_features, int32_t* seed_indices, int32_t* n_iter, void* workspace,
                   size_t workspace_bytes, sq_stream_t stream);
 
+/* The same fit for ONE slide of any size up to SQ_KMEANS_LARGE_MAX_SAMPLES = 65536 patches (kmean_features.py:96-108 on
+ * a slide made with a raised --max_patch_number, compute_features_hdf5.py:26,112-113; sq_kmeans_fit stops at 4096).
+ * Same arithmetic, arguments and outputs as sq_kmeans_fit with n_slides = 1; the k-means++ seeding forms only the
+ * distances of a step's candidates (no n x n Gram matrix) and the member lists come from a chunked counting sort,
+ * the Lloyd iteration is the one sq_kmeans_fit runs.  Valid for every n_clusters <= n_samples <= 65536 (small slides
+ * included), n_clusters <= 256, dim % 4 == 0; anything else is refused with an sq_last_error message that names the bound.
+ * sq_kmeans_large_workspace_bytes returns 0 when n_samples is outside [1, 65536] (or dim / n_clusters < 1).
+ * Synchronises the stream between Lloyd bursts (the stop decision is read on the host); the seeding adds no
+ * synchronisation. */
+#define SQ_KMEANS_LARGE_MAX_SAMPLES 65536
+size_t sq_kmeans_large_workspace_bytes(int n_samples, int dim, int n_clusters);
+int sq_kmeans_fit_large(const float* X, int n_samples, int dim, int n_clusters, int first_center, const double* uniforms,
+                        int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
+                        int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
 /* ------------------------------------------------------------------------------
  * ResNet-50 patch embedding  (src/resnet.py:155-170 forward_extract; :73-93 Bottleneck;
  * :98-136 topology; eval-mode BN; patch transform pre_processing/compute_features_hdf5.py:49-51,119-120)

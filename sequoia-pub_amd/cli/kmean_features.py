@@ -1,6 +1,7 @@
 """Cluster tokens -- counterpart of /root/reference/pre_processing/kmean_features.py (same flags; appends
 dataset ``cluster_features`` [num_clusters, D] to the slide's feature file, skipping slides that have it or
-have fewer patches than clusters).  KMeans + the per-label means run in ``sq_kmeans_fit``."""
+have fewer patches than clusters).  KMeans + the per-label means run in ``sq_kmeans_fit`` (``sq_kmeans_fit_large``
+for a slide of more than 4096 patches)."""
 import argparse
 import os
 
@@ -9,7 +10,7 @@ import torch
 
 from .. import store
 from ..data import shard_rows
-from ..kmeans import kmeans_fit_batch
+from ..kmeans import kmeans_fit
 from .common import init_distributed, ref_frame, seed_everything
 
 
@@ -60,7 +61,7 @@ def main(argv=None):
             print(f'{WSI}: Cluster feature already available')
             f.close()
             continue
-        r = kmeans_fit_batch(torch.from_numpy(features).to(device), args.num_clusters, random_state=0)
+        r = kmeans_fit(torch.from_numpy(features).to(device), args.num_clusters, random_state=0)
         try:
             f.create_dataset("cluster_features", data=r["cluster_features"][0].cpu().numpy())
         except Exception as e:

@@ -13,6 +13,10 @@
 //     sums in index order, fl32(sum/count), empty-cluster relocation, centre-shift / label stop rule
 //   * cluster means of the ORIGINAL features: member rows added in index order in fp32, / count
 // One workgroup per slide runs the whole seeding loop; slides are independent (grid dimension).
+// Slides of more than 4096 points (compute_features_hdf5.py:26,112-113: --max_patch_number is the user's) take
+// sq_kmeans_fit_large: the same arithmetic without the n x n Gram matrix -- a seeding step forms only its candidates'
+// distances, `closest` lives in global memory, member lists come from a chunked counting sort (section 5 below); the
+// Lloyd loop is one function for both entries.
 #include "../../include/sequoia_hip.h"
 #include "sq_common.h"
 
@@ -512,6 +516,7 @@ __global__ __launch_bounds__(1024) void km_assign_kernel(const double* __restric
 }
 
 // counting sort of point ids by label, stable in the point index: members[off[c] .. off[c+1])
+// (n <= 4096: one workgroup, labels in LDS; larger slides: km_lg_hist / km_lg_offsets / km_lg_scatter)
 __global__ __launch_bounds__(KM_THREADS) void km_members_kernel(const int* __restrict__ labels, int* __restrict__ members,
                                                                 int* __restrict__ offsets, const KmState* __restrict__ st, int n,
                                                                 int k, int force) {
@@ -717,6 +722,294 @@ __global__ void km_cluster_means_kernel(const float* __restrict__ X, const int* 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// 5. slides of more than 4096 points: seeding without the Gram matrix, member lists for any n
+// ------------------------------------------------------------------------------------------
+// The Gram route holds n^2 distances and all points of a slide in ONE workgroup's registers.  Here a seeding step only
+// forms the distances of its <= 8 candidates to all n points ([T, n] = Xc[cand] . Xc^T on the fp64 MFMA, 16-row M tile,
+// candidate rows gathered through device-side indices), `closest` lives in global memory, and a step is three plain
+// dependent launches: pick (scan + candidate search per 1024-point chunk), dist (product + distance epilogue +
+// per-tile potentials), choose (potentials -> winner -> `closest` update + chunk sums).  Every reduction has a fixed
+// association that depends on n alone (64-point tiles, 1024-point chunks, tiles / chunks combined in index order).
+// The dot products run through the MFMA in the K order of km_dgemm_nt_kernel (one accumulator, k ascending in steps
+// of 4), and the row norms are the diagonal of the same product, so x.x, x.c and c.c of two identical rows are the
+// same bits and a point's distance to itself or to a duplicate is exactly 0, as on the Gram route.
+constexpr int KM_LG_MAX_N = SQ_KMEANS_LARGE_MAX_SAMPLES;      // 65536, the stated bound of sq_kmeans_fit_large
+constexpr int KM_LG_CHUNK = 1024;                             // points per scan / sort chunk (one workgroup)
+constexpr int KM_LG_MAX_CHUNKS = KM_LG_MAX_N / KM_LG_CHUNK;   // 64
+constexpr int KM_LG_TILE = 64;                                // points per block of the distance product
+constexpr int KM_LG_MAX_TILES = KM_LG_MAX_N / KM_LG_TILE;     // 1024 = one partial per thread of the choose kernel
+
+struct KmLgBufs {         // per call (one slide), device memory
+    double* norms;        // [n] |x|^2 of the centred rows (fp64, MFMA association)
+    float* closest;       // [n] squared distance to the nearest chosen centre
+    float* distc;         // [KM_MAX_TRIALS][n] the step's candidate distances
+    double* part;         // [KM_MAX_TRIALS][KM_LG_MAX_TILES] per-tile potentials of the candidates
+    double* chunk_sum;    // [KM_LG_MAX_CHUNKS] sum of `closest` per chunk
+    int* cnt;             // [KM_MAX_TRIALS][KM_LG_MAX_CHUNKS] #{cumsum < u * pot} per chunk
+    int* cand;            // [KM_MAX_TRIALS] the step's candidates
+    float* pot;           // current potential
+    int* hist;            // [KM_LG_MAX_CHUNKS][KM_MAX_K] per-chunk label histogram, then per-chunk start inside the cluster
+};
+
+// MODE 0: norms[j] = x_j . x_j (diagonal of the 16 x 16 self product of each row group).
+// MODE 1: distc[t][j] = fl32(max(0, (-2 x_cand[t] . x_j + |x_cand[t]|^2) + |x_j|^2)) and the tile's share of every
+//         candidate's potential sum_j min(closest[j], distc[t][j]) (fp64; init: sum_j distc[0][j], the first centre).
+// block = 64 points (4 waves x 16) x 16 candidate rows (rows >= trials are zero).  A block walks the whole contraction
+// on one accumulator per wave, so what it waits for is the round trip of its loads: K goes in chunks of 128 (16 rounds at
+// D = 2048, ten 16-byte loads per thread in flight, issued before the 32 MFMAs of the chunk in hand), staged in LDS as
+// fp32 rows (k contiguous, +4 floats of padding: the MFMA operand reads hit 64 different banks) and widened on the way out.
+constexpr int KM_LG_KC = 128;
+template <int MODE>
+__global__ __launch_bounds__(256) void km_lg_rows_kernel(const float* __restrict__ Xc, double* __restrict__ norms,
+                                                         const int* __restrict__ cnt, int* __restrict__ cand_out,
+                                                         const float* __restrict__ closest, float* __restrict__ distc,
+                                                         double* __restrict__ part, int n, int D, int trials, int nchunks,
+                                                         int init, int first) {
+    __shared__ __attribute__((aligned(16))) float sa[MODE ? 16 : 1][KM_LG_KC + 4];
+    __shared__ __attribute__((aligned(16))) float sb[KM_LG_TILE][KM_LG_KC + 4];
+    __shared__ int cand_s[16];
+    __shared__ double psh[4][KM_MAX_TRIALS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j0 = blockIdx.x * KM_LG_TILE;
+    if (MODE) {
+        if (tid < 16) {
+            int c = 0;
+            if (tid < trials) {
+                if (init) c = first;
+                else {
+                    for (int b = 0; b < nchunks; ++b) c += cnt[tid * KM_LG_MAX_CHUNKS + b];      // searchsorted(side='left')
+                    c = c > n - 1 ? n - 1 : c;
+                }
+                if (blockIdx.x == 0) cand_out[tid] = c;
+            }
+            cand_s[tid] = c;
+        }
+        __syncthreads();
+    }
+    f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
+    // loader: float4 number tid + 256 u of the chunk, 32 of them per row: a wave reads two rows' 512 contiguous bytes
+    const int lk = (tid & 31) * 4, lr = tid >> 5;               // row lr + 8 u
+    const float* bp[8];
+    bool bok[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        bok[u] = j0 + lr + 8 * u < n;
+        bp[u] = Xc + (size_t)(bok[u] ? j0 + lr + 8 * u : 0) * D + lk;
+    }
+    const float* ap[2];
+    bool aok[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        aok[u] = MODE && lr + 8 * u < trials;
+        ap[u] = Xc + (size_t)(aok[u] ? cand_s[lr + 8 * u] : 0) * D + lk;
+    }
+    float4 va[2], vb[8];
+    auto fetch = [&](int k0) {
+        const bool kok = k0 + lk < D;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            va[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (aok[u] && kok) va[u] = *reinterpret_cast<const float4*>(ap[u] + k0);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            vb[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (bok[u] && kok) vb[u] = *reinterpret_cast<const float4*>(bp[u] + k0);
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < D; k0 += KM_LG_KC) {
+        if (MODE) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) *reinterpret_cast<float4*>(&sa[lr + 8 * u][lk]) = va[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) *reinterpret_cast<float4*>(&sb[lr + 8 * u][lk]) = vb[u];
+        __syncthreads();
+        if (k0 + KM_LG_KC < D) fetch(k0 + KM_LG_KC);
+        const int klim = min(KM_LG_KC, D - k0);                  // D % 4 == 0: whole MFMA steps, k ascending as in km_dgemm_nt_kernel
+        auto step = [&](int ks) {
+            const int kq = ks + (lane >> 4);
+            const double fb = (double)sb[wave * 16 + (lane & 15)][kq];
+            const double fa = MODE ? (double)sa[lane & 15][kq] : fb;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, fb, acc, 0, 0, 0);
+        };
+        int ks = 0;
+        for (; ks + 32 <= klim; ks += 32) {
+#pragma unroll
+            for (int q = 0; q < 32; q += 4) step(ks + q);
+        }
+        for (; ks < klim; ks += 4) step(ks);
+        __syncthreads();
+    }
+    // f64 C/D layout: col (point) = lane & 15, row (candidate) = (lane >> 4) + 4 * reg
+    const int j = j0 + wave * 16 + (lane & 15);
+    if (!MODE) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if ((lane >> 4) + 4 * r == (lane & 15) && j < n) norms[j] = acc[r];
+        return;
+    }
+    const double nj = j < n ? norms[j] : 0.0;
+    const float cl = (j < n && !init) ? closest[j] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {                                // candidate rows 0..7 (KM_MAX_TRIALS)
+        const int t = (lane >> 4) + 4 * r;
+        double pv = 0.0;
+        if (t < trials && j < n) {
+            double d = -2.0 * acc[r];
+            d += norms[cand_s[t]];
+            d += nj;
+            float f = (float)d;
+            f = f > 0.f ? f : 0.f;
+            distc[(size_t)t * n + j] = f;
+            pv = (double)(init ? f : fminf(cl, f));
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) pv += __shfl_xor(pv, o, 64);      // the 16 points of this wave, fixed butterfly
+        if ((lane & 15) == 0) psh[wave][t] = pv;
+    }
+    __syncthreads();
+    if (tid < trials) part[(size_t)tid * KM_LG_MAX_TILES + blockIdx.x] = ((psh[0][tid] + psh[1][tid]) + psh[2][tid]) + psh[3][tid];
+}
+
+// stable_cumsum (fp64) of `closest` over chunk b (chunk sums added in chunk order in front of a blocked scan) and, for
+// every trial, how many of the chunk's points have cumsum < u * pot
+__global__ __launch_bounds__(KM_LG_CHUNK) void km_lg_pick_kernel(const float* __restrict__ closest, const double* __restrict__ chunk_sum,
+                                                                 const float* __restrict__ pot, const double* __restrict__ uniforms,
+                                                                 int* __restrict__ cnt, int n, int trials) {
+    __shared__ double scan_w[16];
+    __shared__ int shi[16][KM_MAX_TRIALS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int j = blockIdx.x * KM_LG_CHUNK + tid;
+    double base = 0.0;
+    for (int b = 0; b < (int)blockIdx.x; ++b) base += chunk_sum[b];
+    const double v = j < n ? (double)closest[j] : 0.0;
+    double wscan = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double t = __shfl_up(wscan, o, 64);
+        if (lane >= o) wscan += t;
+    }
+    if (lane == 63) scan_w[wv] = wscan;
+    __syncthreads();
+    double woff = base;
+    for (int i = 0; i < wv; ++i) woff += scan_w[i];
+    const double cum = woff + wscan;
+    const double p = (double)pot[0];
+#pragma unroll
+    for (int t = 0; t < KM_MAX_TRIALS; ++t) {
+        if (t < trials) {
+            const double rv = uniforms[t] * p;
+            const int c = __popcll(__ballot(j < n && cum < rv));
+            if (lane == 0) shi[wv][t] = c;
+        }
+    }
+    __syncthreads();
+    if (tid < trials) {
+        int r = 0;
+        for (int i = 0; i < 16; ++i) r += shi[i][tid];
+        cnt[tid * KM_LG_MAX_CHUNKS + blockIdx.x] = r;
+    }
+}
+
+// potentials fl32(sum_fp64) of the candidates (tile shares, one per thread, reduced in a fixed tree), np.argmin
+// (first minimum); then closest = min(closest, winner's distances) for this block's chunk and the chunk's new sum.
+// Every block takes the same decision from the same numbers; block 0 records it.
+__global__ __launch_bounds__(KM_LG_CHUNK) void km_lg_choose_kernel(const double* __restrict__ part, const float* __restrict__ distc,
+                                                                   const int* __restrict__ cand, float* __restrict__ closest,
+                                                                   double* __restrict__ chunk_sum, float* __restrict__ pot,
+                                                                   int* __restrict__ seed_out, int n, int trials, int ntiles, int init) {
+    __shared__ double sh[16 * KM_MAX_TRIALS];
+    const int tid = threadIdx.x;
+    double p[KM_MAX_TRIALS];
+#pragma unroll
+    for (int t = 0; t < KM_MAX_TRIALS; ++t) p[t] = (t < trials && tid < ntiles) ? part[(size_t)t * KM_LG_MAX_TILES + tid] : 0.0;
+    block_reduce_sum_n<KM_MAX_TRIALS>(p, sh);
+    float best_pot = 0.f;
+    int best_t = 0;
+#pragma unroll
+    for (int t = 0; t < KM_MAX_TRIALS; ++t) {
+        if (t < trials) {
+            const float pt = (float)p[t];
+            if (t == 0 || pt < best_pot) { best_pot = pt; best_t = t; }
+        }
+    }
+    const int j = blockIdx.x * KM_LG_CHUNK + tid;
+    double c = 0.0;
+    if (j < n) {
+        const float f = distc[(size_t)best_t * n + j];
+        const float m = init ? f : fminf(closest[j], f);
+        closest[j] = m;
+        c = (double)m;
+    }
+    c = block_reduce_sum(c, sh);
+    if (tid == 0) {
+        chunk_sum[blockIdx.x] = c;
+        if (blockIdx.x == 0) { pot[0] = best_pot; seed_out[0] = cand[best_t]; }
+    }
+}
+
+// Member lists for any n: a counting sort of point ids by label, stable in the point index, in three launches --
+// per-chunk histograms; a scan over the chunks in chunk order (per cluster) and over the clusters; scatter with the
+// rank inside the chunk.  Gives exactly the members / offsets of km_members_kernel.
+__global__ __launch_bounds__(KM_LG_CHUNK) void km_lg_hist_kernel(const int* __restrict__ labels, int* __restrict__ hist,
+                                                                 const KmState* __restrict__ st, int n, int k, int force) {
+    __shared__ int h[KM_MAX_K];
+    if (st[0].done && !force) return;
+    if (threadIdx.x < KM_MAX_K) h[threadIdx.x] = 0;
+    __syncthreads();
+    const int j = blockIdx.x * KM_LG_CHUNK + threadIdx.x;
+    if (j < n) {
+        const int lab = labels[j];
+        if ((unsigned)lab < (unsigned)k) atomicAdd(&h[lab], 1);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < k) hist[blockIdx.x * KM_MAX_K + threadIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(KM_MAX_K) void km_lg_offsets_kernel(int* __restrict__ hist, int* __restrict__ offsets,
+                                                                 const KmState* __restrict__ st, int nchunks, int k, int force) {
+    __shared__ int soff[KM_MAX_K + 1];
+    if (st[0].done && !force) return;
+    const int c = threadIdx.x;
+    if (c < k) {
+        int run = 0;
+        for (int b = 0; b < nchunks; ++b) {
+            const int t = hist[b * KM_MAX_K + c];
+            hist[b * KM_MAX_K + c] = run;          // members of cluster c in earlier chunks
+            run += t;
+        }
+        soff[c + 1] = run;
+    }
+    __syncthreads();
+    if (c == 0) {
+        soff[0] = 0;
+        for (int i = 0; i < k; ++i) soff[i + 1] += soff[i];
+    }
+    __syncthreads();
+    for (int i = c; i <= k; i += blockDim.x) offsets[i] = soff[i];
+}
+
+__global__ __launch_bounds__(KM_LG_CHUNK) void km_lg_scatter_kernel(const int* __restrict__ labels, const int* __restrict__ hist,
+                                                                    const int* __restrict__ offsets, int* __restrict__ members,
+                                                                    const KmState* __restrict__ st, int n, int k, int force) {
+    __shared__ int slab[KM_LG_CHUNK];
+    if (st[0].done && !force) return;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.x * KM_LG_CHUNK + tid;
+    const int lab = j < n ? labels[j] : -1;
+    slab[tid] = lab;
+    __syncthreads();
+    if ((unsigned)lab >= (unsigned)k) return;
+    int rank = 0;
+    for (int i = 0; i < tid; ++i) rank += slab[i] == lab;
+    const int pos = offsets[lab] + hist[blockIdx.x * KM_MAX_K + lab] + rank;
+    if (pos < n) members[pos] = j;
+}
+
+
 struct KmBufs {
     float* Xc; double* colvar; double* G; float* centers; float* centers2; double* shift_part; double* dots; double* sums; double* weights; double* dist;
     int* seeds; int* labels_old; int* members; int* offsets; int* done_count; KmState* st;
@@ -724,12 +1017,13 @@ struct KmBufs {
     size_t bytes;
 };
 
-void km_bufs(int S, int n, int D, int k, char* base, KmBufs* o) {
+// lg != nullptr: the large-slide route (no Gram matrix, no n^2 distances; its own seeding / sort buffers behind the rest)
+void km_bufs(int S, int n, int D, int k, char* base, KmBufs* o, KmLgBufs* lg = nullptr) {
     size_t off = 0;
     auto take = [&](size_t bytes) { off = sq_align_up(off, 256); char* p = base ? base + off : nullptr; off += bytes; return (void*)p; };
     o->Xc = (float*)take((size_t)S * n * D * 4);
     o->colvar = (double*)take((size_t)S * D * 8);
-    o->G = (double*)take((size_t)S * n * n * 8);
+    o->G = (double*)take(lg ? 0 : (size_t)S * n * n * 8);
     o->centers = (float*)take((size_t)S * k * D * 4);
     o->centers2 = (float*)take((size_t)S * k * D * 4);
     o->shift_part = (double*)take((size_t)S * k * 8 * 2);      // [S][k] shift shares, then [S][k] centre norms
@@ -743,8 +1037,99 @@ void km_bufs(int S, int n, int D, int k, char* base, KmBufs* o) {
     o->offsets = (int*)take((size_t)S * (k + 1) * 4);
     o->done_count = (int*)take(256);
     o->st = (KmState*)take((size_t)S * sizeof(KmState));
-    o->dist32 = (float*)take((size_t)S * n * n * 4);
+    o->dist32 = (float*)take(lg ? 0 : (size_t)S * n * n * 4);
+    if (lg) {
+        lg->norms = (double*)take((size_t)n * 8);
+        lg->closest = (float*)take((size_t)n * 4);
+        lg->distc = (float*)take((size_t)KM_MAX_TRIALS * n * 4);
+        lg->part = (double*)take((size_t)KM_MAX_TRIALS * KM_LG_MAX_TILES * 8);
+        lg->chunk_sum = (double*)take((size_t)KM_LG_MAX_CHUNKS * 8);
+        lg->cnt = (int*)take((size_t)KM_MAX_TRIALS * KM_LG_MAX_CHUNKS * 4);
+        lg->cand = (int*)take(KM_MAX_TRIALS * 4);
+        lg->pot = (float*)take(4);
+        lg->hist = (int*)take((size_t)KM_LG_MAX_CHUNKS * KM_MAX_K * 4);
+    }
     o->bytes = sq_align_up(off, 256);
+}
+
+// The Lloyd loop, the final E-step and the cluster means, shared by sq_kmeans_fit and sq_kmeans_fit_large: expects the
+// centred data, the tolerance state, the seeded centres in b.centers and labels_old = -1.  lg == nullptr: member lists
+// by km_members_kernel (n <= 4096, any S); otherwise by the three-launch counting sort (any n, S == 1).
+int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter, int32_t* labels, float* cluster_features,
+                       int32_t* n_iter, const KmBufs& b, const KmLgBufs* lg, hipStream_t st) {
+    auto members = [&](int force) -> int {
+        if (!lg) {
+            hipLaunchKernelGGL(km_members_kernel, dim3(S), dim3(KM_THREADS), 0, st, labels, b.members, b.offsets, b.st, n, k, force);
+            SQ_LAUNCH_CHECK();
+            return SQ_OK;
+        }
+        const int nchunks = (n + KM_LG_CHUNK - 1) / KM_LG_CHUNK;
+        hipLaunchKernelGGL(km_lg_hist_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, labels, lg->hist, b.st, n, k, force);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_lg_offsets_kernel, dim3(1), dim3(KM_MAX_K), 0, st, lg->hist, b.offsets, b.st, nchunks, k, force);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_lg_scatter_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, labels, lg->hist, b.offsets, b.members, b.st, n, k, force);
+        SQ_LAUNCH_CHECK();
+        return SQ_OK;
+    };
+    float* cur = b.centers;          // centres of the iteration in flight; the update writes the other buffer
+    float* nxt = b.centers2;
+    const int ksl = D >= 32 * KM_DOT_SLICES ? KM_DOT_SLICES : 1;
+    auto e_step = [&](int force) -> int {
+        // dots[slice][centre][point] = centres . points (fp64), K sliced so that the launch fills the chip
+        hipLaunchKernelGGL(km_dgemm_nt_kernel, dim3((n + 63) / 64, (k + 63) / 64, S * ksl), dim3(256), 0, st, cur, b.Xc, b.dots, k, n, D,
+                           (long long)k * D, (long long)n * D, (long long)k * n, ksl, 0);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_center_norms_kernel, dim3(k, S), dim3(64), 0, st, cur, b.shift_part + (size_t)S * k, b.st, D, k, force);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_assign_kernel, dim3((n + 63) / 64, S), dim3(1024), 0, st, b.dots, b.shift_part + (size_t)S * k, labels, b.st, n, D, k, force, ksl);
+        SQ_LAUNCH_CHECK();
+        return members(force);
+    };
+    int it = 0;
+    int done[2] = {0, 0};            // slides finished / of those, strictly converged (labels unchanged)
+    while (it < max_iter) {
+        const int burst = it == 0 ? 2 : 4;      // iterations between host checks of the done flags
+        for (int q = 0; q < burst && it < max_iter; ++q, ++it) {
+            if (int e = e_step(0)) return e;
+            hipLaunchKernelGGL(km_sums_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.members, b.offsets, b.sums, b.st, n, D, k);
+            SQ_LAUNCH_CHECK();
+            hipLaunchKernelGGL(km_relocate_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.Xc, cur, labels, b.offsets, b.sums,
+                               b.weights, b.dist, b.st, n, D, k);
+            SQ_LAUNCH_CHECK();
+            hipLaunchKernelGGL(km_update_centers_kernel, dim3(k, S), dim3(256), 0, st, cur, nxt, b.sums, b.weights, b.shift_part, b.st, D, k);
+            SQ_LAUNCH_CHECK();
+            hipLaunchKernelGGL(km_finish_iter_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.shift_part, labels, b.labels_old, b.st, n, k, max_iter);
+            SQ_LAUNCH_CHECK();
+            float* t = cur; cur = nxt; nxt = t;
+        }
+        hipLaunchKernelGGL(km_count_done_kernel, dim3(1), dim3(64), 0, st, b.st, S, b.done_count);
+        SQ_LAUNCH_CHECK();
+        SQ_HIP_CHECK(hipMemcpyAsync(done, b.done_count, 8, hipMemcpyDeviceToHost, st));
+        SQ_HIP_CHECK(hipStreamSynchronize(st));
+        if (done[0] == S) break;
+    }
+    // final E-step for the slides that did not converge strictly (labels must match the final centres).
+    // For strictly converged slides the labels of the last E-step are already the answer and the
+    // centres moved by a label-preserving update, so re-running the E-step for everyone is only
+    // correct for the non-strict ones: the assign kernel is forced, then strict slides are restored.
+    // When every slide converged strictly (the common case) nothing is left to do: labels and member lists are
+    // those of the last E-step (_kmeans.py: the extra E-step runs only `if not strict_convergence`).
+    if (!(done[0] == S && done[1] == S)) {
+        // strict slides keep labels (== labels_old after the last update); non-strict get a fresh E-step
+        if (int e = e_step(1)) return e;
+        // restore labels of strict slides from labels_old and rebuild their member lists
+        hipLaunchKernelGGL(km_restore_strict_kernel, dim3((n + 255) / 256, S), dim3(256), 0, st, labels, (const int*)b.labels_old, (const KmState*)b.st, n);
+        SQ_LAUNCH_CHECK();
+        if (int e = members(1)) return e;
+    }
+    if (cluster_features) {
+        hipLaunchKernelGGL(km_cluster_means_kernel, dim3(k, S), dim3(256), 0, st, X, b.members, b.offsets, cluster_features, n, D, k);
+        SQ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(km_report_kernel, dim3((S + 63) / 64), dim3(64), 0, st, b.st, S, n_iter);
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
 }
 
 }  // namespace
@@ -797,65 +1182,64 @@ extern "C" int sq_kmeans_fit(const float* X, int S, int n, int D, int k, int fir
     SQ_LAUNCH_CHECK();
     SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, (size_t)S * n * 4, st));          // labels_old = -1
 
-    float* cur = b.centers;          // centres of the iteration in flight; the update writes the other buffer
-    float* nxt = b.centers2;
-    const int ksl = D >= 32 * KM_DOT_SLICES ? KM_DOT_SLICES : 1;
-    auto e_step = [&](int force) -> int {
-        // dots[slice][centre][point] = centres . points (fp64), K sliced so that the launch fills the chip
-        hipLaunchKernelGGL(km_dgemm_nt_kernel, dim3((n + 63) / 64, (k + 63) / 64, S * ksl), dim3(256), 0, st, cur, b.Xc, b.dots, k, n, D,
-                           (long long)k * D, (long long)n * D, (long long)k * n, ksl, 0);
-        SQ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_center_norms_kernel, dim3(k, S), dim3(64), 0, st, cur, b.shift_part + (size_t)S * k, b.st, D, k, force);
-        SQ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_assign_kernel, dim3((n + 63) / 64, S), dim3(1024), 0, st, b.dots, b.shift_part + (size_t)S * k, labels, b.st, n, D, k, force, ksl);
-        SQ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_members_kernel, dim3(S), dim3(KM_THREADS), 0, st, labels, b.members, b.offsets, b.st, n, k, force);
-        SQ_LAUNCH_CHECK();
-        return SQ_OK;
-    };
-    int it = 0;
-    int done[2] = {0, 0};            // slides finished / of those, strictly converged (labels unchanged)
-    while (it < max_iter) {
-        const int burst = it == 0 ? 2 : 4;      // iterations between host checks of the done flags
-        for (int q = 0; q < burst && it < max_iter; ++q, ++it) {
-            if (int e = e_step(0)) return e;
-            hipLaunchKernelGGL(km_sums_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.members, b.offsets, b.sums, b.st, n, D, k);
-            SQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(km_relocate_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.Xc, cur, labels, b.offsets, b.sums,
-                               b.weights, b.dist, b.st, n, D, k);
-            SQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(km_update_centers_kernel, dim3(k, S), dim3(256), 0, st, cur, nxt, b.sums, b.weights, b.shift_part, b.st, D, k);
-            SQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(km_finish_iter_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.shift_part, labels, b.labels_old, b.st, n, k, max_iter);
-            SQ_LAUNCH_CHECK();
-            float* t = cur; cur = nxt; nxt = t;
-        }
-        hipLaunchKernelGGL(km_count_done_kernel, dim3(1), dim3(64), 0, st, b.st, S, b.done_count);
-        SQ_LAUNCH_CHECK();
-        SQ_HIP_CHECK(hipMemcpyAsync(done, b.done_count, 8, hipMemcpyDeviceToHost, st));
-        SQ_HIP_CHECK(hipStreamSynchronize(st));
-        if (done[0] == S) break;
+    return km_lloyd_and_means(X, S, n, D, k, max_iter, labels, cluster_features, n_iter, b, nullptr, st);
+}
+
+extern "C" size_t sq_kmeans_large_workspace_bytes(int n_samples, int dim, int n_clusters) {
+    if (n_samples < 1 || n_samples > KM_LG_MAX_N || dim < 1 || n_clusters < 1) return 0;
+    KmBufs b;
+    KmLgBufs lg;
+    km_bufs(1, n_samples, dim, n_clusters, nullptr, &b, &lg);
+    return b.bytes;
+}
+
+extern "C" int sq_kmeans_fit_large(const float* X, int n, int D, int k, int first_center, const double* uniforms,
+                                   int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
+                                   int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes,
+                                   sq_stream_t stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    SQ_REQUIRE(n <= KM_LG_MAX_N, "kmeans (large): n_samples=%d > %d per slide", n, KM_LG_MAX_N);
+    SQ_REQUIRE(X && labels && uniforms && workspace, "kmeans (large): null pointer");
+    SQ_REQUIRE(n >= k && k >= 1 && k <= KM_MAX_K, "kmeans (large): need n_samples >= n_clusters and 1 <= n_clusters <= %d (n=%d k=%d)", KM_MAX_K, n, k);
+    SQ_REQUIRE(D >= 4 && D % 4 == 0, "kmeans (large): dim=%d must be a multiple of 4", D);
+    SQ_REQUIRE(n_local_trials >= 1 && n_local_trials <= KM_MAX_TRIALS, "kmeans (large): n_local_trials=%d", n_local_trials);
+    SQ_REQUIRE(first_center >= 0 && first_center < n, "kmeans (large): first_center=%d", first_center);
+    KmBufs b;
+    KmLgBufs lg;
+    km_bufs(1, n, D, k, (char*)workspace, &b, &lg);
+    if (b.bytes > workspace_bytes) {
+        sq_set_error("kmeans (large): workspace %zu < required %zu", workspace_bytes, b.bytes);
+        return SQ_ERR_WORKSPACE;
     }
-    // final E-step for the slides that did not converge strictly (labels must match the final centres).
-    // For strictly converged slides the labels of the last E-step are already the answer and the
-    // centres moved by a label-preserving update, so re-running the E-step for everyone is only
-    // correct for the non-strict ones: the assign kernel is forced, then strict slides are restored.
-    // When every slide converged strictly (the common case) nothing is left to do: labels and member lists are
-    // those of the last E-step (_kmeans.py: the extra E-step runs only `if not strict_convergence`).
-    if (!(done[0] == S && done[1] == S)) {
-        // strict slides keep labels (== labels_old after the last update); non-strict get a fresh E-step
-        if (int e = e_step(1)) return e;
-        // restore labels of strict slides from labels_old and rebuild their member lists
-        hipLaunchKernelGGL(km_restore_strict_kernel, dim3((n + 255) / 256, S), dim3(256), 0, st, labels, (const int*)b.labels_old, (const KmState*)b.st, n);
-        SQ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_members_kernel, dim3(S), dim3(KM_THREADS), 0, st, labels, b.members, b.offsets, b.st, n, k, 1);
-        SQ_LAUNCH_CHECK();
-    }
-    if (cluster_features) {
-        hipLaunchKernelGGL(km_cluster_means_kernel, dim3(k, S), dim3(256), 0, st, X, b.members, b.offsets, cluster_features, n, D, k);
-        SQ_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(km_report_kernel, dim3((S + 63) / 64), dim3(64), 0, st, b.st, S, n_iter);
+    const int nchunks = (n + KM_LG_CHUNK - 1) / KM_LG_CHUNK, ntiles = (n + KM_LG_TILE - 1) / KM_LG_TILE;
+    hipLaunchKernelGGL(km_center_kernel, dim3((D + KC_COLS - 1) / KC_COLS, 1), dim3(256), 0, st, X, b.Xc, b.colvar, n, D);
     SQ_LAUNCH_CHECK();
-    return SQ_OK;
+    hipLaunchKernelGGL(km_tol_kernel, dim3(1), dim3(256), 0, st, b.colvar, b.st, D, tol);
+    SQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_lg_rows_kernel<0>, dim3(ntiles), dim3(256), 0, st, (const float*)b.Xc, lg.norms, (const int*)nullptr, (int*)nullptr,
+                       (const float*)nullptr, (float*)nullptr, (double*)nullptr, n, D, 0, nchunks, 0, 0);
+    SQ_LAUNCH_CHECK();
+    // the first centre: closest = its distances, pot = their sum
+    hipLaunchKernelGGL(km_lg_rows_kernel<1>, dim3(ntiles), dim3(256), 0, st, (const float*)b.Xc, lg.norms, (const int*)lg.cnt, lg.cand,
+                       (const float*)lg.closest, lg.distc, lg.part, n, D, 1, nchunks, 1, first_center);
+    SQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_lg_choose_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, (const double*)lg.part, (const float*)lg.distc,
+                       (const int*)lg.cand, lg.closest, lg.chunk_sum, lg.pot, b.seeds, n, 1, ntiles, 1);
+    SQ_LAUNCH_CHECK();
+    for (int c = 1; c < k; ++c) {       // k - 1 dependent steps of three launches; the candidates never leave the device
+        hipLaunchKernelGGL(km_lg_pick_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, (const float*)lg.closest, (const double*)lg.chunk_sum,
+                           (const float*)lg.pot, uniforms + (size_t)(c - 1) * n_local_trials, lg.cnt, n, n_local_trials);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_lg_rows_kernel<1>, dim3(ntiles), dim3(256), 0, st, (const float*)b.Xc, lg.norms, (const int*)lg.cnt, lg.cand,
+                           (const float*)lg.closest, lg.distc, lg.part, n, D, n_local_trials, nchunks, 0, 0);
+        SQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL(km_lg_choose_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, (const double*)lg.part, (const float*)lg.distc,
+                           (const int*)lg.cand, lg.closest, lg.chunk_sum, lg.pot, b.seeds + c, n, n_local_trials, ntiles, 0);
+        SQ_LAUNCH_CHECK();
+    }
+    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)k * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(km_gather_centers_kernel, dim3(k, 1), dim3(256), 0, st, b.Xc, b.seeds, b.centers, n, D, k);
+    SQ_LAUNCH_CHECK();
+    SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, (size_t)n * 4, st));          // labels_old = -1
+    return km_lloyd_and_means(X, 1, n, D, k, max_iter, labels, cluster_features, n_iter, b, &lg, st);
 }

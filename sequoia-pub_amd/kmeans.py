@@ -1,6 +1,7 @@
 """KMeans -- host-side mirror of the interface /root/reference/pre_processing/kmean_features.py:96-97
 uses (``sklearn.cluster.KMeans(n_clusters, random_state=0).fit(X).labels_``) plus the cluster-mean
-step of :99-108, on the HIP k-means kernels (``sq_kmeans_fit``).
+step of :99-108, on the HIP k-means kernels (``sq_kmeans_fit``; ``sq_kmeans_fit_large`` for slides of more
+than ``GRAM_MAX_ROWS`` patches, which a raised ``--max_patch_number`` produces: compute_features_hdf5.py:26,112-113).
 
 The only host arithmetic is the data-independent MT19937 draw sequence of scikit-learn's
 ``_kmeans_plusplus`` (``RandomState(random_state).choice(n, p=uniform)`` then ``uniform(size=2+log k)``
@@ -22,6 +23,9 @@ def seeding_draws(n_samples, n_clusters, random_state=0):
         u[c] = rs.uniform(size=trials)
     return first, u
 
+
+GRAM_MAX_ROWS = 4096          # sq_kmeans_fit seeds from one n x n Gram matrix per slide and stops here
+LARGE_MAX_ROWS = 65536        # SQ_KMEANS_LARGE_MAX_SAMPLES, the bound of sq_kmeans_fit_large
 
 _draws_cache = {}
 
@@ -65,6 +69,53 @@ def kmeans_fit_batch(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, 
     return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
 
 
+def _fit_large(X, n_clusters, random_state, max_iter, tol, want_means):
+    """One slide [n, D] through sq_kmeans_fit_large (any n_clusters <= n <= LARGE_MAX_ROWS).  The size is checked before
+    anything is allocated or copied."""
+    n, D = X.shape
+    dev = X.device
+    L = _lib.lib()
+    need = L.sq_kmeans_large_workspace_bytes(n, D, n_clusters)
+    if need == 0:          # a size the entry refuses: let it say why (it names its bound) before anything is allocated
+        _lib.check(L.sq_kmeans_fit_large(None, n, D, n_clusters, 0, None, 1, max_iter, float(tol), None, None, None, None, None, 0, None))
+        raise _lib.SequoiaHipError(f"kmeans (large): unsupported size n={n} dim={D} k={n_clusters}")
+    X = X.to(torch.float32).contiguous()
+    first, u_dev, trials = _device_draws(n, n_clusters, random_state, dev)
+    labels = torch.empty(1, n, dtype=torch.int32, device=dev)
+    means = torch.empty(1, n_clusters, D, dtype=torch.float32, device=dev) if want_means else None
+    seeds = torch.empty(1, n_clusters, dtype=torch.int32, device=dev)
+    n_iter = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.sq_kmeans_fit_large(_lib.ptr(X), n, D, n_clusters, first, _lib.ptr(u_dev), trials, max_iter, float(tol),
+                                         _lib.ptr(labels), _lib.ptr(means), _lib.ptr(seeds), _lib.ptr(n_iter), _lib.ptr(ws), need,
+                                         _lib.stream_ptr(dev)))
+    return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
+
+
+def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_means=True, *, route=None):
+    """ONE slide: X f32 [n, D] (or [1, n, D]) CUDA tensor of any patch count up to LARGE_MAX_ROWS.  Returns the dict of
+    kmeans_fit_batch for S = 1: labels i32 [1, n], cluster_features f32 [1, k, D], indices i32 [1, k], n_iter i32 [1].
+
+    The kernels are chosen from the row count alone: n <= GRAM_MAX_ROWS runs kmeans_fit_batch (seeding from the slide's
+    Gram matrix), larger slides run sq_kmeans_fit_large (per-step candidate distances, chunked member sort; the same
+    Lloyd kernels).  ``route`` is a TEST HOOK, keyword-only: "large" sends a small slide through the large-slide entry so
+    that the tests can compare the two routes where both exist; "gram" forces the other; leave it None otherwise."""
+    _lib.require_gpu()
+    if X.dim() == 3 and X.shape[0] == 1:
+        X = X[0]
+    if X.dim() != 2:
+        raise _lib.SequoiaHipError(f"kmeans_fit takes one slide [n, D], got shape {tuple(X.shape)}")
+    if not X.is_cuda:
+        raise _lib.SequoiaHipError("kmeans_fit needs a CUDA tensor (no CPU fallback)")
+    if route not in (None, "gram", "large"):
+        raise ValueError(f"route={route!r}")
+    large = X.shape[0] > GRAM_MAX_ROWS if route is None else route == "large"
+    if not large:
+        return kmeans_fit_batch(X.unsqueeze(0), n_clusters, random_state, max_iter, tol, want_means)
+    return _fit_large(X, n_clusters, random_state, max_iter, tol, want_means)
+
+
 class KMeans:
     """The subset of sklearn.cluster.KMeans the reference touches: constructor (n_clusters,
     random_state), ``fit(X)``, ``labels_``; also ``cluster_features_`` (kmean_features.py:99-105)."""
@@ -80,7 +131,7 @@ class KMeans:
         X = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
         if X.shape[0] < self.n_clusters:
             raise ValueError(f"n_samples={X.shape[0]} should be >= n_clusters={self.n_clusters}.")
-        r = kmeans_fit_batch(torch.from_numpy(X).to(self.device), self.n_clusters, self.random_state, self.max_iter, self.tol)
+        r = kmeans_fit(torch.from_numpy(X).to(self.device), self.n_clusters, self.random_state, self.max_iter, self.tol)
         self.labels_ = r["labels"][0].cpu().numpy()
         self.cluster_features_ = r["cluster_features"][0].cpu().numpy()
         self.seed_indices_ = r["indices"][0].cpu().numpy()
