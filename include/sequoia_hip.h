@@ -123,7 +123,9 @@ int sq_vis_forward_tiles(const sq_vis_config* cfg, int dtype, const float* param
 /* Backward of ViS.forward -- replaces torch autograd over tformer_lin.py in the training loop
  * (src/vit.py:163-180 `loss.backward()`).  grad_out f32 [B, G]; grad_params: flat f32 buffer with
  * the parameter layout, fully overwritten; grad_x f32 [B, num_clusters, D] or NULL.
- * fwd_workspace must be the workspace of the matching sq_vis_forward(save_for_backward = 1). */
+ * fwd_workspace must be the workspace of the matching sq_vis_forward(save_for_backward = 1).
+ * Training needs nheads to be a power of two (1, 2, 4, ..., 64); the forward pass takes any nheads in 1..64.  Another nheads is
+ * refused with SQ_ERR_ARG before anything is launched (sq_vis_backward_workspace_bytes returns 0 and sets the same message). */
 size_t sq_vis_backward_workspace_bytes(const sq_vis_config* cfg, int dtype, int batch);
 int sq_vis_backward(const sq_vis_config* cfg, int dtype, const float* params, const void* params_lp,
                     const float* grad_out, float* grad_params, float* grad_x, int batch, void* fwd_workspace,
@@ -177,6 +179,9 @@ int sq_vit_forward(const sq_vit_config* cfg, int dtype, const float* params, con
 int sq_vit_forward_ex(const sq_vit_config* cfg, int dtype, const float* params, const void* params_lp, const float* x,
                       const float* gather_src, const int32_t* gather_idx, int gather_rows, float* out, float* head_in,
                       int batch, int save_for_backward, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+/* Backward of sq_vit_forward(save_for_backward = 1).  The attention backward kernel keeps one (slide, head) in LDS --
+ * 4 * (257 N + N^2) bytes of the 160 KiB -- so it needs num_clusters <= 111; the forward pass takes num_clusters up to 128.
+ * 112..128 are refused with SQ_ERR_ARG before anything is launched. */
 size_t sq_vit_backward_workspace_bytes(const sq_vit_config* cfg, int dtype, int batch);
 int sq_vit_backward(const sq_vit_config* cfg, int dtype, const float* params, const void* params_lp,
                     const float* grad_out, float* grad_params, float* grad_x, int batch, void* fwd_workspace,

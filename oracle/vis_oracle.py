@@ -183,6 +183,50 @@ def adamw_step(params, grads, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.
 # ---------------------------------------------------------------------------
 # ViT baseline (src/vit.py:49-115) -- secondary model on the same loops
 # ---------------------------------------------------------------------------
+def init_vit_state_dict(num_outputs, dim, depth, heads, mlp_dim, dim_head=64, num_clusters=100, seed=0):
+    """Seeded synthetic ViT weights with the reference's key names and default-init distributions (vit.py:96-104:
+    randn pos-emb, bias-free to_qkv / to_out, nn.Linear FeedForward and head, LayerNorm ones/zeros).  Like
+    ``init_vis_state_dict`` the draw order is this oracle's own.  ``heads * dim_head`` need not equal ``dim``.
+    """
+    g = torch.Generator().manual_seed(seed)
+    inner = heads * dim_head
+
+    def linear(out_f, in_f):
+        bound = 1.0 / math.sqrt(in_f)
+        w = (torch.rand(out_f, in_f, generator=g) * 2 - 1) * bound
+        b = (torch.rand(out_f, generator=g) * 2 - 1) * bound
+        return w, b
+
+    sd = OrderedDict()
+    sd["pos_emb1D"] = torch.randn(num_clusters, dim, generator=g)
+    for l in range(depth):
+        p = f"transformer.layers.{l}.0."
+        sd[p + "norm.weight"] = torch.ones(dim)
+        sd[p + "norm.bias"] = torch.zeros(dim)
+        sd[p + "to_qkv.weight"] = linear(3 * inner, dim)[0]
+        sd[p + "to_out.weight"] = linear(dim, inner)[0]
+        p = f"transformer.layers.{l}.1.net."
+        sd[p + "0.weight"] = torch.ones(dim)
+        sd[p + "0.bias"] = torch.zeros(dim)
+        sd[p + "1.weight"], sd[p + "1.bias"] = linear(mlp_dim, dim)
+        sd[p + "3.weight"], sd[p + "3.bias"] = linear(dim, mlp_dim)
+    sd["linear_head.0.weight"] = torch.ones(dim)
+    sd["linear_head.0.bias"] = torch.zeros(dim)
+    sd["linear_head.1.weight"], sd["linear_head.1.bias"] = linear(num_outputs, dim)
+    return sd
+
+
+def vit_loss_and_grads(sd, x, target, heads):
+    """MSELoss(mean) forward + autograd backward of the ViT; also returns the gradient w.r.t. the input tokens."""
+    leaf = OrderedDict((k, v.detach().clone().requires_grad_(True)) for k, v in sd.items())
+    xl = x.detach().clone().requires_grad_(True)
+    pred = vit_forward(leaf, xl, heads)
+    loss = F.mse_loss(pred, target)
+    loss.backward()
+    grads = OrderedDict((k, v.grad) for k, v in leaf.items())
+    return loss.detach(), pred.detach(), grads, xl.grad
+
+
 def vit_attention(sd, prefix, x, heads):
     """vit.py:62-74 (Attention.forward)."""
     D = x.shape[-1]

@@ -99,11 +99,20 @@ void bwd_bufs(const sq_vis_config& c, int dtype, int B, char* base, BwdBufs* o) 
     o->bytes = sq_align_up(a.off, 256);
 }
 
+// The LayerNorm(64) + GELU backward kernels split a row of nheads * 64 columns over a power-of-two number of lanes
+// (elementwise_bwd.hip: sq_k_ln64_gelu_bwd_any), so training needs nheads in {1, 2, 4, 8, 16, 32, 64}; the forward pass
+// takes any nheads in 1..64.  Checked before anything is launched: a refused call leaves no work queued on any stream.
+int check_bwd_cfg(const sq_vis_config* c) {
+    SQ_REQUIRE((c->nheads & (c->nheads - 1)) == 0,
+               "vis_backward: nheads=%d: nheads must be a power of two <= 64 for the training path (the forward pass takes any nheads in 1..64)", c->nheads);
+    return SQ_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sq_vis_backward_workspace_bytes(const sq_vis_config* c, int dtype, int batch) {
     sq_vis_layout lay;
-    if (sq_vis_layout_init(c, &lay) != SQ_OK || batch < 1) return 0;
+    if (sq_vis_layout_init(c, &lay) != SQ_OK || check_bwd_cfg(c) != SQ_OK || batch < 1) return 0;
     BwdBufs b;
     bwd_bufs(*c, dtype, batch, nullptr, &b);
     return b.bytes;
@@ -136,6 +145,7 @@ extern "C" int sq_vis_backward_buckets(const sq_vis_config* c, int dtype, const 
                                        sq_stream_t stream_, const sq_event_t* bucket_events, int n_bucket_events) {
     sq_vis_layout lay;
     if (int e = sq_vis_layout_init(c, &lay)) return e;
+    if (int e = check_bwd_cfg(c)) return e;
     hipStream_t st = (hipStream_t)stream_;
     SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16, "vis_backward: dtype %d", dtype);
     SQ_REQUIRE(params && grad_out && grad_params && fwd_workspace && bwd_workspace, "vis_backward: null pointer");

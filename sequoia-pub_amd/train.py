@@ -50,6 +50,8 @@ def vis_backward(model, grad_out, batch, need_x_grad, bucket_events=None):
     dev = model.flat.device
     grad_out = grad_out.to(dev, torch.float32).contiguous()
     need = getattr(_lib.lib(), model._C_BWS)(ctypes.byref(model.cfg), model.compute_dtype, batch)
+    if need == 0:                # a shape the backward pass refuses (sq_last_error says why): nothing has been launched
+        _lib.check(-1)
     if getattr(model, "_bws", None) is None or model._bws.numel() < need or model._bws.device != dev:
         model._bws = torch.empty(need, dtype=torch.uint8, device=dev)
     gflat = getattr(model, "_gflat", None)

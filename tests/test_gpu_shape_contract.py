@@ -1,0 +1,220 @@
+"""ViS and ViT on the HIP path across the shapes their config checks admit (tests/shape_cases.py), against the oracle in float64.
+
+The kernels behind the two aggregators are chosen by shape (LayerNorm row kernels by D, the LayerNorm(64) + GELU backward by
+nheads, row-bias / group-sum epilogues by N, column sums by B, the attention lane mask by N vs 64, ...); every row of the case
+table names the branch it is there for.  Per row and numeric mode: the forward pass in both forms (inference, and the saving
+forward a training step uses), the loss, every parameter gradient the oracle returns and the gradient w.r.t. the input tokens.
+Tolerances are the project's (shape_cases.TOL): fp32 mode 1e-4 throughout; bf16 mode predictions 3e-2, gradient tensors 8e-2,
+loss 2e-2.  The fp32 run is the one with teeth for indexing and masking mistakes (the logic kernels are one template for both
+element types; tests/test_oracle_shape_floor.py shows such mistakes move a tensor by > 1e-3 at the targeting row).  In bf16
+mode each row also prints the HIP path's error next to the CPU bfloat16 oracle's against the same float64 result (reported,
+not asserted: the HIP path accumulates in fp32 and should not be the worse of the two).
+
+Shapes the backward pass refuses (ViS: nheads not a power of two; ViT: num_clusters > 111) must match in the forward pass, be
+refused by message before anything is launched, and leave the process able to run a valid step that matches the oracle."""
+import numpy as np
+import pytest
+import torch
+
+import shape_cases as sc
+from gpu_util import assert_allclose_rel, rel_err
+
+pytestmark = pytest.mark.gpu
+
+from sequoia_pub_amd import _lib  # noqa: E402
+from sequoia_pub_amd import train as sq_train  # noqa: E402
+from sequoia_pub_amd.vis import ViS  # noqa: E402
+from sequoia_pub_amd.vit import ViT  # noqa: E402
+
+MODES = ["fp32", "bf16"]
+
+
+def _ids(cases):
+    return [c["id"] for c in cases]
+
+
+def _model(case, mode):
+    if case["kind"] == "vis":
+        m = ViS(num_outputs=case["G"], input_dim=case["D"], depth=case["depth"], nheads=case["nheads"], dimensions_f=64,
+                dimensions_s=64, dimensions_c=64, num_clusters=case["N"], device="cuda:0", compute_dtype=mode)
+    else:
+        m = ViT(num_outputs=case["G"], dim=case["D"], depth=case["depth"], heads=case["heads"], mlp_dim=case["mlp_dim"],
+                num_clusters=case["N"], device="cuda:0", compute_dtype=mode)
+    m.load_state_dict(sc.state_dict(case))
+    m.to("cuda:0")
+    return m
+
+
+def _where(got, ref):
+    """Where a tensor is worst: index, the two values, and (for matrices) the three worst rows."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    d = np.abs(got - ref)
+    i = np.unravel_index(int(d.argmax()), d.shape) if d.ndim else ()
+    s = f"shape {d.shape} worst at {tuple(int(v) for v in i)}: got {got[i]:.6g} ref {ref[i]:.6g} (max|ref| {np.abs(ref).max():.3g})"
+    if d.ndim >= 2:
+        rows = d.reshape(-1, d.shape[-1]).max(axis=1)
+        s += f"; worst rows {[int(r) for r in np.argsort(-rows)[:3]]} of {rows.size}"
+    return s
+
+
+def _forward_both_forms(m, case, mode, x, ref_pred):
+    """Inference (no saved activations) and the saving forward of a training step: each against the oracle.  Returns the
+    saving forward's predictions (device tensor)."""
+    tol = sc.TOL[mode]["pred"]
+    n = ref_pred.shape[0]
+    with torch.no_grad():
+        inf = m(x).float().cpu().numpy()
+    sav_dev = m._run_forward(x, save=True)
+    sav = sav_dev.float().cpu().numpy()
+    e_inf, e_sav = rel_err(inf[:n], ref_pred), rel_err(sav[:n], ref_pred)
+    print(f"{case['id']} {mode}: predictions vs float64 oracle: inference {e_inf:.3e}, saving forward {e_sav:.3e}; "
+          f"the two forms differ by {rel_err(inf, sav):.3e}")
+    for name, out, e in (("inference", inf, e_inf), ("saving forward", sav, e_sav)):
+        assert np.isfinite(out).all(), f"{case['id']} {mode} {name}: non-finite predictions"
+        assert e < tol, f"{case['id']} {mode} {name}: predictions {e:.3e} >= {tol}: {_where(out[:n], ref_pred)}"
+        assert_allclose_rel(out[:n], ref_pred, tol, f"{case['id']} {mode} {name} predictions")
+    return sav_dev
+
+
+def _step(case, mode):
+    """Forward (both forms) + MSE + backward of one row against the float64 oracle; prints the per-tensor error table."""
+    _lib.require_gpu()
+    ref = sc.reference(case, torch.float64)
+    tol = sc.TOL[mode]
+    m = _model(case, mode)
+    x, y = sc.inputs(case)
+    x, y = x.cuda(), y.cuda()
+    pred = _forward_both_forms(m, case, mode, x, ref["pred"])
+    loss, gpred = sq_train.mse_loss_grad(m, pred, y)
+    gflat, gx = sq_train.vis_backward(m, gpred, case["B"], True)
+    torch.cuda.synchronize()
+    gv = m.grad_views(gflat)
+    assert set(ref["grads"]) == set(gv), "the oracle and the flat-buffer map name different tensors"
+    got = dict(pred=pred.cpu().numpy(), loss=float(loss), gx=gx.cpu().numpy(), grads={k: v.cpu().numpy() for k, v in gv.items()})
+    t = sc.error_table(got, ref)
+    k, e = sc.worst_grad(t)
+    print(f"SHAPE_CONTRACT {case['id']} {mode} hip: pred {t['pred']:.2e} loss {t['loss']:.2e} gx {t['gx']:.2e} worst-grad {e:.2e} at {k}")
+    for name in sorted(t["grads"], key=lambda n: -t["grads"][n])[:6]:
+        print(f"    {t['grads'][name]:.3e}  {name}")
+    if mode == "bf16":          # reported, not asserted: the CPU bfloat16 oracle's distance from the same float64 result
+        tb = sc.error_table(sc.reference(case, torch.bfloat16), ref)
+        kb, eb = sc.worst_grad(tb)
+        print(f"SHAPE_CONTRACT {case['id']} {mode} cpu-bf16-oracle: pred {tb['pred']:.2e} loss {tb['loss']:.2e} gx {tb['gx']:.2e} worst-grad {eb:.2e} at {kb}")
+        over = {n: (t["grads"][n], tb["grads"][n]) for n in t["grads"] if t["grads"][n] > 2 * tb["grads"][n] and t["grads"][n] > 1e-3}
+        for name, v in (("pred", (t["pred"], tb["pred"])), ("gx", (t["gx"], tb["gx"]))):
+            if v[0] > 2 * v[1]:
+                over[name] = v
+        for n, (a, b) in sorted(over.items(), key=lambda kv: -kv[1][0])[:8]:
+            print(f"    HIP bf16 above twice the CPU bf16 oracle: {n}: {a:.3e} vs {b:.3e}")
+    bad = [f"{n}: {err:.3e} >= {tol['grad']}: {_where(got['grads'][n], ref['grads'][n])}" for n, err in t["grads"].items() if not err < tol["grad"]]
+    if not t["gx"] < tol["grad"]:
+        bad.append(f"d loss / d tokens: {t['gx']:.3e} >= {tol['grad']}: {_where(got['gx'], ref['gx'])}")
+    if not t["loss"] < tol["loss"]:
+        bad.append(f"loss {got['loss']:.8g} vs {ref['loss']:.8g}: {t['loss']:.3e} >= {tol['loss']}")
+    assert not bad, f"{case['id']} {mode}:\n" + "\n".join(bad)
+    assert all(np.isfinite(v).all() for v in got["grads"].values()) and np.isfinite(got["gx"]).all()
+    return t
+
+
+def _refused_backward(case, mode, message):
+    """Forward in both forms matches the oracle; the backward pass refuses the shape by message."""
+    _lib.require_gpu()
+    ref = sc.reference(case, torch.float64)
+    m = _model(case, mode)
+    x, y = sc.inputs(case)
+    x, y = x.cuda(), y.cuda()
+    pred = _forward_both_forms(m, case, mode, x, ref["pred"])
+    _, gpred = sq_train.mse_loss_grad(m, pred, y)
+    with pytest.raises(_lib.SequoiaHipError, match=message):
+        sq_train.vis_backward(m, gpred, case["B"], True)
+    xg = x.clone().requires_grad_(True)                 # and through autograd, the way a training script gets there
+    out = m(xg)
+    with pytest.raises(_lib.SequoiaHipError, match=message):
+        out.backward(gpred)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", [c for c in sc.VIS_CASES if c["backward"] == "ok"], ids=_ids([c for c in sc.VIS_CASES if c["backward"] == "ok"]))
+def test_vis_step_matches_float64_oracle(case, mode):
+    _step(case, mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", [c for c in sc.VIS_CASES if c["backward"] == sc.POW2], ids=_ids([c for c in sc.VIS_CASES if c["backward"] == sc.POW2]))
+def test_vis_nheads_not_a_power_of_two_forward_matches_backward_is_refused_and_the_process_stays_usable(case, mode):
+    _refused_backward(case, mode, sc.POW2)
+    _step(sc.BY_ID[sc.VIS_AFTER_REFUSAL], mode)         # same process: streams, queued gradients, saved-activation note all usable
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", [c for c in sc.VIT_CASES if c["backward"] == "ok"], ids=_ids([c for c in sc.VIT_CASES if c["backward"] == "ok"]))
+def test_vit_step_matches_float64_oracle(case, mode):
+    _step(case, mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", [c for c in sc.VIT_CASES if c["backward"] == sc.LDS], ids=_ids([c for c in sc.VIT_CASES if c["backward"] == sc.LDS]))
+def test_vit_above_111_tokens_forward_matches_backward_is_refused_and_the_process_stays_usable(case, mode):
+    _refused_backward(case, mode, sc.LDS)
+    _step(sc.BY_ID[sc.VIT_AFTER_REFUSAL], mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_vit_constructor_rejects_129_tokens_and_the_process_stays_usable(mode):
+    _lib.require_gpu()
+    with pytest.raises(_lib.SequoiaHipError, match="num_clusters"):
+        ViT(num_outputs=24, dim=192, depth=1, heads=2, mlp_dim=320, num_clusters=129, device="cuda:0", compute_dtype=mode)
+    _step(sc.BY_ID[sc.VIT_AFTER_REFUSAL], mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("cid,rows", sc.GATHER_CASES, ids=[c for c, _ in sc.GATHER_CASES])
+def test_sliding_window_form_matches_the_oracle_on_the_gathered_tokens(cid, rows, mode):
+    """_run_head_inputs (sq_vis_forward_ex / sq_vit_forward_ex: the window batch is gathered inside the first kernel, -1 = a
+    zero row) + apply_head against the oracle on the gathered tokens.  Every index is inside the cache."""
+    _lib.require_gpu()
+    case = sc.BY_ID[cid]
+    ref = sc.gather_reference(case, rows)
+    cache, members = sc.gather_inputs(case, rows)
+    m = _model(case, mode)
+    with torch.no_grad():
+        head_in = m._run_head_inputs(cache.cuda().contiguous(), members.cuda().contiguous())
+        out = m.apply_head(head_in).float().cpu().numpy()
+    e = rel_err(out, ref)
+    print(f"SHAPE_CONTRACT {cid} {mode} gather form: pred {e:.2e} ({int((members < 0).sum())} of {members.numel()} members are zero rows)")
+    tol = sc.TOL[mode]["pred"]
+    assert e < tol, _where(out, ref)
+    assert_allclose_rel(out, ref, tol, f"{cid} {mode} gather form")
+
+
+def test_vis_combiner_in_the_epilogue_off_n100(monkeypatch):
+    """bf16 inference large enough for the combiner to run in the f projection's epilogue (gemm_p8.hip) at N = 50: a row bias
+    per 50 token rows, 5.12 slides per 256-row tile, 70 000 rows = 273 tiles and a ragged one.  Against the two launches
+    (SQ_FWD_NO_FUSED_COMB=1: same bf16 operands, another MFMA shape for the 64-deep sums, bound as in test_gpu_vis.py) and, for
+    the first slides, against the float64 oracle at the bf16 tolerance."""
+    _lib.require_gpu()
+    case = sc.VIS_FUSED_COMBINER
+    ref = sc.reference(case, torch.float64)["pred"]
+    n = ref.shape[0]
+    m = _model(case, "bf16")
+    m.eval()
+    x, _ = sc.inputs(case)
+    xd = x.cuda()
+    with torch.no_grad():
+        monkeypatch.delenv("SQ_FWD_NO_FUSED_COMB", raising=False)
+        fused = m(xd).float().cpu()
+        fused2 = m(xd).float().cpu()
+        monkeypatch.setenv("SQ_FWD_NO_FUSED_COMB", "1")
+        plain = m(xd).float().cpu()
+        monkeypatch.delenv("SQ_FWD_NO_FUSED_COMB")
+    assert torch.isfinite(fused).all() and torch.equal(fused, fused2)
+    d = rel_err(fused.numpy(), plain.numpy())
+    e_f, e_p = rel_err(fused[:n].numpy(), ref), rel_err(plain[:n].numpy(), ref)
+    eb = rel_err(sc.reference(case, torch.bfloat16)["pred"], ref)
+    print(f"SHAPE_CONTRACT {case['id']} bf16 combiner in the epilogue vs two launches: rel diff {d:.2e}, bit-equal outputs "
+          f"{float((fused == plain).float().mean()):.4f}; vs float64 oracle {e_f:.2e} (two launches {e_p:.2e}, cpu-bf16-oracle {eb:.2e})")
+    assert d < 2e-3, _where(fused.numpy(), plain.numpy())
+    tol = sc.TOL["bf16"]["pred"]
+    assert e_f < tol and e_p < tol
+    assert_allclose_rel(fused[:n].numpy(), ref, tol, "combiner in the epilogue, first slides")
