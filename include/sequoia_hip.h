@@ -418,6 +418,41 @@ int sq_he2rna_window_topk_mean(const float* scores, int ld_scores, const float* 
                                const int32_t* ks, int n_ks, float scale, float* out, int n_windows, int n_tiles, int n_genes,
                                sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Pillow-exact resize of uint8 patches (the resize in front of the extractors: `transforms.Resize(224)` on a PIL image,
+ * /root/reference/pre_processing/compute_features_hdf5.py:53-56,125-126 and spatial_vis/visualize.py:226-230, which is
+ * Image.resize(..., BILINEAR); `patch.resize(patch_size)`, pre_processing/patch_gen_hdf5.py:117, Pillow's default BICUBIC).
+ * Pillow's resampler (src/libImaging/Resample.c) is deterministic integer arithmetic on per-axis coefficient tables, and
+ * these entry points restate it bit for bit: two separable passes, horizontal then vertical, through a uint8
+ * intermediate image (the rounding between the passes is part of the result); a pass whose input and output extents are
+ * equal is the identity.  Per axis in -> out: scale = in / out, filterscale = max(scale, 1), support = S * filterscale
+ * (S = 1 bilinear, 2 bicubic), ksize = 2 ceil(support) + 1; output index xx takes the input samples [xmin, xmin + n) around
+ * center = (xx + 0.5) scale with weights f((x + xmin - center + 0.5) / filterscale), normalised to sum 1 in double and
+ * rounded to 22 fractional bits; out = clamp((2^21 + sum k[i] src[xmin + i]) >> 22, 0, 255) in int32.
+ *
+ * The tables are data-independent double arithmetic, so they are made on the HOST, once per
+ * (h_in, w_in, h_out, w_out, filter), and uploaded by the caller (like the *_layout_init entries, no device work):
+ *   sq_resize_plan_bytes : size of the plan in bytes; 0 (and an sq_last_error message) for sizes outside 1..16384 or an
+ *                          unknown filter.
+ *   sq_resize_plan_init  : fills `plan` (host memory, plan_bytes >= sq_resize_plan_bytes) with int32 words:
+ *                            [0..7]  h_in, w_in, h_out, w_out, filter, ksize_h, ksize_v, 0
+ *                            horizontal pass (w_in -> w_out): bounds [w_out][2] = {xmin, n}, then coefficients
+ *                            [w_out][ksize_h] (22 fractional bits, zero beyond n)
+ *                            vertical pass (h_in -> h_out): bounds [h_out][2], then coefficients [h_out][ksize_v]
+ *                          An identity pass has ksize 1: bounds {xx, 1}, coefficient 2^22.
+ *   sq_resize_u8         : src_u8 uint8 NHWC [n, h_in, w_in, 3] -> dst_u8 uint8 NHWC [n, h_out, w_out, 3] with the uploaded
+ *                          plan of exactly these sizes and filter (device memory, 4-byte aligned).  One launch; the
+ *                          intermediate image lives in LDS.  Sizes whose narrowest band of rows does not fit the 160 KiB
+ *                          of LDS (very wide images under a large reduction) are refused with the byte count.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_RESIZE_BILINEAR 0 /* PIL.Image.BILINEAR */
+#define SQ_RESIZE_BICUBIC 1  /* PIL.Image.BICUBIC, a = -0.5 */
+#define SQ_RESIZE_MAX_DIM 16384
+size_t sq_resize_plan_bytes(int h_in, int w_in, int h_out, int w_out, int filter);
+int sq_resize_plan_init(int h_in, int w_in, int h_out, int w_out, int filter, int32_t* plan, size_t plan_bytes);
+int sq_resize_u8(const uint8_t* src_u8, int n, int h_in, int w_in, uint8_t* dst_u8, int h_out, int w_out, int filter,
+                 const int32_t* plan_dev, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

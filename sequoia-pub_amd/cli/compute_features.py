@@ -37,6 +37,9 @@ def main(argv=None):
                              'bf16 = throughput mode (not label-exact); uni: fp32, bf16 or f16x3 (split-fp16, the fast parity mode)')
     parser.add_argument('--weights', type=str, default=None,
                         help='resnet: torchvision resnet50 state_dict (.pth), default model_zoo URL; uni: path of pytorch_model.bin (required)')
+    parser.add_argument('--resize', default='float', choices=['float', 'pil'],
+                        help='uni, patches that are not 224 px: float = antialiased float interpolation (uni.resize_u8, within one grey level of PIL); '
+                             'pil = bit for bit the reference\'s PIL BILINEAR resize (imgproc.resize_u8_pil)')
     args = parser.parse_args(argv)
     seed_everything(args.seed)
     rank, world, device = init_distributed()
@@ -83,8 +86,12 @@ def main(argv=None):
                 patches = np.stack([np.asarray(f_read[key][:]) for key in keys])
             patches = torch.from_numpy(patches)
             if args.feat_type == 'uni' and patches.shape[1] != 224:              # transforms.Resize(224), :54
-                from ..uni import resize_u8
-                patches = resize_u8(patches.to(device), 224)
+                if args.resize == 'pil':
+                    from ..imgproc import resize_u8_pil
+                    patches = resize_u8_pil(patches.to(device), 224, "bilinear")
+                else:
+                    from ..uni import resize_u8
+                    patches = resize_u8(patches.to(device), 224)
             feats = model.extract_patches_u8(patches, sub_batch=1000).cpu().numpy()      # clamped per mode / patch size by the extractor
             f_write = store.File(os.path.join(path_h5, WSI + '.h5'), "w")
             f_write.create_dataset(f"{args.feat_type}_features", data=feats)

@@ -70,15 +70,21 @@ def read_tiles(slide, df, patch_size_resized, lo=0, hi=None):
     return torch.from_numpy(tiles)
 
 
-def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chunk=None, shard=None):
+def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chunk=None, shard=None, resize="float"):
     """Feature cache [n_tiles, D] on the device: tiles go through in chunks -- read, upload, resize ON THE DEVICE
-    (antialiased bilinear, uni.resize_u8) when the read size differs from the extractor's input, embed -- so only the
+    (antialiased bilinear: ``resize="float"`` uni.resize_u8, ``resize="pil"`` imgproc.resize_u8_pil, bit for bit the PIL
+    BILINEAR resize of visualize.py:226-230) when the read size differs from the extractor's input, embed -- so only the
     features stay resident (a 40x slide with 50 000 valid tiles of 512 x 512 would otherwise need ~40 GB of host
     uint8 plus the fp32 resize copies).  With ``shard=(rank, world[, group])`` the chunks are dealt round-robin over the
     ranks (chunk c to rank c % world: the same launches the one-rank run makes for those tiles) and the cache is
     all-gathered once (SURVEY 8e "Config 5": n_tiles x D fp32), so every rank ends with the complete, identical cache."""
     from ..spatial import _shard_info, gathered_row_of_window
-    from ..uni import resize_u8
+    if resize == "pil":
+        from ..imgproc import resize_u8_pil as resize_u8
+    elif resize == "float":
+        from ..uni import resize_u8
+    else:
+        raise ValueError(f"resize={resize!r}: 'float' or 'pil'")
     rank, world, group = _shard_info(shard)
     chunk = int(chunk or TILE_CHUNK)
     D = 2048 if hasattr(feat_model, 'conv1') else 1024
@@ -140,6 +146,9 @@ def main(argv=None):
     p.add_argument('--tile_chunk', type=int, default=TILE_CHUNK, help='tiles per read -> upload -> embed round (and the unit dealt over the ranks under torchrun)')
     p.add_argument('--compute_dtype', default='bf16', choices=['fp32', 'bf16', 'f16x3', 'bf16x3'],
                    help='f16x3 / bf16x3: the extractor on split planes (fp32-class features; uni: f16x3 only); the aggregator then runs in fp32')
+    p.add_argument('--resize', default='float', choices=['float', 'pil'],
+                   help='tiles read at another size than the extractor takes: float = antialiased float interpolation (uni.resize_u8, within one '
+                        'grey level of PIL); pil = bit for bit PIL\'s BILINEAR resize (imgproc.resize_u8_pil)')
     args = p.parse_args(argv)
     assert args.feat_type in ['resnet', 'uni'] and args.model_type in ['vit', 'vis', 'he2rna']
     # under torchrun: ONE slide over the ranks -- tile chunks for the feature cache, window batches and tile chunks for the
@@ -179,14 +188,14 @@ def main(argv=None):
         if args.extractor_weights:
             feat_model.load_state_dict(torch.load(args.extractor_weights, map_location='cpu'))
         feat_model = feat_model.to(device).eval()
-        tile_features = embed_tiles(slide, df, patch_size_resized, 256, feat_model, device, chunk=args.tile_chunk, shard=shard)
+        tile_features = embed_tiles(slide, df, patch_size_resized, 256, feat_model, device, chunk=args.tile_chunk, shard=shard, resize=args.resize)
     else:
         from ..uni import create_model
         feat_model = create_model("vit_large_patch16_224", img_size=224, patch_size=16, init_values=1e-5, num_classes=0,
                                   dynamic_img_size=True, compute_dtype=args.compute_dtype)
         feat_model.load_state_dict(torch.load(args.extractor_weights or "./uni_ckpt/pytorch_model.bin", map_location='cpu'), strict=True)
         feat_model = feat_model.to(device).eval()
-        tile_features = embed_tiles(slide, df, patch_size_resized, 224, feat_model, device, chunk=args.tile_chunk, shard=shard)
+        tile_features = embed_tiles(slide, df, patch_size_resized, 224, feat_model, device, chunk=args.tile_chunk, shard=shard, resize=args.resize)
 
     # ---- fold ensemble (visualize.py:248-300)
     res_df = df.copy(deep=True)

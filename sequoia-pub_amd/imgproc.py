@@ -1,0 +1,82 @@
+"""Image preprocessing on the device.  ``resize_u8_pil``: the resize the reference runs in front of its extractors --
+``transforms.Resize(224)`` on a PIL image (/root/reference/pre_processing/compute_features_hdf5.py:53-56,125-126 and
+spatial_vis/visualize.py:226-230: ``Image.resize(..., BILINEAR)``) and ``patch.resize(patch_size)``
+(pre_processing/patch_gen_hdf5.py:117: BICUBIC) -- for a batch of uint8 patches, bit for bit what Pillow computes
+(``sq_resize_u8``, csrc/resize.hip).
+
+The only host arithmetic is Pillow's data-independent coefficient tables (double precision, ``sq_resize_plan_init``),
+made and uploaded once per shape."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+SQ_RESIZE_BILINEAR = 0
+SQ_RESIZE_BICUBIC = 1
+FILTERS = {"bilinear": SQ_RESIZE_BILINEAR, "bicubic": SQ_RESIZE_BICUBIC, SQ_RESIZE_BILINEAR: SQ_RESIZE_BILINEAR,
+           SQ_RESIZE_BICUBIC: SQ_RESIZE_BICUBIC}
+
+vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+_lib.register_signature("sq_resize_plan_bytes", sz, [i32, i32, i32, i32, i32])
+_lib.register_signature("sq_resize_plan_init", i32, [i32, i32, i32, i32, i32, vp, sz])
+_lib.register_signature("sq_resize_u8", i32, [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp])
+
+
+def resize_plan(h_in, w_in, h_out, w_out, resample="bilinear"):
+    """The host plan of sq_resize_plan_init as an int32 array (layout: include/sequoia_hip.h).  Needs no GPU."""
+    L = _lib.lib()
+    flt = _filter_id(resample)
+    need = L.sq_resize_plan_bytes(h_in, w_in, h_out, w_out, flt)
+    if need == 0:
+        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    plan = np.empty(need // 4, dtype=np.int32)
+    _lib.check(L.sq_resize_plan_init(h_in, w_in, h_out, w_out, flt, plan.ctypes.data_as(vp), need))
+    return plan
+
+
+def _filter_id(resample):
+    try:
+        return FILTERS[resample]
+    except (KeyError, TypeError):
+        raise ValueError(f"resample={resample!r}: 'bilinear' or 'bicubic'") from None
+
+
+_plan_cache = {}
+
+
+def _device_plan(h_in, w_in, h_out, w_out, flt, dev):
+    """The tables depend only on the shapes and the filter: the double arithmetic and the (synchronous, pageable) upload are
+    paid once per shape, as kmeans._device_draws does for the seeding draws."""
+    key = (int(h_in), int(w_in), int(h_out), int(w_out), int(flt), str(dev))
+    hit = _plan_cache.get(key)
+    if hit is None:
+        plan = resize_plan(h_in, w_in, h_out, w_out, flt)
+        if len(_plan_cache) >= 64:
+            _plan_cache.clear()
+        hit = _plan_cache[key] = torch.from_numpy(plan).to(dev)      # blocking copy: visible to every stream
+    return hit
+
+
+def resize_u8_pil(patches_u8, size, resample="bilinear"):
+    """uint8 [n, H, W, 3] CUDA tensor -> uint8 [n, h, w, 3], every byte equal to
+    ``PIL.Image.fromarray(patch).resize((w, h), resample)``.  ``size``: an int (a square output, what ``Resize(224)`` gives a
+    square patch) or ``(h, w)``; ``resample``: "bilinear" or "bicubic".  Asynchronous on the current stream; no CPU fallback."""
+    _lib.require_gpu()
+    if not (torch.is_tensor(patches_u8) and patches_u8.is_cuda):
+        raise _lib.SequoiaHipError("resize_u8_pil needs a CUDA tensor (no CPU fallback)")
+    if patches_u8.dtype != torch.uint8 or patches_u8.dim() != 4 or patches_u8.shape[3] != 3:
+        raise ValueError(f"resize_u8_pil takes uint8 [n, H, W, 3], got {patches_u8.dtype} {tuple(patches_u8.shape)}")
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    flt = _filter_id(resample)
+    x = patches_u8.contiguous()
+    n, H, W, _ = x.shape
+    dev = x.device
+    plan = _device_plan(H, W, h, w, flt, dev)          # refuses a bad size with the library's message before anything is allocated
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().sq_resize_u8(_lib.ptr(x), n, H, W, _lib.ptr(out), h, w, flt, _lib.ptr(plan), _lib.stream_ptr(dev)))
+    return out
