@@ -296,6 +296,22 @@ int sq_resnet50_extract(int dtype, const void* weights, const float* bias, const
 int sq_resnet50_extract_checked(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
                                 const float* patches_f32_nchw, int n_patches, int patch_size, float* features,
                                 void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream);
+/* Rectangular and odd-sized patches: the same network on patches_u8 [n, height, width, 3] or patches_f32_nchw [n, 3, height, width].
+ * Call sites: spatial_vis/visualize.py:212-216 feeds the extractor transforms.Resize((256, 265)) tiles (height 256, width 265)
+ * through :62-66 into src/resnet.py:155-170, which is plain PyTorch and takes any height and width.
+ * Stage sizes per axis: conv1 ceil(s/2), max-pool ceil(s/4), layers 2-4 ceil of half again, final map ceil(s/32).
+ * Admitted: SQ_RESNET50_HW_MIN <= height, width <= SQ_RESNET50_HW_MAX, each independently -- exactly the sizes whose final map is
+ * 7..13 per axis, where nn.AvgPool2d(7) (src/resnet.py:110,166-168) yields one (top-left) 7 x 7 window and hence [n, 2048].  Above,
+ * the reference returns more than 2048 features; below, it fails.  Outside the range sq_resnet50_workspace_bytes_hw returns 0 and
+ * sq_resnet50_extract_hw returns an error (sq_last_error says why) without launching anything.
+ * Same weight layout, same four dtypes, same nonfinite_flag semantics as sq_resnet50_extract_checked; for height == width, a
+ * multiple of 32 in [224, 416], workspace size and features are bit-identical to that entry's. */
+#define SQ_RESNET50_HW_MIN 193
+#define SQ_RESNET50_HW_MAX 416
+size_t sq_resnet50_workspace_bytes_hw(int dtype, int n_patches, int height, int width);
+int sq_resnet50_extract_hw(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
+                           const float* patches_f32_nchw, int n_patches, int height, int width, float* features,
+                           void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream);
 
 /* dst_bf16[i] = bf16(src[i]) -- refresh of the bf16 parameter shadow after an optimizer step */
 int sq_cast_f32_to_bf16(const float* src, void* dst_bf16, size_t n, sq_stream_t stream);

@@ -7,8 +7,10 @@ What differs in HOW: every valid tile is embedded ONCE into a feature cache and 
 mean per window, vote on the window predictions -- and under torchrun the slide is dealt over the ranks for each of them.  The reference hard-codes its data locations per project; here they are the
 defaults of ``--slide_path`` / ``--mask_path`` / ``--checkpoint`` and can be overridden.  Slides are opened with
 openslide when it is installed, or given as an ``.npy`` RGB array (``patchgen.ArraySlide``, 20x).  ResNet tiles are
-resized to 256 x 256 (the reference's ``Resize((256, 265))`` is not a size the convolution engine takes); UNI tiles to
-224 as in the reference."""
+resized to 256 x 256 by default; ``--resnet_input reference`` gives the extractor what the reference's
+``transforms.Resize((256, 265))`` gives it (spatial_vis/visualize.py:212-216): EVERY tile, 256 x 256 ones included, resized
+to height 256, width 265 with PIL's BILINEAR filter, byte for byte (``imgproc.resize_u8_pil``; ``--resize`` does not apply
+to it).  UNI tiles go to 224 as in the reference."""
 import argparse
 import os
 import pickle
@@ -77,7 +79,9 @@ def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chu
     features stay resident (a 40x slide with 50 000 valid tiles of 512 x 512 would otherwise need ~40 GB of host
     uint8 plus the fp32 resize copies).  With ``shard=(rank, world[, group])`` the chunks are dealt round-robin over the
     ranks (chunk c to rank c % world: the same launches the one-rank run makes for those tiles) and the cache is
-    all-gathered once (SURVEY 8e "Config 5": n_tiles x D fp32), so every rank ends with the complete, identical cache."""
+    all-gathered once (SURVEY 8e "Config 5": n_tiles x D fp32), so every rank ends with the complete, identical cache.
+    ``out_size``: an int (square input) or ``(h, w)``, e.g. (256, 265) for the ResNet extractor as visualize.py:212-216
+    feeds it; a rectangular size needs ``resize="pil"`` (the float resize is square only)."""
     from ..spatial import _shard_info, gathered_row_of_window
     if resize == "pil":
         from ..imgproc import resize_u8_pil as resize_u8
@@ -85,6 +89,12 @@ def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chu
         from ..uni import resize_u8
     else:
         raise ValueError(f"resize={resize!r}: 'float' or 'pil'")
+    if not isinstance(out_size, int):
+        out_size = (int(out_size[0]), int(out_size[1]))
+        if out_size[0] == out_size[1]:
+            out_size = out_size[0]
+        elif resize != "pil":
+            raise ValueError(f"out_size={out_size}: a rectangular extractor input needs resize='pil'")
     rank, world, group = _shard_info(shard)
     chunk = int(chunk or TILE_CHUNK)
     D = 2048 if hasattr(feat_model, 'conv1') else 1024
@@ -149,6 +159,9 @@ def main(argv=None):
     p.add_argument('--resize', default='float', choices=['float', 'pil'],
                    help='tiles read at another size than the extractor takes: float = antialiased float interpolation (uni.resize_u8, within one '
                         'grey level of PIL); pil = bit for bit PIL\'s BILINEAR resize (imgproc.resize_u8_pil)')
+    p.add_argument('--resnet_input', default='256x256', choices=['256x256', 'reference'],
+                   help='--feat_type resnet: 256x256 = square tiles (default); reference = every tile resized to height 256, width 265 as '
+                        'the reference\'s Resize((256, 265)) does, byte for byte PIL\'s BILINEAR resize whatever --resize says')
     args = p.parse_args(argv)
     assert args.feat_type in ['resnet', 'uni'] and args.model_type in ['vit', 'vis', 'he2rna']
     # under torchrun: ONE slide over the ranks -- tile chunks for the feature cache, window batches and tile chunks for the
@@ -188,7 +201,10 @@ def main(argv=None):
         if args.extractor_weights:
             feat_model.load_state_dict(torch.load(args.extractor_weights, map_location='cpu'))
         feat_model = feat_model.to(device).eval()
-        tile_features = embed_tiles(slide, df, patch_size_resized, 256, feat_model, device, chunk=args.tile_chunk, shard=shard, resize=args.resize)
+        if args.resnet_input == 'reference':              # spatial_vis/visualize.py:212-216: Resize((256, 265)) on the PIL tile
+            tile_features = embed_tiles(slide, df, patch_size_resized, (256, 265), feat_model, device, chunk=args.tile_chunk, shard=shard, resize='pil')
+        else:
+            tile_features = embed_tiles(slide, df, patch_size_resized, 256, feat_model, device, chunk=args.tile_chunk, shard=shard, resize=args.resize)
     else:
         from ..uni import create_model
         feat_model = create_model("vit_large_patch16_224", img_size=224, patch_size=16, init_values=1e-5, num_classes=0,

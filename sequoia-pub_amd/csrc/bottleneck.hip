@@ -433,7 +433,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
 }  // namespace
 
-// t1 [P, 64], res / y [P, 256], t1n [P, cn] (cn = 64 or 128), all bf16; P = n * H * W pixels of W-wide square maps.
+// t1 [P, 64], res / y [P, 256], t1n [P, cn] (cn = 64 or 128), all bf16; P = n * H * W pixels of H x W maps.
 // Downsample form: res == nullptr, the identity is xin [P, 64] . wd^T + bd.
 // w*_bytes: bytes from each weight pointer to the end of its allocation (descriptor extent; the tail chunk of the
 // 3x3 weights over-reads 128 bytes past row 63, which must stay inside the packed weight buffer).
@@ -443,7 +443,8 @@ int sq_launch_bottleneck_tail_c64(const bf16_t* t1, const bf16_t* res, bf16_t* y
                                   const bf16_t* xin, const bf16_t* wd, size_t wd_bytes, const float* bd,
                                   int n_img, int H, int W, hipStream_t stream) {
     SQ_REQUIRE(cn == 64 || cn == 128, "bottleneck tail: next width %d (64 or 128)", cn);
-    SQ_REQUIRE(H == W && W >= 3 && (128 + 2 * W + 2) * 128 <= R0_BYTES, "bottleneck tail: map %d x %d does not fit the halo buffer", H, W);
+    // H x W maps: the halo is 128 + 2 W + 2 flat rows whatever H is; the kernel's tap masks take rows and columns apart (HW / W rows)
+    SQ_REQUIRE(H >= 1 && W >= 3 && (128 + 2 * W + 2) * 128 <= R0_BYTES, "bottleneck tail: map %d x %d does not fit the halo buffer", H, W);
     const long long P = (long long)n_img * H * W;
     SQ_REQUIRE(P > 0 && P * 512 < (1ll << 31), "bottleneck tail: %lld pixels exceed the 2 GiB descriptor limit", P);
     SQ_REQUIRE(w2_bytes >= 64 * 576 * 2 + 128 && w3_bytes >= 256 * 64 * 2 && w1n_bytes >= (size_t)cn * 256 * 2, "bottleneck tail: weight extents");

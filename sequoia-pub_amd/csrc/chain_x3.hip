@@ -91,7 +91,7 @@ struct ChainX3Args {
     const uint16_t* w2;                          // [64, 576], k = (kh*3 + kw)*64 + cin; lo plane plW behind
     const float* b2; const float* cs2;
     uint32_t w2_bytes;
-    int W, HW;                                   // map width and pixels per image (square maps)
+    int W, HW;                                   // map width and pixels per image (HW / W rows)
     int dbg;                                     // ablation switches (tools/chain_probe.py): 1 no stores, 2 no identity reads, 4 no 3x3, 8 no second product
     int xcd_walk;                                // tile walk (kernel comment)
 };
@@ -561,8 +561,8 @@ int sq_launch_chain_x3_c64(int f16, const uint16_t* t2, long long plT2, const ui
     SQ_REQUIRE(P > 0 && P * N1 * 2 < (1ll << 31), "chain_x3: %lld pixels exceed the 2 GiB descriptor limit", P);
     const bool tail = t1 != nullptr;
     SQ_REQUIRE((t2 || tail) && y && t1n && w3 && w1n && b3 && b1n && frag && w3_bytes >= (size_t)N1 * K1 * 2, "chain_x3: null pointer / weight extent");
-    SQ_REQUIRE(!tail || (w2 && b2 && w2_bytes >= (size_t)64 * 576 * 2 && W >= 3 && W <= 70 && HW == W * W && P % HW == 0),
-               "chain_x3: tail form needs the 3x3 weights and square maps up to 70 wide (W=%d)", W);
+    SQ_REQUIRE(!tail || (w2 && b2 && w2_bytes >= (size_t)64 * 576 * 2 && W >= 3 && W <= 70 && HW >= W && HW % W == 0 && P % HW == 0),
+               "chain_x3: tail form needs the 3x3 weights and maps up to 70 wide (W=%d, HW=%d)", W, HW);
     const bool wide = tail && W > 62;             // 63 .. 70: 208-row planes, three-stage weight ring
     const bool ds = res == nullptr;
     SQ_REQUIRE(!ds || (xin && wd && bd && wd_bytes >= (size_t)N1 * K1 * 2), "chain_x3: neither an identity tensor nor a downsample branch");

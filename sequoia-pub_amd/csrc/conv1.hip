@@ -34,12 +34,12 @@ constexpr int LUT_BYTES = 3 * 256 * 2;
 constexpr int W_LD = 152;                // packed conv1 weight row: k = (ky*7 + kx)*3 + c, zero padded (resnet.hip)
 
 struct Conv1Args {
-    const uint8_t* u8;          // [n, S, S, 3] or null
-    const float* f32;           // [n, 3, S, S] normalised, or null
+    const uint8_t* u8;          // [n, H, W, 3] or null
+    const float* f32;           // [n, 3, H, W] normalised, or null
     const bf16_t* w;            // [64, 152]
     const float* bias;          // [64]
-    bf16_t* out;                // [n, S/4, S/4, 64]
-    int n, S, tiles_per_side, tiles;
+    bf16_t* out;                // [n, PH, PW, 64]
+    int n, H, W, tiles_y, tiles_x, tiles;     // pooled 8 x 8 tiles per image: tiles_y x tiles_x, the last row / column may be partial
 };
 
 __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
@@ -87,8 +87,10 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
         a_off[i] = ((2 * oy) * RW + 2 * ox + 2 * g) * 8;
     }
 
-    const int S = p.S, PH = S / 4;
-    const int tps2 = p.tiles_per_side * p.tiles_per_side;
+    const int H = p.H, W = p.W;
+    const int OHc = (H + 1) / 2, OWc = (W + 1) / 2;            // conv1's map
+    const int PH = (OHc + 1) / 2, PW = (OWc + 1) / 2;          // pooled map
+    const int tps2 = p.tiles_y * p.tiles_x;
     constexpr int NPX = (RH * RW + 255) / 256;     // staged pixels per thread (7)
 
     // uint8 source: the NEXT tile's pixels are fetched into registers while this tile is on the MFMA
@@ -99,17 +101,17 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
     uint32_t pre_ok = 0;
     auto prefetch = [&](int tile) {
         const int img = tile / tps2, tt = tile - img * tps2;
-        const int ty = tt / p.tiles_per_side, tx = tt - ty * p.tiles_per_side;
+        const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
         const int iy0 = 4 * TP * ty - 5, ix0 = 4 * TP * tx - 5;
-        const uint8_t* base = p.u8 + (size_t)img * S * S * 3;
+        const uint8_t* base = p.u8 + (size_t)img * H * W * 3;
         pre_ok = 0;
 #pragma unroll
         for (int j = 0; j < NPX; ++j) {
             const int idx = tid + j * 256;
             const int r = idx / RW, q = idx - r * RW;
             const int iy = iy0 + r, ix = ix0 + q;
-            const bool ok = idx < RH * RW && (unsigned)iy < (unsigned)S && (unsigned)ix < (unsigned)S;
-            const uint8_t* px = base + ((uint32_t)(ok ? iy : 0) * S + (ok ? ix : 0)) * 3;
+            const bool ok = idx < RH * RW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+            const uint8_t* px = base + ((uint32_t)(ok ? iy : 0) * W + (ok ? ix : 0)) * 3;
             uint16_t v01;
             __builtin_memcpy(&v01, px, 2);
             pre01[j] = v01; pre2[j] = px[2];
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
     for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
         const int img = tile / tps2;
         const int tt = tile - img * tps2;
-        const int ty = tt / p.tiles_per_side, tx = tt - ty * p.tiles_per_side;
+        const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
 
         // ---- stage the normalised input window
         if (p.u8) {
@@ -145,10 +147,10 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
                 const int r = idx / RW, q = idx - r * RW;
                 const int iy = iy0 + r, ix = ix0 + q;
                 uint32_t lo = 0, hi = 0;
-                if ((unsigned)iy < (unsigned)S && (unsigned)ix < (unsigned)S) {
-                    const float* px = p.f32 + ((size_t)img * 3 * S + iy) * S + ix;
-                    lo = pack_bf16x2(px[0], px[(size_t)S * S]);
-                    hi = (uint32_t)f32_to_bf16(px[2 * (size_t)S * S]);
+                if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const float* px = p.f32 + ((size_t)img * 3 * H + iy) * W + ix;
+                    lo = pack_bf16x2(px[0], px[(size_t)H * W]);
+                    hi = (uint32_t)f32_to_bf16(px[2 * (size_t)H * W]);
                 }
                 *reinterpret_cast<u32x2*>(s_in + idx * 8) = u32x2{lo, hi};
             }
@@ -191,8 +193,11 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
 
         // ---- 3 x 3 stride-2 max over the conv tile: thread = (pooled pixel, 16 channels).  All values are >= 0, so
         // bf16 order == unsigned 16-bit order (packed integer max) and 0 stands for the pool's -inf padding; taps
-        // outside the image (first conv row / column of the first tile row / column) are redirected to their valid
-        // neighbour, which cannot change a maximum.
+        // outside the conv map are redirected to their valid neighbour, which cannot change a maximum: conv row / column -1
+        // (first tile row / column) and, at odd conv extents, conv row OHc / column OWc.  The tile HAS a value there,
+        // computed from zero-padded pixels, and PyTorch's -inf padding must keep it out of the maximum (treating it as 0
+        // would be equivalent post-ReLU, every window holding an in-range value >= 0; the redirect needs no such argument).
+        // Pooled pixels past PH / PW (partial last tiles) are computed and not stored.
         {
             const int pp = tid >> 2, cg = tid & 3;
             const int py = pp >> 3, px = pp & 7;
@@ -204,13 +209,17 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
                     int cy = 2 * py + dy, cx = 2 * px + dx;                        // conv pixel inside the tile
                     if (ty == 0 && cy == 0) cy = 1;
                     if (tx == 0 && cx == 0) cx = 1;
+                    if (2 * TP * ty + cy - 1 == OHc) cy -= 1;                      // tile pixel (cy, cx) = conv pixel (2 TP ty + cy - 1, 2 TP tx + cx - 1)
+                    if (2 * TP * tx + cx - 1 == OWc) cx -= 1;
                     const char* src = s_out + (cy * TC + cx) * CROW + cg * 32;
                     b0 = __builtin_elementwise_max(b0, *reinterpret_cast<const u16x8*>(src));
                     b1 = __builtin_elementwise_max(b1, *reinterpret_cast<const u16x8*>(src + 16));
                 }
-            bf16_t* dst = p.out + (((size_t)img * PH + TP * ty + py) * PH + TP * tx + px) * 64 + cg * 16;
-            *reinterpret_cast<u16x8*>(dst) = b0;
-            *reinterpret_cast<u16x8*>(dst + 8) = b1;
+            if (TP * ty + py < PH && TP * tx + px < PW) {                          // partial last tile row / column
+                bf16_t* dst = p.out + (((size_t)img * PH + TP * ty + py) * PW + TP * tx + px) * 64 + cg * 16;
+                *reinterpret_cast<u16x8*>(dst) = b0;
+                *reinterpret_cast<u16x8*>(dst + 8) = b1;
+            }
         }
         // the next tile's staging only touches s_in (all MFMA reads are behind the barrier above); its conv
         // tile is written after the next barrier, by which time every thread has finished pooling this one
@@ -219,14 +228,15 @@ __global__ __launch_bounds__(256, 2) void conv1_pool_kernel(const Conv1Args p) {
 
 }  // namespace
 
-// out [n, S/4, S/4, 64] bf16 = maxpool(relu(conv1(normalise(patches)) + bias)); S a multiple of 32
+// out [n, PH, PW, 64] bf16 = maxpool(relu(conv1(normalise(patches)) + bias)); PH = ceil(H/4), PW = ceil(W/4), any H, W
 int sq_launch_conv1_pool_bf16(const uint8_t* u8, const float* f32_nchw, const bf16_t* w152, const float* bias, bf16_t* out,
-                              int n, int S, hipStream_t stream) {
-    SQ_REQUIRE(S % (4 * TP) == 0 && n >= 1, "conv1_pool: patch size %d must be a multiple of %d", S, 4 * TP);
+                              int n, int H, int W, hipStream_t stream) {
+    SQ_REQUIRE(H >= 7 && W >= 7 && n >= 1, "conv1_pool: n=%d patches of %d x %d", n, H, W);
     Conv1Args a;
-    a.u8 = u8; a.f32 = f32_nchw; a.w = w152; a.bias = bias; a.out = out; a.n = n; a.S = S;
-    a.tiles_per_side = S / (4 * TP);
-    const long long tiles = (long long)n * a.tiles_per_side * a.tiles_per_side;
+    a.u8 = u8; a.f32 = f32_nchw; a.w = w152; a.bias = bias; a.out = out; a.n = n; a.H = H; a.W = W;
+    const int PH = ((H + 1) / 2 + 1) / 2, PW = ((W + 1) / 2 + 1) / 2;      // pooled map: ceil(ceil(s/2)/2) per axis
+    a.tiles_y = (PH + TP - 1) / TP; a.tiles_x = (PW + TP - 1) / TP;
+    const long long tiles = (long long)n * a.tiles_y * a.tiles_x;
     SQ_REQUIRE(tiles < (1ll << 31), "conv1_pool: too many tiles");
     a.tiles = (int)tiles;
     const size_t lds = IN_BYTES + COUT_BYTES + LUT_BYTES;
@@ -238,8 +248,8 @@ int sq_launch_conv1_pool_bf16(const uint8_t* u8, const float* f32_nchw, const bf
     const int grid = (int)(tiles < 512 ? tiles : 512);      // persistent: 2 blocks per CU keep their weights in registers
     int prof = -1;
     if (sq_prof_on()) {
-        const double px_out = (double)n * (S / 2) * (S / 2);
-        prof = sq_prof_begin("conv1_pool_bf16", 2.0 * px_out * 64 * 147, (double)n * S * S * 3 + (double)n * (S / 4) * (S / 4) * 64 * 2, stream);
+        const double px_out = (double)n * ((H + 1) / 2) * ((W + 1) / 2);
+        prof = sq_prof_begin("conv1_pool_bf16", 2.0 * px_out * 64 * 147, (double)n * H * W * 3 + (double)n * PH * PW * 64 * 2, stream);
     }
     hipLaunchKernelGGL(conv1_pool_kernel, dim3(grid), dim3(256), lds, stream, a);
     SQ_LAUNCH_CHECK();

@@ -36,21 +36,21 @@ constexpr int RW_BYTES = 16384;           // fragment-ordered weights of the fus
 constexpr int LDS_BYTES = 2 * IN_BYTES + COUT_BYTES + LUT_BYTES + RW_BYTES;
 
 struct Conv1X3Args {
-    const uint8_t* u8;          // [n, S, S, 3] or null
-    const float* f32;           // [n, 3, S, S] normalised, or null
+    const uint8_t* u8;          // [n, H, W, 3] or null
+    const float* f32;           // [n, 3, H, W] normalised, or null
     const uint16_t* w;          // hi plane [64, 152]; lo plane w_plane elements behind
     long long w_plane;
     const float* bias;          // [64]
     const float* colscale;      // [64] or null
-    uint16_t* out;              // hi plane [n, S/4, S/4, 64]; lo plane out_plane elements behind
+    uint16_t* out;              // hi plane [n, PH, PW, 64]; lo plane out_plane elements behind
     long long out_plane;
-    int n, S, tiles_per_side, tiles;
+    int n, H, W, tiles_y, tiles_x, tiles;     // pooled 8 x 8 tiles per image: tiles_y x tiles_x, the last row / column may be partial
     // optional: the first bottleneck's reduce 1x1 (64 -> 64, src/resnet.py:75-77) on the pooled tile before it leaves the CU:
     // t1 = relu(x . w1^T * cs1 + b1) as planes beside x -- the launch that would read x back (0.8 GB per 1000 patches) is gone
     const uint16_t* w1;         // hi plane [64, 64] (row-major, or K-tile-major when w1_tiled); lo plane w_plane elements behind
     int w1_tiled;
     const float* b1; const float* cs1;
-    uint16_t* t1;               // hi plane [n, S/4, S/4, 64]; lo plane out_plane elements behind; null: not fused
+    uint16_t* t1;               // hi plane [n, PH, PW, 64]; lo plane out_plane elements behind; null: not fused
 };
 
 template <bool F16>
@@ -125,8 +125,10 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
         a_off[i] = ((2 * oy) * RW + 2 * ox + 2 * g) * 8;
     }
 
-    const int S = p.S, PH = S / 4;
-    const int tps2 = p.tiles_per_side * p.tiles_per_side;
+    const int H = p.H, W = p.W;
+    const int OHc = (H + 1) / 2, OWc = (W + 1) / 2;            // conv1's map
+    const int PH = (OHc + 1) / 2, PW = (OWc + 1) / 2;          // pooled map
+    const int tps2 = p.tiles_y * p.tiles_x;
     constexpr int NPX = (RH * RW + NT - 1) / NT;   // staged pixels per thread (4)
 
     // uint8 source: the NEXT tile's pixels are fetched into registers while this tile is on the MFMA.  Raw load results
@@ -135,17 +137,17 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
     uint32_t pre_ok = 0;
     auto prefetch = [&](int tile) {
         const int img = tile / tps2, tt = tile - img * tps2;
-        const int ty = tt / p.tiles_per_side, tx = tt - ty * p.tiles_per_side;
+        const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
         const int iy0 = 4 * TP * ty - 5, ix0 = 4 * TP * tx - 5;
-        const uint8_t* base = p.u8 + (size_t)img * S * S * 3;
+        const uint8_t* base = p.u8 + (size_t)img * H * W * 3;
         pre_ok = 0;
 #pragma unroll
         for (int j = 0; j < NPX; ++j) {
             const int idx = tid + j * NT;
             const int r = idx / RW, q = idx - r * RW;
             const int iy = iy0 + r, ix = ix0 + q;
-            const bool ok = idx < RH * RW && (unsigned)iy < (unsigned)S && (unsigned)ix < (unsigned)S;
-            const uint8_t* px = base + ((uint32_t)(ok ? iy : 0) * S + (ok ? ix : 0)) * 3;
+            const bool ok = idx < RH * RW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+            const uint8_t* px = base + ((uint32_t)(ok ? iy : 0) * W + (ok ? ix : 0)) * 3;
             uint16_t v01;
             __builtin_memcpy(&v01, px, 2);
             pre01[j] = v01; pre2[j] = px[2];
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
     for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
         const int img = tile / tps2;
         const int tt = tile - img * tps2;
-        const int ty = tt / p.tiles_per_side, tx = tt - ty * p.tiles_per_side;
+        const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
 
         // ---- stage the normalised, split input window
         if (p.u8) {
@@ -184,9 +186,9 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
                 const int r = idx / RW, q = idx - r * RW;
                 const int iy = iy0 + r, ix = ix0 + q;
                 u32x2 hv = {0, 0}, lv = {0, 0};
-                if ((unsigned)iy < (unsigned)S && (unsigned)ix < (unsigned)S) {
-                    const float* px = p.f32 + ((size_t)img * 3 * S + iy) * S + ix;
-                    const float x0 = px[0], x1 = px[(size_t)S * S], x2 = px[2 * (size_t)S * S];
+                if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+                    const float* px = p.f32 + ((size_t)img * 3 * H + iy) * W + ix;
+                    const float x0 = px[0], x1 = px[(size_t)H * W], x2 = px[2 * (size_t)H * W];
                     hv[0] = F::pack2(x0, x1); hv[1] = F::pack2(x2, 0.f);
                     lv[0] = F::rest2(x0, x1, hv[0]); lv[1] = F::pack2(x2 - F::lo_f(hv[1]), 0.f);
                 }
@@ -236,8 +238,11 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
         __syncthreads();
 
         // ---- 3 x 3 stride-2 max over the conv tile: thread = (pooled pixel, 8 channels).  All values are >= 0, so 0 stands
-        // for the pool's -inf padding; taps outside the image (first conv row / column of the first tile row / column) are
-        // redirected to their valid neighbour, which cannot change a maximum.
+        // for the pool's -inf padding; taps outside the conv map are redirected to their valid neighbour, which cannot change a
+        // maximum: conv row / column -1 (first tile row / column) and, at odd conv extents, conv row OHc / column OWc.  The tile
+        // HAS a value there, computed from zero-padded pixels, and PyTorch's -inf padding must keep it out of the maximum
+        // (treating it as 0 would be equivalent post-ReLU, every window holding an in-range value >= 0; the redirect needs no
+        // such argument).  Pooled pixels past PH / PW (partial last tiles) are computed and not stored.
         {
             const int pp = tid >> 3, cg = tid & 7;
             const int py = pp >> 3, px = pp & 7;
@@ -251,6 +256,8 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
                     int cy = 2 * py + dy, cx = 2 * px + dx;                        // conv pixel inside the tile
                     if (ty == 0 && cy == 0) cy = 1;
                     if (tx == 0 && cx == 0) cx = 1;
+                    if (2 * TP * ty + cy - 1 == OHc) cy -= 1;                      // tile pixel (cy, cx) = conv pixel (2 TP ty + cy - 1, 2 TP tx + cx - 1)
+                    if (2 * TP * tx + cx - 1 == OWc) cx -= 1;
                     const char* src = s_out + (cy * TC + cx) * CROW + cg * 32;
                     const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 16);
 #pragma unroll
@@ -258,9 +265,11 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
                 }
             u32x4 hi, lo;
             x3_split8<F16>(best, hi, lo);
-            uint16_t* dst = p.out + (((size_t)img * PH + TP * ty + py) * PH + TP * tx + px) * 64 + cg * 8;
-            *reinterpret_cast<u32x4*>(dst) = hi;
-            *reinterpret_cast<u32x4*>(dst + p.out_plane) = lo;
+            if (TP * ty + py < PH && TP * tx + px < PW) {                          // partial last tile row / column
+                uint16_t* dst = p.out + (((size_t)img * PH + TP * ty + py) * PW + TP * tx + px) * 64 + cg * 8;
+                *reinterpret_cast<u32x4*>(dst) = hi;
+                *reinterpret_cast<u32x4*>(dst + p.out_plane) = lo;
+            }
             if (fuse) {     // the pooled tile as the A image of the reduce: [64 px][128 B] hi | lo over the (dead) input planes, chunk ^= (px >> 1) & 7
                 char* a = smem + pp * 128 + ((cg ^ ((pp >> 1) & 7)) << 4);
                 *reinterpret_cast<u32x4*>(a) = hi;
@@ -310,9 +319,11 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
                 for (int e = 0; e < 8; ++e) v[e] = x3_relu(sc[e] * v[e] + bb[e]);
                 u32x4 hi, lo;
                 x3_split8<F16>(v, hi, lo);
-                uint16_t* dst = p.t1 + (((size_t)img * PH + TP * ty + py) * PH + TP * tx + px) * 64 + cg * 8;
-                *reinterpret_cast<u32x4*>(dst) = hi;
-                *reinterpret_cast<u32x4*>(dst + p.out_plane) = lo;
+                if (TP * ty + py < PH && TP * tx + px < PW) {                      // rows of pooled pixels past the map: computed, not stored
+                    uint16_t* dst = p.t1 + (((size_t)img * PH + TP * ty + py) * PW + TP * tx + px) * 64 + cg * 8;
+                    *reinterpret_cast<u32x4*>(dst) = hi;
+                    *reinterpret_cast<u32x4*>(dst + p.out_plane) = lo;
+                }
             }
             // (the next tile's staging overwrites the A image: its readers are behind the barrier above; the next conv tile is written
             // behind the next staging barrier, by which time every thread has read its t1 chunk of s_out)
@@ -324,18 +335,19 @@ __global__ __launch_bounds__(NT) void conv1_pool_x3_kernel(const Conv1X3Args p) 
 
 }  // namespace
 
-// out planes [n, S/4, S/4, 64] = split(maxpool(relu(colscale * conv1(normalise(patches)) + bias))); S a multiple of 32
+// out planes [n, PH, PW, 64] = split(maxpool(relu(colscale * conv1(normalise(patches)) + bias))); PH = ceil(H/4), PW = ceil(W/4), any H, W
 int sq_launch_conv1_pool_x3(int f16, const uint8_t* u8, const float* f32_nchw, const uint16_t* w152_hi, long long w_plane, const float* bias,
-                            const float* colscale, uint16_t* out_hi, long long out_plane, int n, int S, hipStream_t stream,
+                            const float* colscale, uint16_t* out_hi, long long out_plane, int n, int H, int W, hipStream_t stream,
                             const uint16_t* w1_hi, int w1_tiled, const float* b1, const float* cs1, uint16_t* t1_hi) {
-    SQ_REQUIRE(S % (4 * TP) == 0 && n >= 1, "conv1_pool_x3: patch size %d must be a multiple of %d", S, 4 * TP);
+    SQ_REQUIRE(H >= 7 && W >= 7 && n >= 1, "conv1_pool_x3: n=%d patches of %d x %d", n, H, W);
     Conv1X3Args a;
     a.u8 = u8; a.f32 = f32_nchw; a.w = w152_hi; a.w_plane = w_plane; a.bias = bias; a.colscale = colscale;
-    a.out = out_hi; a.out_plane = out_plane; a.n = n; a.S = S;
+    a.out = out_hi; a.out_plane = out_plane; a.n = n; a.H = H; a.W = W;
     SQ_REQUIRE(!t1_hi || (w1_hi && b1), "conv1_pool_x3: the fused reduce needs its weights and bias");
     a.w1 = w1_hi; a.w1_tiled = w1_tiled; a.b1 = b1; a.cs1 = cs1; a.t1 = t1_hi;
-    a.tiles_per_side = S / (4 * TP);
-    const long long tiles = (long long)n * a.tiles_per_side * a.tiles_per_side;
+    const int PH = ((H + 1) / 2 + 1) / 2, PW = ((W + 1) / 2 + 1) / 2;      // pooled map: ceil(ceil(s/2)/2) per axis
+    a.tiles_y = (PH + TP - 1) / TP; a.tiles_x = (PW + TP - 1) / TP;
+    const long long tiles = (long long)n * a.tiles_y * a.tiles_x;
     SQ_REQUIRE(tiles < (1ll << 31), "conv1_pool_x3: too many tiles");
     a.tiles = (int)tiles;
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
@@ -347,10 +359,10 @@ int sq_launch_conv1_pool_x3(int f16, const uint8_t* u8, const float* f32_nchw, c
     const int grid = (int)(tiles < 256 ? tiles : 256);      // persistent: one block per CU keeps its weight planes in registers
     int prof = -1;
     if (sq_prof_on()) {
-        const double px_out = (double)n * (S / 2) * (S / 2);
+        const double px_out = (double)n * ((H + 1) / 2) * ((W + 1) / 2);
         prof = sq_prof_begin(f16 ? (t1_hi ? "conv1_pool_reduce_f16x3" : "conv1_pool_f16x3") : (t1_hi ? "conv1_pool_reduce_bf16x3" : "conv1_pool_bf16x3"),
-                             2.0 * px_out * 64 * 147 + (t1_hi ? 2.0 * n * (S / 4) * (S / 4) * 64.0 * 64.0 : 0.0),
-                             (double)n * S * S * 3 + (double)n * (S / 4) * (S / 4) * 64 * 4 * (t1_hi ? 2 : 1), stream);
+                             2.0 * px_out * 64 * 147 + (t1_hi ? 2.0 * n * PH * PW * 64.0 * 64.0 : 0.0),
+                             (double)n * H * W * 3 + (double)n * PH * PW * 64 * 4 * (t1_hi ? 2 : 1), stream);
     }
     if (f16) hipLaunchKernelGGL(conv1_pool_x3_kernel<true>, dim3(grid), dim3(NT), LDS_BYTES, stream, a);
     else hipLaunchKernelGGL(conv1_pool_x3_kernel<false>, dim3(grid), dim3(NT), LDS_BYTES, stream, a);

@@ -28,7 +28,7 @@ int sq_launch_bottleneck_chain_c128(const bf16_t* t2, const bf16_t* res, bf16_t*
                                     const bf16_t* w1n, size_t w3_bytes, size_t w1n_bytes, const float* b3, const float* b1n,
                                     long long P, hipStream_t stream);
 int sq_launch_conv1_pool_bf16(const uint8_t* u8, const float* f32_nchw, const bf16_t* w152, const float* bias, bf16_t* out,
-                              int n, int S, hipStream_t stream);
+                              int n, int H, int W, hipStream_t stream);
 int sq_launch_chain_x3_c64(int f16, const uint16_t* t2, long long plT2, const uint16_t* res, long long plRes, uint16_t* y, long long plY,
                            uint16_t* t1n, long long plT1n, int n2, const uint16_t* w3, const uint16_t* w1n, long long plW, size_t w3_bytes,
                            const float* b3, const float* cs3, const float* b1n, const float* cs1n,
@@ -41,7 +41,7 @@ int sq_launch_chain_x3w(int f16, int c, const uint16_t* t2, long long plT2, cons
                         uint16_t* t1n, long long plT1n, int n2, const uint16_t* w3, const uint16_t* w1n, long long plW, size_t w3_bytes, size_t w1n_bytes,
                         const float* b3, const float* cs3, const float* b1n, const float* cs1n, long long P, int w_tiled, hipStream_t stream);
 int sq_launch_conv1_pool_x3(int f16, const uint8_t* u8, const float* f32_nchw, const uint16_t* w152_hi, long long w_plane, const float* bias,
-                            const float* colscale, uint16_t* out_hi, long long out_plane, int n, int S, hipStream_t stream,
+                            const float* colscale, uint16_t* out_hi, long long out_plane, int n, int H, int W, hipStream_t stream,
                             const uint16_t* w1_hi, int w1_tiled, const float* b1, const float* cs1, uint16_t* t1_hi);
 
 namespace {
@@ -57,7 +57,7 @@ constexpr float BN_STD[3] = {0.229f, 0.224f, 0.225f};
 // to evaluating the formula per element; tap geometry comes from a 152-entry table.
 template <typename T>
 __global__ __launch_bounds__(256) void im2col_conv1_kernel(const uint8_t* __restrict__ src_u8, const float* __restrict__ src_f32,
-                                                           T* __restrict__ out, int n, int S, int OH) {
+                                                           T* __restrict__ out, int n, int H, int W, int OH, int OW) {
     __shared__ float lut[3][256];
     __shared__ int8_t t_kh[CONV1_KP], t_kw[CONV1_KP], t_c[CONV1_KP];
     for (int i = threadIdx.x; i < 3 * 256; i += 256) {
@@ -74,12 +74,12 @@ __global__ __launch_bounds__(256) void im2col_conv1_kernel(const uint8_t* __rest
     __syncthreads();
     constexpr int CH = CONV1_KP / 8;     // 19 chunks of 8
     // 32-bit index arithmetic (64-bit div/mod costs hundreds of instructions per element; total < 2^31 checked by the caller)
-    const uint32_t total = (uint32_t)n * OH * OH * CH;
+    const uint32_t total = (uint32_t)n * OH * OW * CH;
     for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const uint32_t ch = idx % CH;
         const uint32_t m = idx / CH;
-        const uint32_t t1 = m / OH;
-        const int ow = (int)(m - t1 * OH), img = (int)(t1 / OH), oh = (int)(t1 - (uint32_t)img * OH);
+        const uint32_t t1 = m / OW;
+        const int ow = (int)(m - t1 * OW), img = (int)(t1 / OH), oh = (int)(t1 - (uint32_t)img * OH);
         const int ih0 = oh * 2 - 3, iw0 = ow * 2 - 3;
         float v[8];
 #pragma unroll
@@ -88,9 +88,9 @@ __global__ __launch_bounds__(256) void im2col_conv1_kernel(const uint8_t* __rest
             const int c = t_c[k];
             const int ih = ih0 + t_kh[k], iw = iw0 + t_kw[k];
             float x = 0.f;
-            if (c >= 0 && (unsigned)ih < (unsigned)S && (unsigned)iw < (unsigned)S) {
-                if (src_u8) x = lut[c][src_u8[(((size_t)img * S + ih) * S + iw) * 3 + c]];
-                else x = src_f32[(((size_t)img * 3 + c) * S + ih) * S + iw];
+            if (c >= 0 && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
+                if (src_u8) x = lut[c][src_u8[(((size_t)img * H + ih) * W + iw) * 3 + c]];
+                else x = src_f32[(((size_t)img * 3 + c) * H + ih) * W + iw];
             }
             v[e] = x;
         }
@@ -112,15 +112,15 @@ __device__ __forceinline__ void stf(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 
 // MaxPool2d(3, stride 2, padding 1) on NHWC (resnet.py:105); thread = (pixel, 16-byte channel group)
 template <typename T>
-__global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__ in, T* __restrict__ out, int n, int H, int OH, int C) {
+__global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__ in, T* __restrict__ out, int n, int H, int W, int OH, int OW, int C) {
     constexpr int V = 16 / (int)sizeof(T);     // channels per 16-byte access
     const int CG = C / V;
-    const uint32_t total = (uint32_t)n * OH * OH * CG;
+    const uint32_t total = (uint32_t)n * OH * OW * CG;
     for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const uint32_t cg = idx % CG;
         const uint32_t px = idx / CG;
-        const uint32_t t1 = px / OH;
-        const int ow = (int)(px - t1 * OH), img = (int)(t1 / OH), oh = (int)(t1 - (uint32_t)img * OH);
+        const uint32_t t1 = px / OW;
+        const int ow = (int)(px - t1 * OW), img = (int)(t1 / OH), oh = (int)(t1 - (uint32_t)img * OH);
         float best[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) best[e] = -INFINITY;
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int ih = oh * 2 - 1 + kh, iw = ow * 2 - 1 + kw;
-                if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)H) {
-                    const u32x4 t = *reinterpret_cast<const u32x4*>(in + (((size_t)img * H + ih) * H + iw) * C + cg * V);
+                if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
+                    const u32x4 t = *reinterpret_cast<const u32x4*>(in + (((size_t)img * H + ih) * W + iw) * C + cg * V);
                     if constexpr (sizeof(T) == 2) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -155,15 +155,15 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
     }
 }
 
-// AvgPool2d(7) (resnet.py:110,166): mean of the top-left 7x7 window of the final map, fp32 out
+// AvgPool2d(7) (resnet.py:110,166): mean of the top-left 7x7 window of the final H x W map (row pitch W), fp32 out
 template <typename T>
-__global__ void avgpool7_kernel(const T* __restrict__ in, float* __restrict__ out, int n, int H, int C) {
+__global__ void avgpool7_kernel(const T* __restrict__ in, float* __restrict__ out, int n, int H, int W, int C) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n * C) return;
     const int c = idx % C, img = idx / C;
     float acc = 0.f;
     for (int h = 0; h < 7; ++h)
-        for (int w = 0; w < 7; ++w) acc += ldf(in + (((size_t)img * H + h) * H + w) * C + c);
+        for (int w = 0; w < 7; ++w) acc += ldf(in + (((size_t)img * H + h) * W + w) * C + c);
     out[idx] = acc / 49.0f;
 }
 
@@ -172,7 +172,7 @@ __global__ void avgpool7_kernel(const T* __restrict__ in, float* __restrict__ ou
 // AvgPool2d(7) over hi / lo planes, fp32 out (same summation order as avgpool7_kernel)
 // A non-finite pooled value (an fp16 plane overflowed somewhere upstream: x3_fmt.h x3_relu) ORs 1 into *nonfinite.
 template <bool F16>
-__global__ void avgpool7_x3_kernel(const bf16_t* __restrict__ in, long long plane, float* __restrict__ out, int n, int H, int C,
+__global__ void avgpool7_x3_kernel(const bf16_t* __restrict__ in, long long plane, float* __restrict__ out, int n, int H, int W, int C,
                                    unsigned* __restrict__ nonfinite) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n * C) return;
@@ -180,7 +180,7 @@ __global__ void avgpool7_x3_kernel(const bf16_t* __restrict__ in, long long plan
     float acc = 0.f;
     for (int h = 0; h < 7; ++h)
         for (int w = 0; w < 7; ++w) {
-            const size_t o = (((size_t)img * H + h) * H + w) * C + c;
+            const size_t o = (((size_t)img * H + h) * W + w) * C + c;
             acc += X3Fmt<F16>::one(in[o]) + X3Fmt<F16>::one(in[plane + o]);
         }
     out[idx] = acc / 49.0f;
@@ -207,13 +207,21 @@ void build_specs(ConvSpec* specs) {
 
 struct RnBufs { void* col; void* act[5]; void* frag; size_t bytes; };
 
-void rn_bufs(int dtype, int n, int S, char* base, RnBufs* o) {
+// elements of the largest activation of one patch: conv1's output [ceil(H/2), ceil(W/2), 64], or -- odd conv maps only, where
+// two pooled rows cover more than two conv rows -- layer 1's output [ceil(H/4), ceil(W/4), 256]; every later stage is smaller
+size_t rn_act_elems(int H, int W) {
+    const size_t OH = (H + 1) / 2, OW = (W + 1) / 2, PH = (OH + 1) / 2, PW = (OW + 1) / 2;
+    const size_t a = OH * OW * 64, b = PH * PW * 256;
+    return a > b ? a : b;
+}
+
+void rn_bufs(int dtype, int n, int H, int W, char* base, RnBufs* o) {
     size_t off = 0;
     auto take = [&](size_t bytes) { off = sq_align_up(off, 256); char* p = base ? base + off : nullptr; off += bytes; return (void*)p; };
     const size_t es = sq_dtype_size(dtype);
-    const size_t OH = S / 2;
-    o->col = dtype == SQ_F32 ? take((size_t)n * OH * OH * CONV1_KP * es) : nullptr;    // bf16 and the split modes: fused stem, no im2col matrix
-    const size_t act = (size_t)n * OH * OH * 64 * es;          // largest activation: conv1 out == layer1 out
+    const size_t OH = (H + 1) / 2, OW = (W + 1) / 2;
+    o->col = dtype == SQ_F32 ? take((size_t)n * OH * OW * CONV1_KP * es) : nullptr;    // bf16 and the split modes: fused stem, no im2col matrix
+    const size_t act = (size_t)n * rn_act_elems(H, W) * es;    // largest activation: conv1 out == layer1 out at multiples of 4
     for (int i = 0; i < 5; ++i) o->act[i] = take(act);
     o->frag = (dtype == SQ_BF16X3 || dtype == SQ_F16X3) ? take(sq_chain_x3_frag_bytes()) : nullptr;     // chain_x3.hip's fragment-ordered weights
     o->bytes = sq_align_up(off, 256);
@@ -244,9 +252,23 @@ extern "C" int sq_resnet50_layout_init(sq_resnet50_layout* out) {
 extern "C" size_t sq_resnet50_workspace_bytes(int dtype, int n_patches, int patch_size) {
     if (n_patches < 1 || patch_size < 32 || patch_size % 32) return 0;
     RnBufs b;
-    rn_bufs(dtype, n_patches, patch_size, nullptr, &b);
+    rn_bufs(dtype, n_patches, patch_size, patch_size, nullptr, &b);
     return b.bytes;
 }
+
+// sizes sq_resnet50_extract_hw admits: final map 7..13 per axis, i.e. AvgPool2d(7) yields exactly one window (src/resnet.py:110,166-168)
+static bool rn_hw_admitted(int H, int W) { return H >= SQ_RESNET50_HW_MIN && H <= SQ_RESNET50_HW_MAX && W >= SQ_RESNET50_HW_MIN && W <= SQ_RESNET50_HW_MAX; }
+
+extern "C" size_t sq_resnet50_workspace_bytes_hw(int dtype, int n_patches, int height, int width) {
+    if (n_patches < 1 || !rn_hw_admitted(height, width)) return 0;
+    if (dtype != SQ_F32 && dtype != SQ_BF16 && dtype != SQ_BF16X3 && dtype != SQ_F16X3) return 0;
+    RnBufs b;
+    rn_bufs(dtype, n_patches, height, width, nullptr, &b);
+    return b.bytes;
+}
+
+static int rn_extract(bool hw_rule, int dtype, const void* weights, const float* bias, const uint8_t* patches_u8, const float* patches_f32_nchw, int n,
+                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st);
 
 extern "C" int sq_resnet50_extract(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
                                    const float* patches_f32_nchw, int n, int S, float* features, void* workspace,
@@ -258,15 +280,35 @@ extern "C" int sq_resnet50_extract(int dtype, const void* weights, const float* 
 extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
                                            const float* patches_f32_nchw, int n, int S, float* features, void* workspace,
                                            size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
+    return rn_extract(false, dtype, weights, bias, patches_u8, patches_f32_nchw, n, S, S, features, workspace, workspace_bytes, nonfinite_flag,
+                      (hipStream_t)stream_);
+}
+
+extern "C" int sq_resnet50_extract_hw(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
+                                      const float* patches_f32_nchw, int n, int height, int width, float* features, void* workspace,
+                                      size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream_) {
+    return rn_extract(true, dtype, weights, bias, patches_u8, patches_f32_nchw, n, height, width, features, workspace, workspace_bytes,
+                      nonfinite_flag, (hipStream_t)stream_);
+}
+
+// the forward pass itself for an H0 x W0 input.  hw_rule: admit what sq_resnet50_extract_hw admits (else: the square entries' rule)
+static int rn_extract(bool hw_rule, int dtype, const void* weights, const float* bias, const uint8_t* patches_u8, const float* patches_f32_nchw, int n,
+                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st) {
     SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16 || dtype == SQ_BF16X3 || dtype == SQ_F16X3, "resnet50: dtype %d", dtype);
     SQ_REQUIRE(weights && bias && features && workspace, "resnet50: null pointer");
     SQ_REQUIRE((patches_u8 != nullptr) != (patches_f32_nchw != nullptr), "resnet50: give exactly one of patches_u8 / patches_f32_nchw");
-    SQ_REQUIRE(n >= 1 && S >= 224 && S % 32 == 0, "resnet50: n=%d patch_size=%d (need a multiple of 32, >= 224)", n, S);
+    if (hw_rule) {
+        SQ_REQUIRE(n >= 1 && rn_hw_admitted(H0, W0),
+                   "resnet50_hw: n=%d, patch %d x %d; height and width must each lie in [%d, %d] -- the sizes whose final map is 7..13 per axis, "
+                   "so that AvgPool2d(7) yields one window and 2048 features (above: the reference returns more; below: it fails)",
+                   n, H0, W0, SQ_RESNET50_HW_MIN, SQ_RESNET50_HW_MAX);
+    } else {
+        SQ_REQUIRE(n >= 1 && H0 >= 224 && H0 % 32 == 0, "resnet50: n=%d patch_size=%d (need a multiple of 32, >= 224)", n, H0);
+    }
     sq_resnet50_layout lay;
     sq_resnet50_layout_init(&lay);
     RnBufs b;
-    rn_bufs(dtype, n, S, (char*)workspace, &b);
+    rn_bufs(dtype, n, H0, W0, (char*)workspace, &b);
     if (b.bytes > workspace_bytes) {
         sq_set_error("resnet50: workspace %zu < required %zu", workspace_bytes, b.bytes);
         return SQ_ERR_WORKSPACE;
@@ -278,24 +320,25 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
     const bool lp = dtype == SQ_BF16;
     auto W = [&](const sq_conv_desc& d) { return (const void*)((const char*)weights + (size_t)d.w_off * es); };
     const size_t w_bytes_total = (size_t)lay.w_total * es;
-    const size_t act_cap = (size_t)n * (S / 2) * (S / 2) * 64 * es;
-    const long long act_plane = (long long)n * (S / 2) * (S / 2) * 64;            // x3: elements between an activation's hi and lo plane
-    SQ_REQUIRE(act_cap < (1ull << 31) && (lp || x3 || (size_t)n * (S / 2) * (S / 2) * CONV1_KP * es < (1ull << 31)),
+    const int OH1 = (H0 + 1) / 2, OW1 = (W0 + 1) / 2;                             // conv1's map: ceil(H/2) x ceil(W/2)
+    const size_t act_cap = (size_t)n * rn_act_elems(H0, W0) * es;
+    const long long act_plane = (long long)n * (long long)rn_act_elems(H0, W0);   // x3: elements between an activation's hi and lo plane
+    SQ_REQUIRE(act_cap < (1ull << 31) && (lp || x3 || (size_t)n * OH1 * OW1 * CONV1_KP * es < (1ull << 31)),
                "resnet50: sub-batch of %d patches exceeds the 2 GiB buffer-descriptor limit (bf16 and the split modes: <= 1300 patches of 224, fp32: <= 280)", n);
 
-    // conv as a GEMM launch.  in: NHWC [n, H, H, cin];  out: [n, OH, OH, cout]
-    // dual (split modes): the block's downsample branch dd(din) -- din = the block's input [n, dH, dH, dd.cin] -- rides in the
+    // conv as a GEMM launch.  in: NHWC [n, H, Wd, cin];  out: [n, OH, OW, cout]
+    // dual (split modes): the block's downsample branch dd(din) -- din = the block's input [n, dH, dW, dd.cin] -- rides in the
     // expand launch as a second product instead of being written and read back as `res` (gemm.h A2 / B2)
-    auto conv = [&](const sq_conv_desc& d, const void* in, int H, void* out, int OH, const void* res, int act,
-                    const sq_conv_desc* dd = nullptr, const void* din = nullptr, int dH = 0) -> int {
+    auto conv = [&](const sq_conv_desc& d, const void* in, int H, int Wd, void* out, int OH, int OW, const void* res, int act,
+                    const sq_conv_desc* dd = nullptr, const void* din = nullptr, int dH = 0, int dW = 0) -> int {
         GemmArgs g;
-        g.M = n * OH * OH; g.N = d.cout; g.K = d.k_padded;
+        g.M = n * OH * OW; g.N = d.cout; g.K = d.k_padded;
         g.A = in;
         if (d.k == 1 && d.stride == 1) {
             g.lda = d.cin; g.a_bytes = (size_t)g.M * d.cin * es;
         } else {
-            g.conv = 1; g.H = H; g.W = H; g.Cin = d.cin; g.OH = OH; g.OW = OH; g.KW = d.k; g.stride = d.stride; g.pad = d.pad;
-            g.a_bytes = (size_t)n * H * H * d.cin * es;
+            g.conv = 1; g.H = H; g.W = Wd; g.Cin = d.cin; g.OH = OH; g.OW = OW; g.KW = d.k; g.stride = d.stride; g.pad = d.pad;
+            g.a_bytes = (size_t)n * H * Wd * d.cin * es;
         }
         g.B = W(d); g.ldb = d.k_padded; g.b_bytes = w_bytes_total - (size_t)d.w_off * es;
         g.bias = bias + d.b_off;
@@ -307,10 +350,10 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
             g.x3_f16 = f16; g.colscale = colscale + d.b_off;
             g.b_tiled = 1;             // every convolution behind the stem: K-tile-major planes (resnet.py split_planes)
             if (dd) {
-                g.A2 = din; g.plA2 = act_plane; g.lda2 = dd->cin; g.a2_bytes = (size_t)n * dH * dH * dd->cin * es;
+                g.A2 = din; g.plA2 = act_plane; g.lda2 = dd->cin; g.a2_bytes = (size_t)n * dH * dW * dd->cin * es;
                 g.B2 = W(*dd); g.ldb2 = dd->k_padded; g.b2_bytes = w_bytes_total - (size_t)dd->w_off * es; g.K2 = dd->k_padded;
                 g.bias2 = bias + dd->b_off; g.colscale2 = colscale + dd->b_off;
-                g.dH = dH; g.dW = dH; g.dOH = OH; g.dOW = OH; g.dstride = dd->stride;
+                g.dH = dH; g.dW = dW; g.dOH = OH; g.dOW = OW; g.dstride = dd->stride;
             }
             return sq_launch_gemm_x3(g, st);
         }
@@ -318,12 +361,11 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
     };
 #define RUN(expr) do { if (int _e = (expr)) return _e; } while (0)
 
-    const int OH1 = S / 2;
-    int H = OH1 / 2;    // after the max-pool
+    int H = (OH1 + 1) / 2, Wd = (OW1 + 1) / 2;    // after the max-pool (3x3, stride 2, pad 1): ceil of half per axis
     bool stem_t1 = false;
     if (lp) {           // conv1 + bn1 + relu + maxpool in one kernel (conv1.hip)
         const sq_conv_desc& d = lay.conv[0];
-        RUN(sq_launch_conv1_pool_bf16(patches_u8, patches_f32_nchw, (const bf16_t*)W(d), bias + d.b_off, (bf16_t*)b.act[1], n, S, st));
+        RUN(sq_launch_conv1_pool_bf16(patches_u8, patches_f32_nchw, (const bf16_t*)W(d), bias + d.b_off, (bf16_t*)b.act[1], n, H0, W0, st));
     } else if (x3) {    // the same fusion on hi / lo planes (conv1_x3.hip)
         const sq_conv_desc& d = lay.conv[0];
         // the first bottleneck's reduce 1x1 (64 -> 64) rides in the stem launch (SQ_RESNET_NO_STEM_REDUCE=1: its own launch): its
@@ -331,18 +373,18 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
         const sq_conv_desc& r1 = lay.conv[1];
         stem_t1 = r1.k == 1 && r1.stride == 1 && r1.cin == 64 && r1.cout == 64 && !sq_env_flag("SQ_RESNET_NO_STEM_REDUCE");
         RUN(sq_launch_conv1_pool_x3(f16, patches_u8, patches_f32_nchw, (const uint16_t*)W(d), lay.w_total, bias + d.b_off, colscale + d.b_off,
-                                    (uint16_t*)b.act[1], act_plane, n, S, st,
+                                    (uint16_t*)b.act[1], act_plane, n, H0, W0, st,
                                     stem_t1 ? (const uint16_t*)W(r1) : nullptr, 1, stem_t1 ? bias + r1.b_off : nullptr,
                                     stem_t1 ? colscale + r1.b_off : nullptr, stem_t1 ? (uint16_t*)b.act[2] : nullptr));
     } else {
         {   // conv1 + bn1 + relu
-            const size_t work = (size_t)n * OH1 * OH1 * (CONV1_KP / 8);
+            const size_t work = (size_t)n * OH1 * OW1 * (CONV1_KP / 8);
             size_t nb = (work + 255) / 256; if (nb > 65535) nb = 65535;
-            hipLaunchKernelGGL(im2col_conv1_kernel<float>, dim3((int)nb), dim3(256), 0, st, patches_u8, patches_f32_nchw, (float*)b.col, n, S, OH1);
+            hipLaunchKernelGGL(im2col_conv1_kernel<float>, dim3((int)nb), dim3(256), 0, st, patches_u8, patches_f32_nchw, (float*)b.col, n, H0, W0, OH1, OW1);
             SQ_LAUNCH_CHECK();
             GemmArgs g;
             const sq_conv_desc& d = lay.conv[0];
-            g.M = n * OH1 * OH1; g.N = 64; g.K = CONV1_KP;
+            g.M = n * OH1 * OW1; g.N = 64; g.K = CONV1_KP;
             g.A = b.col; g.lda = CONV1_KP; g.a_bytes = (size_t)g.M * CONV1_KP * es;
             g.B = W(d); g.ldb = CONV1_KP; g.b_bytes = w_bytes_total;
             g.bias = bias + d.b_off; g.act = SQ_ACT_RELU;
@@ -350,16 +392,17 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
             RUN(sq_launch_gemm(g, dtype, st));
         }
         {
-            const size_t work = (size_t)n * H * H * 64 / (16 / es);
+            const size_t work = (size_t)n * H * Wd * 64 / (16 / es);
             size_t nb = (work + 255) / 256; if (nb > 65535) nb = 65535;
-            hipLaunchKernelGGL(maxpool3x3s2_kernel<float>, dim3((int)nb), dim3(256), 0, st, (const float*)b.act[0], (float*)b.act[1], n, OH1, H, 64);
+            hipLaunchKernelGGL(maxpool3x3s2_kernel<float>, dim3((int)nb), dim3(256), 0, st, (const float*)b.act[0], (float*)b.act[1], n, OH1, OW1, H, Wd, 64);
             SQ_LAUNCH_CHECK();
         }
     }
     // bottleneck stack: x lives in act[xi]; t1, t2, ds, y are taken from the other four buffers.
     // bf16, 56 x 56 stage (layer 1): the 3x3, the expand 1x1 (+ identity, ReLU) and the NEXT block's reduce 1x1 are one
     // launch (bottleneck.hip) -- that block's conv1 output then already sits in act[t1i] when its turn comes.
-    const bool fuse56 = lp && !sq_env_flag("SQ_RESNET_NO_FUSE") && (128 + 2 * H + 2) * 128 <= 32768;
+    // (the tail's halo is 128 + 2 Wd + 2 flat rows: the map's WIDTH decides whether it fits; its tap masks take H and Wd apart)
+    const bool fuse56 = lp && !sq_env_flag("SQ_RESNET_NO_FUSE") && (128 + 2 * Wd + 2) * 128 <= 32768;
     const bool fuse_chain = lp && !sq_env_flag("SQ_RESNET_NO_FUSE") && !sq_env_flag("SQ_RESNET_NO_CHAIN");
     const bool fuse_chain256 = fuse_chain;
     int xi = 1, ci = 1, t1i = stem_t1 ? 2 : -1;
@@ -373,8 +416,9 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
             void* t1 = b.act[t1_idx];
             const sq_conv_desc& c1 = lay.conv[ci]; const sq_conv_desc& c2 = lay.conv[ci + 1]; const sq_conv_desc& c3 = lay.conv[ci + 2];
             const bool has_ds = bk == 0;
-            const int OH = H / c2.stride;
-            if (t1i < 0) RUN(conv(c1, x, H, t1, H, nullptr, SQ_ACT_RELU));
+            // 3x3 stride 2 pad 1 and the 1x1 stride 2 downsample both give floor((s - 1) / 2) + 1 = ceil(s / 2)
+            const int OH = (H - 1) / c2.stride + 1, OW = (Wd - 1) / c2.stride + 1;
+            if (t1i < 0) RUN(conv(c1, x, H, Wd, t1, H, Wd, nullptr, SQ_ACT_RELU));
             const int cnext = ci + (has_ds ? 4 : 3);
             if (fuse56 && li == 0) {
                 void* y = b.act[free_[1]]; void* t1n = b.act[free_[2]];
@@ -386,7 +430,7 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                                                   (const bf16_t*)W(c2), (const bf16_t*)W(c3), (const bf16_t*)W(n1), rest(c2), rest(c3), rest(n1),
                                                   bias + c2.b_off, bias + c3.b_off, bias + n1.b_off,
                                                   has_ds ? (const bf16_t*)x : nullptr, has_ds ? (const bf16_t*)W(dsd) : nullptr,
-                                                  has_ds ? rest(dsd) : 0, has_ds ? bias + dsd.b_off : nullptr, n, H, H, st));
+                                                  has_ds ? rest(dsd) : 0, has_ds ? bias + dsd.b_off : nullptr, n, H, Wd, st));
                 xi = free_[1];
                 t1i = free_[2];
                 ci = cnext;
@@ -401,8 +445,8 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                 cnext < SQ_RESNET50_CONVS && lay.conv[cnext].k == 1 && lay.conv[cnext].stride == 1 && lay.conv[cnext].cin == 256 &&
                 (lay.conv[cnext].cout == 64 || lay.conv[cnext].cout == 128) &&
                 (!has_ds || (lay.conv[ci + 3].k == 1 && lay.conv[ci + 3].stride == 1 && lay.conv[ci + 3].cin == 64 && !sq_env_flag("SQ_RESNET_NO_CHAIN_DS")));
-            const bool x3_tail = x3_chain && c2.k == 3 && c2.cin == 64 && c2.cout == 64 && H <= 70 && !sq_env_flag("SQ_RESNET_NO_TAIL");
-            if (!x3_tail) RUN(conv(c2, t1, H, t2, OH, nullptr, SQ_ACT_RELU));
+            const bool x3_tail = x3_chain && c2.k == 3 && c2.cin == 64 && c2.cout == 64 && Wd <= 70 && !sq_env_flag("SQ_RESNET_NO_TAIL");
+            if (!x3_tail) RUN(conv(c2, t1, H, Wd, t2, OH, OW, nullptr, SQ_ACT_RELU));
             if (x3_chain) {
                 const sq_conv_desc& n1 = lay.conv[cnext];
                 const sq_conv_desc& dsd = lay.conv[ci + 3];           // only read when has_ds
@@ -415,12 +459,12 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                                            has_ds ? (const uint16_t*)x : nullptr, act_plane, has_ds ? (const uint16_t*)W(dsd) : nullptr,
                                            has_ds ? rest(dsd) : 0, has_ds ? bias + dsd.b_off : nullptr, has_ds ? colscale + dsd.b_off : nullptr,
                                            x3_tail ? (const uint16_t*)t1 : nullptr, act_plane, x3_tail ? (const uint16_t*)W(c2) : nullptr,
-                                           x3_tail ? rest(c2) : 0, x3_tail ? bias + c2.b_off : nullptr, x3_tail ? colscale + c2.b_off : nullptr, H, H * H,
-                                           (long long)n * OH * OH, (uint16_t*)b.frag, 1, st));
+                                           x3_tail ? rest(c2) : 0, x3_tail ? bias + c2.b_off : nullptr, x3_tail ? colscale + c2.b_off : nullptr, Wd, H * Wd,
+                                           (long long)n * OH * OW, (uint16_t*)b.frag, 1, st));
                 ci = cnext;
                 xi = free_[2];
                 t1i = x3_tail ? free_[0] : t1_idx;
-                H = OH;
+                H = OH; Wd = OW;
                 continue;
             }
             // split modes, plain bottlenecks of the 128- and 256-plane stages (28 x 28, 14 x 14): expand 1x1 + identity + ReLU and the
@@ -433,11 +477,11 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                 auto rest = [&](const sq_conv_desc& d) { return w_bytes_total - (size_t)d.w_off * es; };
                 RUN(sq_launch_chain_x3w(f16, c3.cin, (const uint16_t*)t2, act_plane, (const uint16_t*)x, act_plane, (uint16_t*)y, act_plane,
                                         (uint16_t*)t1, act_plane, n1.cout, (const uint16_t*)W(c3), (const uint16_t*)W(n1), lay.w_total, rest(c3), rest(n1),
-                                        bias + c3.b_off, colscale + c3.b_off, bias + n1.b_off, colscale + n1.b_off, (long long)n * OH * OH, 1, st));
+                                        bias + c3.b_off, colscale + c3.b_off, bias + n1.b_off, colscale + n1.b_off, (long long)n * OH * OW, 1, st));
                 ci = cnext;
                 xi = free_[2];
                 t1i = t1_idx;
-                H = OH;
+                H = OH; Wd = OW;
                 continue;
             }
             const void* identity = x;
@@ -445,7 +489,7 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
             // (SQ_RESNET_NO_DUAL=1: its own launch, a [n, OH, OH, 4 planes] tensor written and read back)
             const bool x3_dual = x3 && has_ds && lay.conv[ci + 3].k == 1 && c3.k == 1 && c3.cout % 128 == 0 && !sq_env_flag("SQ_RESNET_NO_DUAL");
             if (has_ds && !x3_dual) {
-                RUN(conv(lay.conv[ci + 3], x, H, ds, OH, nullptr, SQ_ACT_NONE));
+                RUN(conv(lay.conv[ci + 3], x, H, Wd, ds, OH, OW, nullptr, SQ_ACT_NONE));
                 identity = ds;
             }
             // 128-plane stage (28 x 28): expand 1x1 + identity + ReLU and the NEXT block's reduce 1x1 in one launch
@@ -456,11 +500,11 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                 auto rest = [&](const sq_conv_desc& d) { return w_bytes_total - (size_t)d.w_off * es; };
                 RUN(sq_launch_bottleneck_chain_c128((const bf16_t*)t2, (const bf16_t*)identity, (bf16_t*)y, (bf16_t*)t1, n1.cout,
                                                     (const bf16_t*)W(c3), (const bf16_t*)W(n1), rest(c3), rest(n1), bias + c3.b_off,
-                                                    bias + n1.b_off, (long long)n * OH * OH, st));
+                                                    bias + n1.b_off, (long long)n * OH * OW, st));
                 ci = cnext;
                 xi = free_[2];
                 t1i = t1_idx;
-                H = OH;
+                H = OH; Wd = OW;
                 continue;
             }
             // 256-plane stage (14 x 14): the same chain with the t2 rows held in registers (chain256.hip)
@@ -470,26 +514,26 @@ extern "C" int sq_resnet50_extract_checked(int dtype, const void* weights, const
                 auto rest = [&](const sq_conv_desc& d) { return w_bytes_total - (size_t)d.w_off * es; };
                 RUN(sq_launch_bottleneck_chain_c256((const bf16_t*)t2, (const bf16_t*)identity, (bf16_t*)y, (bf16_t*)t1,
                                                     (const bf16_t*)W(c3), (const bf16_t*)W(n1), rest(c3), rest(n1), bias + c3.b_off,
-                                                    bias + n1.b_off, (long long)n * OH * OH, st));
+                                                    bias + n1.b_off, (long long)n * OH * OW, st));
                 ci = cnext;
                 xi = free_[2];
                 t1i = t1_idx;
-                H = OH;
+                H = OH; Wd = OW;
                 continue;
             }
-            if (x3_dual) RUN(conv(c3, t2, OH, y, OH, nullptr, SQ_ACT_RELU, &lay.conv[ci + 3], x, H));
-            else RUN(conv(c3, t2, OH, y, OH, identity, SQ_ACT_RELU));       // relu(bn3(conv3) + identity)
+            if (x3_dual) RUN(conv(c3, t2, OH, OW, y, OH, OW, nullptr, SQ_ACT_RELU, &lay.conv[ci + 3], x, H, Wd));
+            else RUN(conv(c3, t2, OH, OW, y, OH, OW, identity, SQ_ACT_RELU));       // relu(bn3(conv3) + identity)
             ci = cnext;
             xi = free_[2];
             t1i = -1;
-            H = OH;
+            H = OH; Wd = OW;
         }
     {
         const int total = n * 2048;
-        if (f16) hipLaunchKernelGGL(avgpool7_x3_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], act_plane, features, n, H, 2048, nonfinite_flag);
-        else if (x3) hipLaunchKernelGGL(avgpool7_x3_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], act_plane, features, n, H, 2048, nonfinite_flag);
-        else if (lp) hipLaunchKernelGGL(avgpool7_kernel<bf16_t>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], features, n, H, 2048);
-        else hipLaunchKernelGGL(avgpool7_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)b.act[xi], features, n, H, 2048);
+        if (f16) hipLaunchKernelGGL(avgpool7_x3_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], act_plane, features, n, H, Wd, 2048, nonfinite_flag);
+        else if (x3) hipLaunchKernelGGL(avgpool7_x3_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], act_plane, features, n, H, Wd, 2048, nonfinite_flag);
+        else if (lp) hipLaunchKernelGGL(avgpool7_kernel<bf16_t>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], features, n, H, Wd, 2048);
+        else hipLaunchKernelGGL(avgpool7_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)b.act[xi], features, n, H, Wd, 2048);
         SQ_LAUNCH_CHECK();
     }
 #undef RUN

@@ -208,21 +208,30 @@ class ResNet50(nn.Module):
             raise _lib.SequoiaHipError("ResNet50 weights are on the CPU: call .to('cuda') first (no CPU fallback)")
         src = patches_u8 if patches_u8 is not None else x_f32
         n = src.shape[0]
-        S = src.shape[1] if patches_u8 is not None else src.shape[2]
+        H, W = (src.shape[1], src.shape[2]) if patches_u8 is not None else (src.shape[2], src.shape[3])
         feats = torch.empty(n, 2048, dtype=torch.float32, device=w.device)
-        need = _lib.lib().sq_resnet50_workspace_bytes(self.compute_dtype, n, S)
+        # squares that are a multiple of 32 keep the entry they always took (beyond 416 only it takes them); every other
+        # shape goes through sq_resnet50_extract_hw -- where both apply the two give identical bits
+        square = _is_square32(H, W)
+        need = (_lib.lib().sq_resnet50_workspace_bytes(self.compute_dtype, n, H) if square
+                else _lib.lib().sq_resnet50_workspace_bytes_hw(self.compute_dtype, n, H, W))
         if need == 0:
-            raise ValueError(f"unsupported patch size {S} (need a multiple of 32, >= 224)")
+            raise ValueError(_unsupported(H, W))
         if not isinstance(self._ws, dict):
             self._ws = {}
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < need or ws.device != w.device:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=w.device)
         with torch.cuda.device(w.device):
-            _lib.check(_lib.lib().sq_resnet50_extract_checked(self.compute_dtype, _lib.ptr(w), _lib.ptr(b), _lib.ptr(patches_u8),
-                                                              _lib.ptr(x_f32), n, S, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
-                                                              _lib.ptr(flag) if flag is not None else None,
-                                                              _lib.stream_ptr(w.device)))
+            fl = _lib.ptr(flag) if flag is not None else None
+            if square:
+                _lib.check(_lib.lib().sq_resnet50_extract_checked(self.compute_dtype, _lib.ptr(w), _lib.ptr(b), _lib.ptr(patches_u8),
+                                                                  _lib.ptr(x_f32), n, H, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
+                                                                  fl, _lib.stream_ptr(w.device)))
+            else:
+                _lib.check(_lib.lib().sq_resnet50_extract_hw(self.compute_dtype, _lib.ptr(w), _lib.ptr(b), _lib.ptr(patches_u8),
+                                                             _lib.ptr(x_f32), n, H, W, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
+                                                             fl, _lib.stream_ptr(w.device)))
         return feats
 
     @torch.no_grad()
@@ -235,20 +244,24 @@ class ResNet50(nn.Module):
 
         def rerun():
             tw = self.exact_twin()                      # built and synced once, not per chunk
-            step = max(1, min(128, tw.max_sub_batch(x.shape[2])))
+            step = max(1, min(128, tw.max_sub_batch((x.shape[2], x.shape[3]))))
             return torch.cat([tw._run(x_f32=x[i:i + step]) for i in range(0, x.shape[0], step)])
         return self._resolve_nonfinite(feats, flag, on_nonfinite, rerun)
 
     def max_sub_batch(self, S):
-        """Largest launch group the 2 GiB buffer-descriptor limit allows at patch size S (sq_resnet50_extract's check): the
-        [n, S/2, S/2, 64] activation planes, and in fp32 mode the [n (S/2)^2, 152] im2col matrix of the stem."""
+        """Largest launch group the 2 GiB buffer-descriptor limit allows at patch size S -- an int, or (H, W) -- as
+        sq_resnet50_extract checks it: the activation planes, [n, ceil(H/2), ceil(W/2), 64] (conv1's output) or, when that
+        map is odd, the slightly larger [n, ceil(H/4), ceil(W/4), 256] (layer 1's), and in fp32 mode the
+        [n ceil(H/2) ceil(W/2), 152] im2col matrix of the stem."""
+        H, W = (int(S[0]), int(S[1])) if isinstance(S, (tuple, list, torch.Size)) else (int(S), int(S))
         es = 4 if self.compute_dtype == _lib.SQ_F32 else 2
-        per = (S // 2) ** 2 * (152 if self.compute_dtype == _lib.SQ_F32 else 64) * es
+        oh, ow = (H + 1) // 2, (W + 1) // 2
+        per = max(oh * ow * (152 if self.compute_dtype == _lib.SQ_F32 else 64), ((oh + 1) // 2) * ((ow + 1) // 2) * 256) * es
         return max(1, ((1 << 31) - 1) // per)
 
     @torch.no_grad()
     def extract_patches_u8(self, patches, sub_batch=500, on_nonfinite="rerun", flag=None):
-        """uint8 HWC patches [n, S, S, 3] -> f32 [n, 2048]; fuses compute_features_hdf5.py:119-120's transform.
+        """uint8 HWC patches [n, H, W, 3] (any admitted shape, see _unsupported) -> f32 [n, 2048]; fuses compute_features_hdf5.py:119-120's transform.
         Patches go through in launch groups of <= sub_batch (clamped to what the 2 GiB buffer-descriptor limit allows for
         this mode and patch size); larger groups measured faster -- longer grids, fewer tails.
         Split-fp16 mode: a group whose features came out non-finite (an activation beyond fp16's range) is, per
@@ -259,7 +272,7 @@ class ResNet50(nn.Module):
         patches = torch.as_tensor(patches)
         if patches.shape[0] == 0:                        # a slide whose patch store is empty: no features, no launch
             return torch.empty(0, 2048, dtype=torch.float32, device=dev)
-        sub_batch = max(1, min(int(sub_batch), self.max_sub_batch(patches.shape[1])))
+        sub_batch = max(1, min(int(sub_batch), self.max_sub_batch((patches.shape[1], patches.shape[2]))))
         if self.compute_dtype == _lib.SQ_F16X3:
             if on_nonfinite != "defer":
                 flag = self.new_flag()
@@ -294,6 +307,19 @@ class ResNet50(nn.Module):
 
     def forward(self, x):
         raise NotImplementedError("only forward_extract is on the SEQUOIA path (fc is never used by the reference scripts)")
+
+
+HW_MIN, HW_MAX = 193, 416      # include/sequoia_hip.h SQ_RESNET50_HW_MIN / _MAX
+
+
+def _is_square32(H, W):
+    return H == W and H >= 224 and H % 32 == 0
+
+
+def _unsupported(H, W):
+    return (f"unsupported patch size {H} x {W}: height and width must each lie in [{HW_MIN}, {HW_MAX}] (the final map is then "
+            f"7..13 per axis and AvgPool2d(7) yields 2048 features; above that the reference returns more, below it fails), "
+            f"or the patch is a square multiple of 32, >= 224")
 
 
 def resnet50(pretrained=False, compute_dtype="fp32", **kwargs):
