@@ -1,7 +1,10 @@
 """WSI -> patch HDF5 files -- counterpart of /root/reference/pre_processing/patch_gen_hdf5.py:148-208 (same flags,
 same outputs: ``<patch_path>/<slide>/<slide>.hdf5`` + ``complete.txt``, ``<mask_path>/<slide>/mask.npy``).  Reading
 real ``.svs`` / ``.tiff`` slides needs openslide-python, exactly like the reference; the mask / tiling / filter logic is
-sequoia-pub_amd/patchgen.py."""
+sequoia-pub_amd/patchgen.py.  ``--filter device`` runs the per-tile tissue / contrast filter (and the 40x shrink) on the
+GPU, ``--filter_batch`` candidate tiles at a time, with the same files as a result; the slides then go through the calling
+process one after another -- forked pool workers must not share a process's GPU state -- and ``--parallel`` only prints
+that."""
 import argparse
 import os
 from multiprocessing import Pool
@@ -16,13 +19,15 @@ def get_slide_id(slide_name):
 
 
 def process(opts):
-    slide_path, patch_size, patches_output_dir, mask_path, slide_id, max_patches_per_slide = opts
+    slide_path, patch_size, patches_output_dir, mask_path, slide_id, max_patches_per_slide = opts[:6]
+    device, batch = opts[6:] if len(opts) > 6 else (None, 256)
     try:
         from openslide import OpenSlide
     except ImportError as e:
         raise SystemExit("openslide-python is required to read whole-slide images (pip install openslide-python); "
                          "sequoia-pub_amd.patchgen.extract_patches also accepts any object with OpenSlide's interface") from e
-    extract_patches(OpenSlide(slide_path), mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide)
+    extract_patches(OpenSlide(slide_path), mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide,
+                    device=device, batch=batch)
 
 
 def main(argv=None):
@@ -37,6 +42,10 @@ def main(argv=None):
     p.add_argument('--max_patches_per_slide', default=None, type=int)
     p.add_argument('--debug', default=0, type=int)
     p.add_argument('--parallel', default=1, type=int)
+    p.add_argument('--filter', default='host', choices=['host', 'device'],
+                   help="where the per-tile tissue / contrast filter runs: host = numpy as in the reference; device = sq_patch_filter on the GPU "
+                        "(always cuda:0; choose another card with HIP_VISIBLE_DEVICES)")
+    p.add_argument('--filter_batch', default=256, type=int, help="--filter device: candidate tiles read, uploaded and filtered at a time")
     args = p.parse_args(argv)
 
     slide_list = [s for s in os.listdir(args.wsi_path) if s.endswith('.svs') or s.endswith('.tiff')]
@@ -50,7 +59,14 @@ def main(argv=None):
     print(f"Found {len(slide_list)} slides")
     opts = [(os.path.join(args.wsi_path, s), (args.patch_size, args.patch_size), args.patch_path, args.mask_path,
              get_slide_id(s), args.max_patches_per_slide) for s in slide_list]
-    if args.parallel:
+    if args.filter == 'device':
+        if args.filter_batch < 1:
+            p.error("--filter_batch must be at least 1")
+        if args.parallel:
+            print("--filter device: slides are processed one after another in this process (--parallel is not used)")
+        for o in opts:
+            process(o + ("cuda:0", args.filter_batch))
+    elif args.parallel:
         with Pool(processes=4) as pool:
             pool.map(process, opts)
     else:

@@ -3,8 +3,14 @@
 pyramid level, 3 x dilation + 3 x erosion, seed-5 shuffled grid of level-0 tiles, per-tile tissue / contrast filter,
 one uint8 ``"{x}_{y}"`` dataset per kept tile in ``<patch_path>/<slide>/<slide>.hdf5`` + ``complete.txt``.
 
-This stage sits in front of the accelerated path and is bound by slide decoding, so it stays numpy; what is restated
-here are the scikit-image functions the reference calls (scikit-image is not installed in this image):
+This stage sits in front of the accelerated path.  Its per-tile filter in numpy (float64, one core) takes 8.5 ms per
+256 x 256 candidate tile and 28 ms per 512 x 512 one -- up to minutes per slide, against tens of milliseconds for everything
+behind it -- so the filter also has a device form: ``filter_patches`` (``sq_patch_filter``, csrc/patchfilter.hip) and
+``extract_patches(..., device=...)``, which keeps the slide mask, the visiting order and every written byte of the host
+path and takes 4.25 / 17.8 us per tile with the upload from pinned memory (tools/patch_filter_rate.py measures both
+filters side by side: profiles/patch_filter_rate.txt).  With it, what is left of the stage is reading the regions; slide
+decoding itself has not been measured, openslide is absent.
+What is restated here are the scikit-image functions the reference calls (scikit-image is not installed in this image):
 ``rgb2hsv`` (saturation channel), ``threshold_otsu`` (integer and float histograms), ``is_low_contrast`` -- pinned
 against scikit-image 0.18.3 itself by tests/golden/patchgen.npz (made with the image's conda interpreter,
 tests/golden/make_patchgen_golden.py).  ``binary_dilation`` / ``binary_erosion`` are scipy's, as in the reference.
@@ -13,10 +19,18 @@ A slide is anything with OpenSlide's interface subset (``level_dimensions``, ``r
 ``properties``); ``ArraySlide`` provides it over numpy arrays so the whole flow runs without openslide."""
 import os
 
+import ctypes
+
 import numpy as np
 from scipy.ndimage import binary_dilation, binary_erosion
 
-from . import store
+from . import _lib, store
+
+FILTER_MIN_DIM, FILTER_MAX_DIM = 8, 512            # SQ_PATCH_FILTER_MIN_DIM, SQ_PATCH_FILTER_MAX_DIM
+
+_vp, _sz, _i32, _f64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
+_lib.register_signature("sq_patch_filter_workspace_bytes", _sz, [_i32, _i32, _i32])
+_lib.register_signature("sq_patch_filter", _i32, [_vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
 
 
 # ---- scikit-image restatements ---------------------------------------------------------------------------------
@@ -116,10 +130,112 @@ def _resize_like_reference(patch, size):
     return np.asarray(Image.fromarray(np.ascontiguousarray(patch)).resize((int(size[0]), int(size[1]))))
 
 
+def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_threshold=0.05, return_stats=False,
+                   return_masks=False):
+    """The per-tile filter of extract_patches (patch_gen_hdf5.py:110-115) for a uint8 [n, H, W, 3] CUDA tensor, 8 <= H, W <=
+    512: bool [n], True where ``binary_dilation(get_mask_image(tile, rgb_min), iterations=3).sum() > background_threshold *
+    H * W and not is_low_contrast(tile, fraction_threshold)``.  ``return_stats``: also float64 [n, 8] = thr_R, thr_G, thr_B,
+    thr_S, mask count, dilated count, contrast ratio, 0 -- thresholds and counts equal to the host functions' bit for bit,
+    the ratio to 1e-12 (include/sequoia_hip.h).  ``return_masks``: also the bool [n, H, W] masks before and after the
+    dilation.  Asynchronous on the current stream; no CPU fallback."""
+    import torch
+    _lib.require_gpu()
+    if not (torch.is_tensor(patches_u8) and patches_u8.is_cuda):
+        raise _lib.SequoiaHipError("filter_patches needs a CUDA tensor (no CPU fallback)")
+    if patches_u8.dtype != torch.uint8 or patches_u8.dim() != 4 or patches_u8.shape[3] != 3:
+        raise ValueError(f"filter_patches takes uint8 [n, H, W, 3], got {patches_u8.dtype} {tuple(patches_u8.shape)}")
+    x = patches_u8.contiguous()
+    n, H, W, _ = x.shape
+    dev = x.device
+    L = _lib.lib()
+    need = L.sq_patch_filter_workspace_bytes(max(n, 1), H, W)       # refuses a bad size with the library's message
+    if need == 0:
+        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    stats = torch.empty(n, 8, dtype=torch.float64, device=dev) if return_stats else None
+    raw = torch.empty(n, H, W, dtype=torch.uint8, device=dev) if return_masks else None
+    dil = torch.empty(n, H, W, dtype=torch.uint8, device=dev) if return_masks else None
+    if n:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.sq_patch_filter(_lib.ptr(x), n, H, W, int(rgb_min), float(background_threshold), float(fraction_threshold),
+                                         _lib.ptr(keep), _lib.ptr(stats), _lib.ptr(raw), _lib.ptr(dil), _lib.ptr(ws), need,
+                                         _lib.stream_ptr(dev)))
+    out = (keep.bool(),)
+    if return_stats:
+        out += (stats,)
+    if return_masks:
+        out += (raw.bool(), dil.bool())
+    return out[0] if len(out) == 1 else out
+
+
+def _filtered_on_host(slide, candidates, size_read, patch_size, resize_factor, background_threshold):
+    """The kept tiles of `candidates` (visiting order) as ((x, y), uint8 array) pairs: patch_gen_hdf5.py:108-118, one region
+    read, filtered and, for a 40x slide, shrunk per step of the generator."""
+    for xy in candidates:
+        patch = np.asarray(slide.read_region(xy, 0, size_read))[:, :, :3]
+        tissue = binary_dilation(get_mask_image(patch), iterations=3)
+        if tissue.sum() > background_threshold * tissue.size and not is_low_contrast(patch):
+            if resize_factor != 1.0:
+                patch = _resize_like_reference(patch, patch_size)
+            yield xy, patch
+
+
+def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget, device, batch):
+    """The kept tiles of `candidates` (visiting order) as ((x, y), uint8 array) pairs, at most `budget` of them: regions are
+    read in chunks of `batch` into pinned memory, filtered on `device` and, for a 40x slide, shrunk there with the
+    Pillow-exact bicubic resize.  No chunk is read once the budget is met.  A read error ends the reading; the tiles read
+    before it are still filtered and yielded, then the error is raised -- unless the budget was met by then, where the
+    host loop would not have reached the failing read."""
+    import torch
+    from . import imgproc
+    pinned = torch.empty((batch, size_read[1], size_read[0], 3), dtype=torch.uint8).pin_memory()
+    view = pinned.numpy()
+    pos, error = 0, None
+    while pos < len(candidates) and budget > 0 and error is None:
+        chunk = candidates[pos:pos + batch]
+        pos += len(chunk)
+        k = 0
+        for xy in chunk:
+            try:
+                view[k] = np.asarray(slide.read_region(xy, 0, size_read))[:, :, :3]
+            except Exception as e:
+                error = e
+                break
+            k += 1
+        if k == 0:
+            break
+        tiles = pinned[:k].to(device, non_blocking=True)
+        kept = torch.nonzero(filter_patches(tiles, background_threshold=background_threshold)).flatten()[:budget]
+        if kept.numel():
+            out = tiles[kept]
+            if resize_factor != 1.0:
+                out = imgproc.resize_u8_pil(out, (int(patch_size[1]), int(patch_size[0])), "bicubic")
+            out = out.cpu().numpy()                      # also orders the next chunk's writes to `pinned` behind this upload
+            for i, j in enumerate(kept.tolist()):
+                yield chunk[j], out[i]
+            budget -= int(kept.numel())
+        else:
+            torch.cuda.current_stream(tiles.device).synchronize()
+    if error is not None and budget > 0:
+        raise error
+
+
 def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide=2000,
-                    background_threshold=0.2):
+                    background_threshold=0.2, device=None, batch=256):
     """patch_gen_hdf5.py:51-137 for an already opened slide.  Returns the number of patches written (None when the slide
-    had been completed before)."""
+    had been completed before).  ``device`` (a CUDA device) runs the per-tile filter and the 40x shrink there, `batch`
+    candidate tiles at a time (``filter_patches``, ``imgproc.resize_u8_pil``); the slide mask and the visiting order stay
+    on the host, and the datasets, ``mask.npy`` and ``complete.txt`` are the host path's byte for byte.  Up to batch - 1
+    more regions than the host path may be read near the cap; none of them is written."""
+    if device is not None:
+        if int(batch) < 1:
+            raise ValueError(f"batch={batch}: at least 1")
+        _lib.require_gpu()
+        factor = float(slide.properties.get('aperio.AppMag', 20)) / 20.0
+        region = (int(factor * patch_size[0]), int(factor * patch_size[1]))
+        if not all(FILTER_MIN_DIM <= v <= FILTER_MAX_DIM for v in region):
+            raise ValueError(f"device filter: regions of {region} pixels, every extent must be in {FILTER_MIN_DIM}..{FILTER_MAX_DIM}")
     patch_folder = os.path.join(patches_output_dir, slide_id)
     os.makedirs(patch_folder, exist_ok=True)
     mask_folder = os.path.join(mask_path, slide_id)
@@ -144,18 +260,19 @@ def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, 
             max_patches_per_slide = len(indices)
         np.random.seed(5)
         np.random.shuffle(indices)
-        for x, y in indices:
-            if n_written >= max_patches_per_slide:
+        candidates = ((x, y) for x, y in indices if mask[int(x / ratio_x), int(y / ratio_y)] == 1)      # looked up as they are visited
+        if device is None:
+            kept = _filtered_on_host(slide, candidates, size_read, patch_size, resize_factor, background_threshold)
+        else:
+            kept = _filtered_on_device(slide, list(candidates), size_read, patch_size, resize_factor, background_threshold,
+                                       max_patches_per_slide, device, int(batch))
+        while n_written < max_patches_per_slide:           # the host path reads no region once the cap is met
+            found = next(kept, None)
+            if found is None:
                 break
-            if mask[int(x / ratio_x), int(y / ratio_y)] != 1:
-                continue
-            patch = np.asarray(slide.read_region((x, y), 0, size_read))[:, :, :3]
-            tissue = binary_dilation(get_mask_image(patch), iterations=3)
-            if tissue.sum() > background_threshold * tissue.size and not is_low_contrast(patch):
-                if resize_factor != 1.0:
-                    patch = _resize_like_reference(patch, patch_size)
-                hdf.create_dataset(f"{x}_{y}", data=np.ascontiguousarray(patch))
-                n_written += 1
+            (x, y), patch = found
+            hdf.create_dataset(f"{x}_{y}", data=np.ascontiguousarray(patch))
+            n_written += 1
     except Exception as e:
         print("error with slide id {} patch {}".format(slide_id, n_written))
         print(e)
