@@ -508,6 +508,39 @@ int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, int rgb_min,
                     double contrast_fraction, uint8_t* keep, double* stats, uint8_t* mask_raw, uint8_t* mask_dilated,
                     void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Slide mask: the whole-slide tissue mask of patch generation and its closing
+ * (pre_processing/patch_gen_hdf5.py:25-50,69-72: get_mask_image on the lowest pyramid level, then
+ * binary_dilation(iterations=3) and binary_erosion(iterations=3)) for ONE uint8 image of any size.  Thresholds, saturation
+ * and mask are those of "Patch filter" above, operation for operation (one set of device functions serves both), so the
+ * four thresholds and every mask bit equal the host's.  The closing is `iterations` steps of the cross and then as many
+ * of its erosion, both with zeros outside the image (scipy's defaults: border_value = 0 -- an all-ones image comes back
+ * with a frame of `iterations` zeros).  The cross is symmetric, so mask and closing commute with transposing the image;
+ * `transpose` writes both byte outputs as [w, h], which is the [x, y] layout of the reference's mask.npy.
+ * Several passes over a grid of workgroups; whatever is combined across workgroups is an integer count or a min / max,
+ * so two calls give the same bytes.
+ *
+ *   sq_slide_mask_workspace_bytes : bytes of workspace for an h x w image (histograms, thresholds, a bit image of
+ *                          ceil(w / 32) words per row); 0 (and an sq_last_error message) for an extent outside
+ *                          1..SQ_SLIDE_MASK_MAX_DIM or h w > 2^30: pixel counts and the histograms' totals are kept in 32
+ *                          bits (counts x centre sums then stay below 2^53, as the Otsu walks need).
+ *   sq_slide_mask        : img_u8 uint8 [h, w, 3] (any alignment) -> mask_closed uint8 [h, w] (0 / 1), or [w, h] when
+ *                          `transpose` is not 0; mask_raw the same for the mask before the closing, or null; stats double
+ *                          [8] or null: thr_R, thr_G, thr_B, thr_S, raw count, closed count, min s, max s (all exact).
+ *                          iterations in 0..SQ_SLIDE_MASK_MAX_ITERATIONS (the reference: 3); with 0 the closed mask is the
+ *                          raw one.  Arguments are checked before anything is launched; the call clears the part of the
+ *                          workspace it needs cleared on `stream`, is asynchronous on it and never synchronises.
+ *                          The closing works on tiles of SQ_SLIDE_MASK_TILE_ROWS x SQ_SLIDE_MASK_TILE_COLS mask bits.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_SLIDE_MASK_MAX_DIM 32768
+#define SQ_SLIDE_MASK_MAX_ITERATIONS 8
+#define SQ_SLIDE_MASK_TILE_ROWS 64
+#define SQ_SLIDE_MASK_TILE_COLS 256
+size_t sq_slide_mask_workspace_bytes(int h, int w);
+int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, int iterations, int transpose,
+                  uint8_t* mask_raw, uint8_t* mask_closed, double* stats,
+                  void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

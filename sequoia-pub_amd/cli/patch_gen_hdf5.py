@@ -4,7 +4,8 @@ real ``.svs`` / ``.tiff`` slides needs openslide-python, exactly like the refere
 sequoia-pub_amd/patchgen.py.  ``--filter device`` runs the per-tile tissue / contrast filter (and the 40x shrink) on the
 GPU, ``--filter_batch`` candidate tiles at a time, with the same files as a result; the slides then go through the calling
 process one after another -- forked pool workers must not share a process's GPU state -- and ``--parallel`` only prints
-that."""
+that.  ``--slide_mask device`` (with ``--filter device``) also computes the whole-slide tissue mask and its closing on the
+GPU (``patchgen.slide_mask``); ``mask.npy`` stays the host's byte for byte."""
 import argparse
 import os
 from multiprocessing import Pool
@@ -20,14 +21,14 @@ def get_slide_id(slide_name):
 
 def process(opts):
     slide_path, patch_size, patches_output_dir, mask_path, slide_id, max_patches_per_slide = opts[:6]
-    device, batch = opts[6:] if len(opts) > 6 else (None, 256)
+    device, batch, slide_mask = opts[6:] if len(opts) > 6 else (None, 256, "host")
     try:
         from openslide import OpenSlide
     except ImportError as e:
         raise SystemExit("openslide-python is required to read whole-slide images (pip install openslide-python); "
                          "sequoia-pub_amd.patchgen.extract_patches also accepts any object with OpenSlide's interface") from e
     extract_patches(OpenSlide(slide_path), mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide,
-                    device=device, batch=batch)
+                    device=device, batch=batch, slide_mask=slide_mask)
 
 
 def main(argv=None):
@@ -46,7 +47,12 @@ def main(argv=None):
                    help="where the per-tile tissue / contrast filter runs: host = numpy as in the reference; device = sq_patch_filter on the GPU "
                         "(always cuda:0; choose another card with HIP_VISIBLE_DEVICES)")
     p.add_argument('--filter_batch', default=256, type=int, help="--filter device: candidate tiles read, uploaded and filtered at a time")
+    p.add_argument('--slide_mask', default='host', choices=['host', 'device'],
+                   help="where the whole-slide tissue mask and its closing are computed: host = numpy / scipy as in the reference; "
+                        "device = sq_slide_mask on the GPU (needs --filter device)")
     args = p.parse_args(argv)
+    if args.slide_mask == 'device' and args.filter != 'device':
+        p.error("--slide_mask device needs --filter device")
 
     slide_list = [s for s in os.listdir(args.wsi_path) if s.endswith('.svs') or s.endswith('.tiff')]
     if args.ref_file:
@@ -65,7 +71,7 @@ def main(argv=None):
         if args.parallel:
             print("--filter device: slides are processed one after another in this process (--parallel is not used)")
         for o in opts:
-            process(o + ("cuda:0", args.filter_batch))
+            process(o + ("cuda:0", args.filter_batch, args.slide_mask))
     elif args.parallel:
         with Pool(processes=4) as pool:
             pool.map(process, opts)

@@ -4,7 +4,9 @@
 // of sequoia-pub_amd/patchgen.py, which restates the scikit-image calls.  Every quantity except the luminance percentiles is
 // a chain of single IEEE double operations in numpy's order, so the thresholds, masks and counts are the host's bit for bit
 // as long as nothing is contracted into a fused multiply-add: the file is compiled under `#pragma clang fp contract(off)`
-// (repeated in the functions that depend on it); the double division is hipcc's correctly rounded one.
+// (repeated in the functions that depend on it); the double division is hipcc's correctly rounded one.  The saturation, the
+// histogram edges, the two Otsu walks and the staging of misaligned pixels live in patchfilter.h: the whole-slide mask
+// (slidemask.hip) computes with the same functions.
 //
 // Kernel: one workgroup of 512 threads per tile, three sweeps over the tile's bytes.  A sweep stages 4096 pixels at a time
 // in LDS with 16-byte global loads (tiles of an odd size start at every alignment: the loads are aligned down and the skew
@@ -26,14 +28,13 @@
 // sum in the last bit, so this one quantity is defined to 1e-12 and not to the bit (include/sequoia_hip.h).
 #include "../../include/sequoia_hip.h"
 #include "sq_common.h"
+#include "patchfilter.h"
 
 #pragma clang fp contract(off)      // the whole file: no product may be fused into a following sum
 
 namespace {
 
 constexpr int PF_THREADS = 512, PF_WAVES = PF_THREADS / 64;
-constexpr int PF_CHUNK_PX = 4096;                                  // pixels staged at a time
-constexpr int PF_STAGE_BYTES = 3 * PF_CHUNK_PX + 32;               // + skew (<= 15) + the tail of the last 16-byte line
 constexpr int PF_KEY_LOW_BITS = 11, PF_KEY_BINS = 1 << PF_KEY_LOW_BITS;      // keys < 2 550 001 < 2^22
 constexpr int PF_BYTE_COPIES = 4, PF_KEY_COPIES = 2, PF_S_COPIES = 4;
 constexpr int PF_LDS_MAX = 160 * 1024;
@@ -59,87 +60,6 @@ struct alignas(16) PfShared {
     uint32_t rank[4], rank_hi[4], rank_below[4], rank_slot[4], rank_key[4];
     uint32_t count_raw, count_dil, unused;
 };
-
-// skimage rgb2hsv's saturation of one pixel: c = fl(u8 * (1 / 255.0)), delta = max - min, s = delta / max, 0 where delta == 0
-__device__ __forceinline__ double pf_saturation(int r, int g, int b) {
-#pragma clang fp contract(off)
-    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
-    if (mx == mn) return 0.0;                  // u8 -> c is strictly increasing: delta == 0 exactly when the bytes are equal
-    const double k = 1.0 / 255.0;
-    const double v = (double)mx * k, lo = (double)mn * k;
-    return (v - lo) / v;
-}
-
-// np.linspace(s_min, s_max, 257)[i]
-__device__ __forceinline__ double pf_edge(int i, double s_min, double s_max, double step) {
-#pragma clang fp contract(off)
-    const double e = (double)i * step;
-    return i >= 256 ? s_max : e + s_min;
-}
-
-// np.histogram(s, 256, (s_min, s_max)): the bin with edge[i] <= s < edge[i + 1], the last one closed
-__device__ __forceinline__ int pf_bin(double s, double s_min, double s_max, double step, double inv_step) {
-#pragma clang fp contract(off)
-    int i = (int)((s - s_min) * inv_step);
-    i = min(max(i, 0), 255);
-    while (i > 0 && s < pf_edge(i, s_min, s_max, step)) --i;
-    while (i < 255 && s >= pf_edge(i + 1, s_min, s_max, step)) ++i;
-    return i;
-}
-
-// skimage threshold_otsu of a uint8 channel from its 256 counts: bins lo..hi, centres the integers, first maximum.
-// counts and counts * centre sum to integers below 2^53, so the backward sums are total - forward, exactly.
-__device__ int pf_otsu_u8(const uint32_t* cnt, int total) {
-#pragma clang fp contract(off)
-    int lo = 0, hi = 255;
-    while (lo < 255 && cnt[lo] == 0) ++lo;
-    while (hi > lo && cnt[hi] == 0) --hi;
-    if (lo == hi) return lo;
-    unsigned long long all_cs = 0;
-    for (int i = lo; i <= hi; ++i) all_cs += (unsigned long long)cnt[i] * i;
-    unsigned long long w1 = 0, cs1 = 0;
-    double best = -1.0;
-    int arg = lo;
-    for (int i = lo; i < hi; ++i) {
-        w1 += cnt[i];
-        cs1 += (unsigned long long)cnt[i] * i;
-        const double dw1 = (double)w1, dw2 = (double)((unsigned long long)total - w1);
-        const double m1 = (double)cs1 / dw1, m2 = (double)(all_cs - cs1) / dw2;
-        const double d = m1 - m2;
-        const double var = (dw1 * dw2) * (d * d);
-        if (var > best) best = var, arg = i;
-    }
-    return arg;
-}
-
-// threshold_otsu of the saturation from its 256 counts (one lane): centres (edge[i] + edge[i + 1]) / 2, cumulative sums of
-// counts * centre in np.cumsum's order
-__device__ double pf_otsu_s(const uint32_t* cnt, int total, double s_min, double s_max, double* cs2) {
-#pragma clang fp contract(off)
-    const double step = (s_max - s_min) / 256.0;
-    double acc = 0.0;
-    for (int i = 255; i >= 0; --i) {
-        const double c = (pf_edge(i, s_min, s_max, step) + pf_edge(i + 1, s_min, s_max, step)) / 2.0;
-        const double t = (double)cnt[i] * c;
-        acc = i == 255 ? t : acc + t;
-        cs2[i] = acc;
-    }
-    unsigned long long w1 = 0;
-    double best = -1.0;
-    int arg = 0;
-    acc = 0.0;
-    for (int i = 0; i < 255; ++i) {
-        const double c = (pf_edge(i, s_min, s_max, step) + pf_edge(i + 1, s_min, s_max, step)) / 2.0;
-        const double t = (double)cnt[i] * c;
-        acc = i == 0 ? t : acc + t;
-        w1 += cnt[i];
-        const double dw1 = (double)w1, dw2 = (double)((unsigned long long)total - w1);
-        const double d = acc / dw1 - cs2[i + 1] / dw2;
-        const double var = (dw1 * dw2) * (d * d);
-        if (var > best) best = var, arg = i;
-    }
-    return (pf_edge(arg, s_min, s_max, step) + pf_edge(arg + 1, s_min, s_max, step)) / 2.0;
-}
 
 // np.percentile(.., q)'s virtual index n q + (1 - q) - 1 (method "linear"): lower rank and weight of the upper one
 __device__ __forceinline__ void pf_rank(int n, double q, uint32_t* lower, double* gamma) {
@@ -221,23 +141,7 @@ __device__ __forceinline__ void pf_sweep(const PfArgs& a, int img, uint8_t* stag
     const uint8_t* const send = a.src + (size_t)a.n * hw * 3;
     for (int base = 0; base < hw; base += PF_CHUNK_PX) {
         const int npx = min(PF_CHUNK_PX, hw - base);
-        const uint8_t* const p0 = simg + (size_t)base * 3;
-        const uint8_t* const lo = (const uint8_t*)((uintptr_t)p0 & ~(uintptr_t)15);
-        const int skew = (int)(p0 - lo);
-        const int lines = (skew + npx * 3 + 15) >> 4;          // <= (15 + 12288 + 15) / 16 = 769 lines: 12304 <= PF_STAGE_BYTES
-        __syncthreads();                                       // the previous chunk has been read
-        for (int c = tid; c < lines; c += PF_THREADS) {
-            const uint8_t* p = lo + (size_t)c * 16;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (p >= a.src && p + 16 <= send) {
-                v = *(const u32x4*)p;
-            } else {                                           // the 16-byte lines at either end of the whole buffer
-                for (int b = 0; b < 16; ++b)
-                    if (p + b >= a.src && p + b < send) v[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
-            }
-            *(u32x4*)(stage + c * 16) = v;
-        }
-        __syncthreads();
+        const int skew = pf_stage<PF_THREADS>(a.src, send, simg + (size_t)base * 3, npx, stage);
         const uint8_t* const s = stage + skew;
         for (int i = tid; i < npx; i += PF_THREADS) f(base + i, (int)s[3 * i], (int)s[3 * i + 1], (int)s[3 * i + 2]);
     }

@@ -8,8 +8,11 @@ This stage sits in front of the accelerated path.  Its per-tile filter in numpy 
 behind it -- so the filter also has a device form: ``filter_patches`` (``sq_patch_filter``, csrc/patchfilter.hip) and
 ``extract_patches(..., device=...)``, which keeps the slide mask, the visiting order and every written byte of the host
 path and takes 4.25 / 17.8 us per tile with the upload from pinned memory (tools/patch_filter_rate.py measures both
-filters side by side: profiles/patch_filter_rate.txt).  With it, what is left of the stage is reading the regions; slide
-decoding itself has not been measured, openslide is absent.
+filters side by side: profiles/patch_filter_rate.txt).  The whole-slide mask in front of it (``get_mask`` on the lowest
+level and the closing: seconds per slide in numpy / scipy on one core) has a device form as well: ``slide_mask``
+(``sq_slide_mask``, csrc/slidemask.hip) and ``extract_patches(..., device=..., slide_mask="device")``, every mask bit and
+the bytes of ``mask.npy`` the host's (tools/slide_mask_rate.py, profiles/slide_mask_rate.txt).  With both, what is left of
+the stage is reading the regions; slide decoding itself has not been measured, openslide is absent.
 What is restated here are the scikit-image functions the reference calls (scikit-image is not installed in this image):
 ``rgb2hsv`` (saturation channel), ``threshold_otsu`` (integer and float histograms), ``is_low_contrast`` -- pinned
 against scikit-image 0.18.3 itself by tests/golden/patchgen.npz (made with the image's conda interpreter,
@@ -27,10 +30,15 @@ from scipy.ndimage import binary_dilation, binary_erosion
 from . import _lib, store
 
 FILTER_MIN_DIM, FILTER_MAX_DIM = 8, 512            # SQ_PATCH_FILTER_MIN_DIM, SQ_PATCH_FILTER_MAX_DIM
+SLIDE_MASK_MAX_DIM, SLIDE_MASK_MAX_PIXELS = 32768, 1 << 30      # SQ_SLIDE_MASK_MAX_DIM; h w <= 2^30
+SLIDE_MASK_MAX_ITERATIONS = 8                      # SQ_SLIDE_MASK_MAX_ITERATIONS
+SLIDE_MASK_TILE = (64, 256)                        # SQ_SLIDE_MASK_TILE_ROWS, SQ_SLIDE_MASK_TILE_COLS: the closing kernel's tile
 
 _vp, _sz, _i32, _f64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _lib.register_signature("sq_patch_filter_workspace_bytes", _sz, [_i32, _i32, _i32])
 _lib.register_signature("sq_patch_filter", _i32, [_vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
+_lib.register_signature("sq_slide_mask_workspace_bytes", _sz, [_i32, _i32])
+_lib.register_signature("sq_slide_mask", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp])
 
 
 # ---- scikit-image restatements ---------------------------------------------------------------------------------
@@ -169,6 +177,61 @@ def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_th
     return out[0] if len(out) == 1 else out
 
 
+def slide_mask(img_u8, rgb_min=50, iterations=3, transpose=False, return_raw=False, return_stats=False):
+    """The whole-slide mask of extract_patches (patch_gen_hdf5.py:25-50,69-72) for ONE uint8 [H, W, 3] CUDA tensor of any
+    size up to 32768 x 32768 and 2^30 pixels: bool [H, W] = ``binary_erosion(binary_dilation(get_mask_image(img, rgb_min),
+    iterations=iterations), iterations=iterations)``, every bit the host's; ``iterations`` in 0..8, 0 leaves the mask as it
+    is.  ``transpose``: the results as C-contiguous [W, H], equal to the host's on the transposed image (the layout of the
+    reference's mask.npy) without a transposing copy.  ``return_raw``: also the mask before the closing.  ``return_stats``:
+    also float64 [8] = thr_R, thr_G, thr_B, thr_S, raw count, closed count, min and max of the saturation, all exact.
+    Asynchronous on the current stream; no CPU fallback."""
+    import torch
+    _lib.require_gpu()
+    if not (torch.is_tensor(img_u8) and img_u8.is_cuda):
+        raise _lib.SequoiaHipError("slide_mask needs a CUDA tensor (no CPU fallback)")
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise ValueError(f"slide_mask takes uint8 [H, W, 3], got {img_u8.dtype} {tuple(img_u8.shape)}")
+    x = img_u8.contiguous()
+    H, W, _ = x.shape
+    dev = x.device
+    L = _lib.lib()
+    need = L.sq_slide_mask_workspace_bytes(H, W)                    # refuses a bad size with the library's message
+    if need == 0:
+        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    shape = (W, H) if transpose else (H, W)
+    closed = torch.empty(shape, dtype=torch.uint8, device=dev)
+    raw = torch.empty(shape, dtype=torch.uint8, device=dev) if return_raw else None
+    stats = torch.empty(8, dtype=torch.float64, device=dev) if return_stats else None
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.sq_slide_mask(_lib.ptr(x), H, W, int(rgb_min), int(iterations), int(bool(transpose)), _lib.ptr(raw),
+                                   _lib.ptr(closed), _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+    out = (closed.view(torch.bool),)
+    if return_raw:
+        out += (raw.view(torch.bool),)
+    if return_stats:
+        out += (stats,)
+    return out[0] if len(out) == 1 else out
+
+
+def _mask_level_size(slide):
+    """(level, (width, height)) of the image get_mask reads."""
+    level = len(slide.level_dimensions) - 1
+    return level, tuple(int(v) for v in slide.level_dimensions[level])
+
+
+def _closed_mask_on_device(slide, device):
+    """get_mask + the closing of extract_patches on `device`: the level image as get_mask reads it, uploaded through pinned
+    memory, ``slide_mask(transpose=True)``, and the bool [W, H] array back on the host."""
+    import torch
+    level, size = _mask_level_size(slide)
+    img = np.asarray(slide.read_region((0, 0), level, size))[:, :, :3]
+    pinned = torch.empty(img.shape, dtype=torch.uint8).pin_memory()
+    pinned.numpy()[...] = img
+    mask = slide_mask(pinned.to(device, non_blocking=True), transpose=True)
+    return mask.cpu().numpy(), level
+
+
 def _filtered_on_host(slide, candidates, size_read, patch_size, resize_factor, background_threshold):
     """The kept tiles of `candidates` (visiting order) as ((x, y), uint8 array) pairs: patch_gen_hdf5.py:108-118, one region
     read, filtered and, for a 40x slide, shrunk per step of the generator."""
@@ -222,12 +285,19 @@ def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor,
 
 
 def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide=2000,
-                    background_threshold=0.2, device=None, batch=256):
+                    background_threshold=0.2, device=None, batch=256, slide_mask="host"):
     """patch_gen_hdf5.py:51-137 for an already opened slide.  Returns the number of patches written (None when the slide
     had been completed before).  ``device`` (a CUDA device) runs the per-tile filter and the 40x shrink there, `batch`
     candidate tiles at a time (``filter_patches``, ``imgproc.resize_u8_pil``); the slide mask and the visiting order stay
     on the host, and the datasets, ``mask.npy`` and ``complete.txt`` are the host path's byte for byte.  Up to batch - 1
-    more regions than the host path may be read near the cap; none of them is written."""
+    more regions than the host path may be read near the cap; none of them is written.  ``slide_mask="device"`` (needs
+    ``device``) also computes the slide mask and its closing there (``slide_mask``, ``sq_slide_mask``) from the same level
+    image; ``mask.npy`` keeps the host path's header and bytes.  The level image must be within the library's bounds
+    (extents up to 32768, 2^30 pixels)."""
+    if slide_mask not in ("host", "device"):
+        raise ValueError(f"slide_mask={slide_mask!r}: 'host' or 'device'")
+    if slide_mask == "device" and device is None:
+        raise ValueError("slide_mask='device' needs device=")
     if device is not None:
         if int(batch) < 1:
             raise ValueError(f"batch={batch}: at least 1")
@@ -236,6 +306,11 @@ def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, 
         region = (int(factor * patch_size[0]), int(factor * patch_size[1]))
         if not all(FILTER_MIN_DIM <= v <= FILTER_MAX_DIM for v in region):
             raise ValueError(f"device filter: regions of {region} pixels, every extent must be in {FILTER_MIN_DIM}..{FILTER_MAX_DIM}")
+        if slide_mask == "device":
+            level, (lw, lh) = _mask_level_size(slide)
+            if not (1 <= lw <= SLIDE_MASK_MAX_DIM and 1 <= lh <= SLIDE_MASK_MAX_DIM and lw * lh <= SLIDE_MASK_MAX_PIXELS):
+                raise ValueError(f"device slide mask: level {level} is {lw} x {lh} pixels, every extent must be in 1..{SLIDE_MASK_MAX_DIM} "
+                                 f"and the image at most 2^30 pixels")
     patch_folder = os.path.join(patches_output_dir, slide_id)
     os.makedirs(patch_folder, exist_ok=True)
     mask_folder = os.path.join(mask_path, slide_id)
@@ -246,8 +321,11 @@ def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, 
     hdf = store.File(os.path.join(patch_folder, f"{slide_id}.hdf5"), 'w')
     n_written = 0
     try:          # patch_gen_hdf5.py:78,135-137: one unreadable slide prints its error and must not end the whole run
-        mask, mask_level = get_mask(slide)
-        mask = binary_erosion(binary_dilation(mask, iterations=3), iterations=3)
+        if slide_mask == "device":
+            mask, mask_level = _closed_mask_on_device(slide, device)
+        else:
+            mask, mask_level = get_mask(slide)
+            mask = binary_erosion(binary_dilation(mask, iterations=3), iterations=3)
         np.save(os.path.join(mask_folder, "mask.npy"), mask)
         ratio_x = slide.level_dimensions[0][0] / slide.level_dimensions[mask_level][0]
         ratio_y = slide.level_dimensions[0][1] / slide.level_dimensions[mask_level][1]
