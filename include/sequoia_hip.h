@@ -541,6 +541,48 @@ int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, int iteratio
                   uint8_t* mask_raw, uint8_t* mask_closed, double* stats,
                   void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Tile grid: which grid tiles of a slide the spatial maps read
+ * (spatial_vis/visualize.py:174-205, restated on the host by cli/visualize.py valid_tiles: a double loop over the grid,
+ * scipy's binary_dilation(iterations=3) of a window of the tissue mask per tile, its count against half the window).
+ * The mask is the array of mask.npy: uint8 [mask_w, mask_h], C-contiguous, indexed [x, y], any non-zero byte is tissue.
+ * For grid tile (i, j), 0 <= i < n_col, 0 <= j < n_row, with the read size p (patch_size_resized) and the downsample
+ * factor ds of the mask:
+ *   origin              col = i p, row = j p in level-0 pixels; the host takes n_col = len(range(0, slide_w - p, p)) and
+ *                       n_row likewise, the caller passes both.
+ *   window              c = col / ds, r = row / ds in integer division -- equal to the host's int(col / downsample_factor),
+ *                       a double division, for every extent below 2^31 (the quotient's rounding error stays below 1 / ds);
+ *                       x in [c, min(c + pm, mask_w)), y in [r, min(r + pm, mask_h)): clipped as numpy slicing clips it, on
+ *                       either axis, and EMPTY for pm = 0 or an origin beyond the mask (the two axes of a pyramid level
+ *                       may have been truncated differently).
+ *   dilation            `iterations` steps of the cross INSIDE the window, zeros outside it (scipy's border_value = 0 on
+ *                       the slice): a mask pixel next to the window does not enter.  Inside a rectangle that is "L1
+ *                       distance <= iterations to a set pixel of the window".  The cross is symmetric, so the window is
+ *                       walked in the mask's [x, y] layout, untransposed.
+ *   size, count         the clipped window's element count; the set pixels after the dilation.
+ *   valid               (double)count >= fl(threshold (double)size): with threshold 0.5 a tie 2 count == size is valid, and
+ *                       an empty window is valid (0 >= 0, as scipy and the host loop have it).
+ *
+ *   sq_tile_grid_valid   : mask_u8 (any alignment) -> valid uint8 [n_col, n_row] (0 / 1; n_col is the outer axis, the host's
+ *                          visiting order); counts and sizes int32 [n_col, n_row], each may be null.  mask_w, mask_h in
+ *                          1..SQ_TILE_GRID_MAX_DIM and mask_w mask_h <= 2^30 (the slide mask's bounds; addresses are formed
+ *                          in 64 bits); n_col, n_row >= 1, n_col n_row <= 2^30 and every tile origin below 2^31; p, ds >= 1;
+ *                          pm in 0..SQ_TILE_GRID_MAX_WINDOW (512 = a 40x read with a full-resolution mask; the cap keeps a
+ *                          window's bits in LDS, as the patch filter's does); iterations in
+ *                          0..SQ_TILE_GRID_MAX_ITERATIONS (the reference: 3, threshold 0.5).  One launch: windows up to
+ *                          SQ_TILE_GRID_PACKED_MAX_WINDOW take the packed route (a window row is one 32- or 64-bit word of
+ *                          a lane, 8 to 1 windows per wave), wider ones one workgroup each with the bits in LDS.  All
+ *                          arguments are checked before the launch; asynchronous on `stream`, never synchronises; every
+ *                          window is independent and every sum an integer, so two calls give the same bytes.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_TILE_GRID_MAX_DIM 32768
+#define SQ_TILE_GRID_MAX_WINDOW 512
+#define SQ_TILE_GRID_PACKED_MAX_WINDOW 64
+#define SQ_TILE_GRID_MAX_ITERATIONS 8
+int sq_tile_grid_valid(const uint8_t* mask_u8, int mask_w, int mask_h, int n_col, int n_row, int p, int ds, int pm,
+                       int iterations, double threshold, uint8_t* valid, int32_t* counts, int32_t* sizes,
+                       sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ openslide when it is installed, or given as an ``.npy`` RGB array (``patchgen.Ar
 resized to 256 x 256 by default; ``--resnet_input reference`` gives the extractor what the reference's
 ``transforms.Resize((256, 265))`` gives it (spatial_vis/visualize.py:212-216): EVERY tile, 256 x 256 ones included, resized
 to height 256, width 265 with PIL's BILINEAR filter, byte for byte (``imgproc.resize_u8_pil``; ``--resize`` does not apply
-to it).  UNI tiles go to 224 as in the reference."""
+to it).  UNI tiles go to 224 as in the reference.  ``--valid_tiles device`` decides which grid tiles are read in one kernel launch
+(``valid_tiles_device``) instead of the scipy loop over every tile; the frame and the CSV are the same."""
 import argparse
 import os
 import pickle
@@ -57,6 +58,31 @@ def valid_tiles(mask, slide_dims, patch_size_resized):
         df['xcoord_tf'] = ((df['xcoord'] - min(df['xcoord'])) / patch_size_resized).astype(int)
         df['ycoord_tf'] = ((df['ycoord'] - min(df['ycoord'])) / patch_size_resized).astype(int)
     return df
+
+
+def valid_tiles_device(mask, slide_dims, patch_size_resized, device):
+    """``valid_tiles`` with the grid decided on `device` (``patchgen.valid_tile_grid``, ``sq_tile_grid_valid``): the same
+    DataFrame -- columns, dtypes, index and values, the empty frame included.  ``mask``: the numpy array of mask.npy, any
+    dtype (``mask != 0`` goes up as uint8 through pinned memory), or a CUDA tensor (e.g. what
+    ``patchgen.slide_mask(transpose=True)`` just made: it need not leave the device).  One download: the indices of the
+    valid tiles, whose row-major order is the host loop's visiting order."""
+    from .. import patchgen
+    p = int(patch_size_resized)
+    patchgen.tile_grid_geometry(tuple(mask.shape), slide_dims, p)          # refuses before anything is uploaded
+    if torch.is_tensor(mask):
+        m = mask.to(device)
+        if m.dtype not in (torch.bool, torch.uint8):
+            m = m != 0
+    else:
+        host = np.asarray(mask)
+        pinned = torch.empty(host.shape, dtype=torch.uint8).pin_memory()
+        np.not_equal(host, 0, out=pinned.numpy().view(np.bool_))
+        m = pinned.to(device, non_blocking=True)
+    ij = torch.nonzero(patchgen.valid_tile_grid(m, slide_dims, p, iterations=3, threshold=BACKGROUND_THRESHOLD)).cpu().numpy()
+    if not len(ij):
+        return pd.DataFrame([], columns=['xcoord', 'ycoord'])
+    i, j = ij[:, 0].astype(np.int64), ij[:, 1].astype(np.int64)
+    return pd.DataFrame({'xcoord': i * p, 'ycoord': j * p, 'xcoord_tf': i - i.min(), 'ycoord_tf': j - j.min()})
 
 
 TILE_CHUNK = 512          # tiles per read -> upload -> resize -> embed round: host and device staging stay a few hundred MB
@@ -137,7 +163,7 @@ def build_model(model_type, input_dim, n_genes, device, compute_dtype):
     return HE2RNA(input_dim=input_dim, layers=[256, 256], ks=[1, 2, 5, 10, 20, 50, 100], output_dim=n_genes, device=str(device))
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description='Getting features')
     p.add_argument('--study', type=str, help='cancer study abbreviation, lowercase')
     p.add_argument('--project', type=str, help='name of project (spatial_GBM_pred, TCGA-GBM, PESO, Breast-ST)')
@@ -162,7 +188,14 @@ def main(argv=None):
     p.add_argument('--resnet_input', default='256x256', choices=['256x256', 'reference'],
                    help='--feat_type resnet: 256x256 = square tiles (default); reference = every tile resized to height 256, width 265 as '
                         'the reference\'s Resize((256, 265)) does, byte for byte PIL\'s BILINEAR resize whatever --resize says')
-    args = p.parse_args(argv)
+    p.add_argument('--valid_tiles', default='host', choices=['host', 'device'],
+                   help='where the grid of valid tiles is decided: host = the scipy loop over every grid tile (default); device = one kernel '
+                        'launch on the rank\'s device (patchgen.valid_tile_grid), the same frame')
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     assert args.feat_type in ['resnet', 'uni'] and args.model_type in ['vit', 'vis', 'he2rna']
     # under torchrun: ONE slide over the ranks -- tile chunks for the feature cache, window batches and tile chunks for the
     # aggregator (spatial.sliding_window_all_genes_sharded); rank 0 writes the CSV.  Alone: cuda:0 as in the reference.
@@ -186,7 +219,10 @@ def main(argv=None):
     slide = open_slide(os.path.join(slide_dir, args.wsi_file_name))
     resize_factor = args.resize_factor if args.resize_factor is not None else float(slide.properties.get('aperio.AppMag', 20)) / 20.0
     patch_size_resized = int(resize_factor * patch_size)
-    df = valid_tiles(mask, slide.dimensions, patch_size_resized)
+    if args.valid_tiles == 'device':                    # under torchrun every rank computes it: deterministic, cheaper than a broadcast
+        df = valid_tiles_device(mask, slide.dimensions, patch_size_resized, device)
+    else:
+        df = valid_tiles(mask, slide.dimensions, patch_size_resized)
     print('Got dataframe of valid tiles')
 
     # ---- feature cache: every valid tile embedded once

@@ -33,12 +33,15 @@ FILTER_MIN_DIM, FILTER_MAX_DIM = 8, 512            # SQ_PATCH_FILTER_MIN_DIM, SQ
 SLIDE_MASK_MAX_DIM, SLIDE_MASK_MAX_PIXELS = 32768, 1 << 30      # SQ_SLIDE_MASK_MAX_DIM; h w <= 2^30
 SLIDE_MASK_MAX_ITERATIONS = 8                      # SQ_SLIDE_MASK_MAX_ITERATIONS
 SLIDE_MASK_TILE = (64, 256)                        # SQ_SLIDE_MASK_TILE_ROWS, SQ_SLIDE_MASK_TILE_COLS: the closing kernel's tile
+TILE_GRID_MAX_WINDOW, TILE_GRID_PACKED_MAX_WINDOW = 512, 64     # SQ_TILE_GRID_MAX_WINDOW, SQ_TILE_GRID_PACKED_MAX_WINDOW
+TILE_GRID_MAX_ITERATIONS = 8                       # SQ_TILE_GRID_MAX_ITERATIONS
 
 _vp, _sz, _i32, _f64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
 _lib.register_signature("sq_patch_filter_workspace_bytes", _sz, [_i32, _i32, _i32])
 _lib.register_signature("sq_patch_filter", _i32, [_vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
 _lib.register_signature("sq_slide_mask_workspace_bytes", _sz, [_i32, _i32])
 _lib.register_signature("sq_slide_mask", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp])
+_lib.register_signature("sq_tile_grid_valid", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp])
 
 
 # ---- scikit-image restatements ---------------------------------------------------------------------------------
@@ -212,6 +215,60 @@ def slide_mask(img_u8, rgb_min=50, iterations=3, transpose=False, return_raw=Fal
     if return_stats:
         out += (stats,)
     return out[0] if len(out) == 1 else out
+
+
+def tile_grid_geometry(mask_shape, slide_dims, patch_size_resized):
+    """(downsample_factor, patch_size_in_mask, n_col, n_row) of the valid-tile grid as cli.visualize.valid_tiles derives them
+    (visualize.py:181-189) from the [mask_w, mask_h] shape of the mask, the slide's level-0 (width, height) and the read
+    size.  ValueError for what the device form does not take: a factor below 1 (a mask wider than the slide, where the host
+    divides by zero) and a window above 512."""
+    p = int(patch_size_resized)
+    if p < 1:
+        raise ValueError(f"patch_size_resized={patch_size_resized}: at least 1")
+    if len(mask_shape) != 2 or int(mask_shape[0]) < 1 or int(mask_shape[1]) < 1:
+        raise ValueError(f"valid-tile grid: a mask of shape {tuple(mask_shape)}, [mask_w, mask_h] with both extents at least 1 is needed")
+    downsample_factor = int(slide_dims[0] / mask_shape[0])
+    if downsample_factor < 1:
+        raise ValueError(f"valid-tile grid: slide width {slide_dims[0]} over mask width {mask_shape[0]} gives a downsample factor of "
+                         f"{downsample_factor}, below 1")
+    patch_size_in_mask = int(p / downsample_factor)
+    if patch_size_in_mask > TILE_GRID_MAX_WINDOW:
+        raise ValueError(f"valid-tile grid: a window of {patch_size_in_mask} mask pixels (read size {p}, downsample factor "
+                         f"{downsample_factor}): at most {TILE_GRID_MAX_WINDOW}")
+    n_col, n_row = len(range(0, int(slide_dims[0]) - p, p)), len(range(0, int(slide_dims[1]) - p, p))
+    return downsample_factor, patch_size_in_mask, n_col, n_row
+
+
+def valid_tile_grid(mask, slide_dims, patch_size_resized, iterations=3, threshold=0.5, return_counts=False):
+    """The valid-tile grid of the spatial maps (spatial_vis/visualize.py:174-205; cli.visualize.valid_tiles on the host) for a
+    bool or uint8 CUDA tensor ``mask`` [mask_w, mask_h] in the layout of mask.npy (indexed [x, y], any non-zero byte is
+    tissue): bool [n_col, n_row], True where ``binary_dilation(window, iterations=iterations).sum() >= threshold *
+    window.size`` for the tile's window ``mask[c:c + pm, r:r + pm]`` -- clipped as numpy clips it, possibly empty (then
+    valid), nothing from outside the window entering the dilation.  Row-major order of the result is the host loop's visiting
+    order.  ``return_counts``: also the int32 [n_col, n_row] dilated counts and clipped window sizes.  The downsample factor
+    and the window come from ``tile_grid_geometry`` exactly as the host derives them; a factor below 1 or a window above 512
+    is a ValueError.  ``iterations`` in 0..8 (0: the window as it is).  An empty grid returns an empty tensor without a launch.
+    Asynchronous on the current stream; no CPU fallback."""
+    import torch
+    shape = tuple(mask.shape) if hasattr(mask, "shape") else ()
+    ds, pm, n_col, n_row = tile_grid_geometry(shape, slide_dims, patch_size_resized)
+    _lib.require_gpu()
+    if not (torch.is_tensor(mask) and mask.is_cuda):
+        raise _lib.SequoiaHipError("valid_tile_grid needs a CUDA tensor (no CPU fallback)")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"valid_tile_grid takes a bool or uint8 mask [mask_w, mask_h], got {mask.dtype}")
+    x = mask.contiguous()
+    x = x.view(torch.uint8) if x.dtype == torch.bool else x
+    dev = x.device
+    valid = torch.empty((n_col, n_row), dtype=torch.uint8, device=dev)
+    counts = torch.empty((n_col, n_row), dtype=torch.int32, device=dev) if return_counts else None
+    sizes = torch.empty((n_col, n_row), dtype=torch.int32, device=dev) if return_counts else None
+    if n_col and n_row:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().sq_tile_grid_valid(_lib.ptr(x), x.shape[0], x.shape[1], n_col, n_row, int(patch_size_resized), ds, pm,
+                                                     int(iterations), float(threshold), _lib.ptr(valid), _lib.ptr(counts), _lib.ptr(sizes),
+                                                     _lib.stream_ptr(dev)))
+    return (valid.view(torch.bool), counts, sizes) if return_counts else valid.view(torch.bool)
 
 
 def _mask_level_size(slide):
