@@ -583,6 +583,52 @@ int sq_tile_grid_valid(const uint8_t* mask_u8, int mask_w, int mask_h, int n_col
                        int iterations, double threshold, uint8_t* valid, int32_t* counts, int32_t* sizes,
                        sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Map statistics: what spatial_vis/gbm_celltype_analysis.py and the percentile step of spatial_vis/get_emd.py compute
+ * from a slide's prediction table (f32 [n_tiles, G], as spatial.sliding_window_all_genes leaves it on the device).
+ * Tables are row-major with a leading dimension `ld` (elements); `cols` is a device list of int32 column indices in
+ * [0, ld), NULL = columns 0..C-1 (C <= ld): gene columns are read in place.  n <= SQ_MAP_MAX_ROWS tiles.  Every argument
+ * is checked before the first launch; the calls are asynchronous on `stream` and never synchronise; no atomics, every
+ * sum in a fixed order: two calls give the same bytes.
+ *
+ *   sq_map_percentile   : score2percentile of gbm_celltype_analysis.py:12-16,107 and get_emd.py:21-25,172,175 for every
+ *                         element of every column: scipy.stats.percentileofscore(column, x) with the default kind='rank',
+ *                         (left + right + (left < right)) * (50.0 / n) with left = #(column < x), right = #(column <= x) as
+ *                         integers and ONE f64 product; `scale` is the caller's 50.0 / n.  Bit-equal to scipy.  values is
+ *                         f32 (values_f64 = 0) or f64 (1); out f64 [n, C].  Comparisons are IEEE (-0.0 == 0.0, +-inf
+ *                         ordered).  A column holding a NaN comes back all NaN (nan_policy='propagate').  argmax, when
+ *                         not NULL, is int32 [n]: the first column holding the row's largest percentile, NaN skipped, -1
+ *                         for a row of NaN (df[[... '_perc']].idxmax(axis=1) of :109, ties to the earlier column).
+ *                         1 <= n <= SQ_MAP_MAX_ROWS, C >= 1.  A column is cut into chunks of sq_map_rank_chunk_rows()
+ *                         rows; one workgroup sorts a chunk's keys in LDS, every element is then searched in every sorted
+ *                         chunk of its column (counts add over chunks).
+ *   sq_map_category_means : df[genes of a category].mean(axis=1) of :105.  pred f32 [n, ld]; members int32 [offsets[n_cat]]
+ *                         gene (column) indices, category c owns members[offsets[c] .. offsets[c + 1]) (both on the device,
+ *                         indices in [0, ld) -- the caller validates them); out f64 [n, n_cat] = the f64 sum of the
+ *                         members in list order divided by their count, NaN for an empty category (as pandas).
+ *                         1 <= n <= SQ_MAP_MAX_ROWS, n_cat >= 1, n_members >= 0.
+ *   sq_map_gene_corr    : df[all_genes].corr() of :75 (Pearson) for K columns of pred f32 [n, ld]: out f64 [K, K].  Column
+ *                         means in f64, C = Z^T Z of the centred columns over the n rows on v_mfma_f64_16x16x4_f64 (blocks on
+ *                         and above the diagonal only, the rows cut into slices whose partials are added in slice order),
+ *                         out[i][j] = C_ij / (sqrt(C_ii) sqrt(C_jj)) clipped to [-1, 1] and stored at [i][j] and [j][i]
+ *                         (bit-symmetric); the diagonal is exactly 1.0.  A constant column (every value equal to the
+ *                         first) gives NaN in its row and column, the diagonal included (as pandas).  A NaN VALUE makes
+ *                         its column's row and column NaN (pandas would drop the pair's rows: not done here, the tables
+ *                         of :72 have had their NaN rows dropped).  2 <= n <= SQ_MAP_MAX_ROWS, 1 <= K <= SQ_MAP_MAX_CORR_COLS.
+ *   The two *_workspace_bytes functions return 0 for a refused shape.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_MAP_MAX_ROWS 262144
+#define SQ_MAP_MAX_CORR_COLS 32768
+int sq_map_rank_chunk_rows(void);
+size_t sq_map_percentile_workspace_bytes(int n, int C, int values_f64);
+int sq_map_percentile(const void* values, int values_f64, int n, int ld, const int32_t* cols, int C, double scale,
+                      double* out, int32_t* argmax, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+int sq_map_category_means(const float* pred, int n, int ld, const int32_t* members, int n_members, const int32_t* offsets,
+                          int n_cat, double* out, sq_stream_t stream);
+size_t sq_map_gene_corr_workspace_bytes(int n, int K);
+int sq_map_gene_corr(const float* pred, int n, int ld, const int32_t* cols, int K, double* out, void* workspace,
+                     size_t workspace_bytes, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
