@@ -31,6 +31,44 @@ def _up(n, m):
     return (n + m - 1) // m * m
 
 
+def _layer_stack(xt, input_dim, params, ws, p_drop=0.0, dst=None):
+    """The stack of 1x1 convolutions (he2rna.py:101-106) on token-major rows xt f32 [M, C], of which the last `input_dim`
+    channels go in (:102): ``sq_linear`` per layer, bias and ReLU fused on all layers but the last, dropout behind every hidden
+    layer when p_drop > 0 (one torch.rand [M, ld] per hidden layer, in layer order).  Every activation / weight is zero-padded to
+    a multiple of 8 columns: the GEMM engine wants 16-byte rows, and the reference's default layers=[1] has a hidden width of
+    ONE.  `dst`: where the last layer writes (f32 [M, ld >= G] rows, e.g. a slice of a score table) instead of a new tensor.
+    Returns (acts -- the padded input and every layer's output --, padded weights, dropout masks or None per layer): what the
+    backward pass needs; acts[-1][:, :G] are the scores."""
+    lib = _lib.lib()
+    dev = xt.device
+    M, C = xt.shape
+    n_layers = len(params) // 2
+    with torch.cuda.device(dev):                       # the library keys per-device state on the current device
+        st = _lib.stream_ptr(dev)
+        a = torch.zeros(M, _up(input_dim, 8), dtype=torch.float32, device=dev)
+        a[:, :input_dim] = xt[:, C - input_dim:]
+        acts, wpads, drops = [a], [], []
+        for i in range(n_layers):
+            w, b = params[2 * i], params[2 * i + 1]
+            n_out, k_in = w.shape[0], w.shape[1]
+            wp = torch.zeros(n_out, acts[-1].shape[1], dtype=torch.float32, device=dev)
+            wp[:, :k_in] = w.detach().view(n_out, k_in)
+            last = i + 1 == n_layers
+            out = dst if last and dst is not None else torch.zeros(M, _up(n_out, 8), dtype=torch.float32, device=dev)
+            bias = b.detach().float().contiguous()
+            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias),
+                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], M, n_out, wp.shape[1],
+                                     _lib.ptr(ws), ws.numel(), st))
+            dm = None
+            if not last and p_drop > 0.0:
+                dm = (torch.rand(M, out.shape[1], device=dev) >= p_drop).to(torch.float32) / (1.0 - p_drop)
+                out.mul_(dm)
+            wpads.append(wp)
+            drops.append(dm)
+            acts.append(out)
+    return acts, wpads, drops
+
+
 class _He2rnaFn(torch.autograd.Function):
     """x [B, C, N] f32 -> [B, G]: forward_fixed_k for one k (scale 1) or the eval mean over ks (scale 1 / len(ks))."""
 
@@ -40,42 +78,18 @@ class _He2rnaFn(torch.autograd.Function):
         dev = x.device
         B, C, N = x.shape
         M = B * N
-        st = _lib.stream_ptr(dev)
         xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(M, C)        # free when x came from 'b c f -> b f c'
-        mask = torch.empty(M, dtype=torch.float32, device=dev)
-        _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(xt), M, C, _lib.ptr(mask), st))
-        n_layers = len(params) // 2
-        # every activation / weight is zero-padded to a multiple of 8 columns: the GEMM engine wants 16-byte rows, and
-        # the reference's default layers=[1] has a hidden width of ONE
-        kin = _up(input_dim, 8)
-        a = torch.zeros(M, kin, dtype=torch.float32, device=dev)
-        a[:, :input_dim] = xt[:, C - input_dim:]
-        acts, wpads, drops = [a], [], []
-        for i in range(n_layers):
-            w, b = params[2 * i], params[2 * i + 1]
-            n_out, k_in = w.shape[0], w.shape[1]
-            wp = torch.zeros(n_out, acts[-1].shape[1], dtype=torch.float32, device=dev)
-            wp[:, :k_in] = w.detach().view(n_out, k_in)
-            ld = _up(n_out, 8)
-            out = torch.zeros(M, ld, dtype=torch.float32, device=dev)
-            last = i + 1 == n_layers
-            bias = b.detach().float().contiguous()
-            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias),
-                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, ld, M, n_out, wp.shape[1],
-                                     _lib.ptr(ws), ws.numel(), st))
-            dm = None
-            if not last and p_drop > 0.0:
-                dm = (torch.rand(M, ld, device=dev) >= p_drop).to(torch.float32) / (1.0 - p_drop)
-                out.mul_(dm)
-            wpads.append(wp)
-            drops.append(dm)
-            acts.append(out)
         G = params[-2].shape[0]
         ks_arr = np.asarray(ks, dtype=np.int32)
-        pred = torch.empty(B, G, dtype=torch.float32, device=dev)
-        _lib.check(lib.sq_he2rna_topk_mean(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), float(scale),
-                                           _lib.ptr(pred), B, N, G, st))
-        ctx.saved = (acts, wpads, drops, mask, ks_arr, float(scale), (B, C, N, input_dim), ws, [params[2 * i].shape[1] for i in range(n_layers)])
+        mask = torch.empty(M, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(xt), M, C, _lib.ptr(mask), st))
+            acts, wpads, drops = _layer_stack(xt, input_dim, params, ws, p_drop)
+            pred = torch.empty(B, G, dtype=torch.float32, device=dev)
+            _lib.check(lib.sq_he2rna_topk_mean(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), float(scale),
+                                               _lib.ptr(pred), B, N, G, st))
+        ctx.saved = (acts, wpads, drops, mask, ks_arr, float(scale), (B, C, N, input_dim), ws, [w.shape[1] for w in params[0::2]])
         return pred
 
     @staticmethod
@@ -84,38 +98,39 @@ class _He2rnaFn(torch.autograd.Function):
         acts, wpads, drops, mask, ks_arr, scale, (B, C, N, input_dim), ws, kins = ctx.saved
         dev = gout.device
         M = B * N
-        st = _lib.stream_ptr(dev)
-        n_layers = len(wpads)
-        G = wpads[-1].shape[0]
-        dy = torch.zeros_like(acts[-1])
-        _lib.check(lib.sq_he2rna_topk_mean_bwd(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), scale,
-                                               _lib.ptr(gout.detach().float().contiguous()), _lib.ptr(dy), dy.shape[1], B, N, G, st))
-        grads = [None] * (2 * n_layers)
-        for i in range(n_layers - 1, -1, -1):
-            wp, a_in = wpads[i], acts[i]
-            n_out, k_pad = wp.shape
-            dw = torch.empty(n_out, k_pad, dtype=torch.float32, device=dev)
-            db = torch.empty(n_out, dtype=torch.float32, device=dev)
-            _lib.check(lib.sq_linear_weight_grad(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(a_in), k_pad, _lib.ptr(dw), k_pad, _lib.ptr(db),
-                                                 n_out, k_pad, M, _lib.ptr(ws), ws.numel(), st))
-            grads[2 * i] = dw[:, :kins[i]].unsqueeze(-1)
-            grads[2 * i + 1] = db
-            if i > 0 or ctx.needs_input_grad[0]:
-                wt = torch.zeros(k_pad, dy.shape[1], dtype=torch.float32, device=dev)      # W^T, contraction over the padded outputs
-                wt[:, :n_out] = wp.t()
-                dx = torch.empty(M, k_pad, dtype=torch.float32, device=dev)
-                _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(wt), wt.shape[1], None, None, 0, _lib.SQ_F32, 0,
-                                         _lib.ptr(dx), _lib.SQ_F32, k_pad, M, k_pad, dy.shape[1], _lib.ptr(ws), ws.numel(), st))
-                if i > 0:
-                    dx.mul_((a_in > 0).to(torch.float32))          # ReLU (a dropped unit is 0 here and gets no gradient either way)
-                    if drops[i - 1] is not None:
-                        dx.mul_(drops[i - 1])
-                dy = dx
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.zeros(B, N, C, dtype=torch.float32, device=dev)
-            gx[:, :, C - input_dim:] = dy[:, :input_dim].view(B, N, input_dim)
-            gx = gx.transpose(1, 2)
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            n_layers = len(wpads)
+            G = wpads[-1].shape[0]
+            dy = torch.zeros_like(acts[-1])
+            _lib.check(lib.sq_he2rna_topk_mean_bwd(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), scale,
+                                                   _lib.ptr(gout.detach().float().contiguous()), _lib.ptr(dy), dy.shape[1], B, N, G, st))
+            grads = [None] * (2 * n_layers)
+            for i in range(n_layers - 1, -1, -1):
+                wp, a_in = wpads[i], acts[i]
+                n_out, k_pad = wp.shape
+                dw = torch.empty(n_out, k_pad, dtype=torch.float32, device=dev)
+                db = torch.empty(n_out, dtype=torch.float32, device=dev)
+                _lib.check(lib.sq_linear_weight_grad(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(a_in), k_pad, _lib.ptr(dw), k_pad, _lib.ptr(db),
+                                                     n_out, k_pad, M, _lib.ptr(ws), ws.numel(), st))
+                grads[2 * i] = dw[:, :kins[i]].unsqueeze(-1)
+                grads[2 * i + 1] = db
+                if i > 0 or ctx.needs_input_grad[0]:
+                    wt = torch.zeros(k_pad, dy.shape[1], dtype=torch.float32, device=dev)      # W^T, contraction over the padded outputs
+                    wt[:, :n_out] = wp.t()
+                    dx = torch.empty(M, k_pad, dtype=torch.float32, device=dev)
+                    _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(wt), wt.shape[1], None, None, 0, _lib.SQ_F32, 0,
+                                             _lib.ptr(dx), _lib.SQ_F32, k_pad, M, k_pad, dy.shape[1], _lib.ptr(ws), ws.numel(), st))
+                    if i > 0:
+                        dx.mul_((a_in > 0).to(torch.float32))          # ReLU (a dropped unit is 0 here and gets no gradient either way)
+                        if drops[i - 1] is not None:
+                            dx.mul_(drops[i - 1])
+                    dy = dx
+            gx = None
+            if ctx.needs_input_grad[0]:
+                gx = torch.zeros(B, N, C, dtype=torch.float32, device=dev)
+                gx[:, :, C - input_dim:] = dy[:, :input_dim].view(B, N, input_dim)
+                gx = gx.transpose(1, 2)
         return (gx, None, None, None, None, None) + tuple(grads)
 
 
@@ -199,29 +214,12 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
         scores = torch.empty(n, ld, dtype=torch.float32, device=dev)
         if n == 0:
             return scores, mask
-        ws = self._workspace(dev)
-        params = self._params()
-        layers, k = [], _up(self.input_dim, 8)
-        for i in range(self.n_layers):                    # weights zero-padded to the activations' 8-column rows, as in _He2rnaFn
-            w, b = params[2 * i], params[2 * i + 1]
-            n_out, k_in = w.shape[0], w.shape[1]
-            wp = torch.zeros(n_out, k, dtype=torch.float32, device=dev)
-            wp[:, :k_in] = w.detach().view(n_out, k_in)
-            layers.append((wp, b.detach().float().contiguous(), n_out))
-            k = _up(n_out, 8)
+        ws, params = self._workspace(dev), self._params()
         with torch.cuda.device(dev):
             _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(x), n, C, _lib.ptr(mask), st))
-            for r0 in range(0, n, self.TILE_ROWS):
-                r1 = min(n, r0 + self.TILE_ROWS)
-                a = torch.zeros(r1 - r0, _up(self.input_dim, 8), dtype=torch.float32, device=dev)
-                a[:, :self.input_dim] = x[r0:r1, C - self.input_dim:]
-                for i, (wp, bias, n_out) in enumerate(layers):
-                    last = i + 1 == self.n_layers
-                    out = scores[r0:r1] if last else torch.zeros(r1 - r0, _up(n_out, 8), dtype=torch.float32, device=dev)
-                    _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(a), a.shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias), None, 0, _lib.SQ_F32,
-                                             0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], r1 - r0, n_out, wp.shape[1],
-                                             _lib.ptr(ws), ws.numel(), st))
-                    a = out
+        for r0 in range(0, n, self.TILE_ROWS):
+            r1 = min(n, r0 + self.TILE_ROWS)
+            _layer_stack(x[r0:r1], self.input_dim, params, ws, dst=scores[r0:r1])
         return scores, mask
 
     def window_predictions(self, scores, mask, members):
@@ -251,31 +249,11 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
 class _ScoresFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p_drop, input_dim, ws, *params):
-        lib = _lib.lib()
-        dev = x.device
         B, C, N = x.shape
-        M = B * N
-        st = _lib.stream_ptr(dev)
-        xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(M, C)
-        a = torch.zeros(M, _up(input_dim, 8), dtype=torch.float32, device=dev)
-        a[:, :input_dim] = xt[:, C - input_dim:]
-        n_layers = len(params) // 2
-        for i in range(n_layers):
-            w, b = params[2 * i], params[2 * i + 1]
-            n_out, k_in = w.shape[0], w.shape[1]
-            wp = torch.zeros(n_out, a.shape[1], dtype=torch.float32, device=dev)
-            wp[:, :k_in] = w.detach().view(n_out, k_in)
-            out = torch.zeros(M, _up(n_out, 8), dtype=torch.float32, device=dev)
-            last = i + 1 == n_layers
-            bias = b.detach().float().contiguous()
-            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(a), a.shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias),
-                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], M, n_out, wp.shape[1],
-                                     _lib.ptr(ws), ws.numel(), st))
-            if not last and p_drop > 0.0:
-                out.mul_((torch.rand_like(out) >= p_drop).to(torch.float32) / (1.0 - p_drop))
-            a = out
+        xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(B * N, C)
+        acts, _, _ = _layer_stack(xt, input_dim, params, ws, p_drop)
         G = params[-2].shape[0]
-        return a[:, :G].reshape(B, N, G).transpose(1, 2)
+        return acts[-1][:, :G].reshape(B, N, G).transpose(1, 2)
 
     @staticmethod
     def backward(ctx, g):

@@ -129,6 +129,32 @@ def window_batch_owner(n_windows, batch_windows, world):
     return nb, -(-nb // world)
 
 
+def _slide_prologue(xtf, ytf, tile_features, stride, dev, G, shard):
+    """What every rank does first, in both sharded forms: the slide's window list, the f32 tile-feature cache and the HEAD_CHUNK
+    tile chunks this rank owns.  Returns ((rank, world, group), mem int64 [W, 100], feats f32 [n_tiles, D], chunks -- the rank's
+    chunk indices --, tile_ids int64 [n_local], empty = the function's result when no window is kept, else None)."""
+    rank, world, group = _shard_info(shard)
+    mem = enumerate_windows_device(xtf, ytf, stride, dev)           # nothing below waits for the device before the result is read
+    feats = tile_features.to(dev, torch.float32).contiguous()
+    n_tiles = feats.shape[0]
+    chunks = range(rank, -(-n_tiles // HEAD_CHUNK), world)
+    tile_ids = torch.cat([torch.arange(c * HEAD_CHUNK, min(n_tiles, (c + 1) * HEAD_CHUNK), device=dev) for c in chunks]) if len(chunks) \
+        else torch.zeros(0, dtype=torch.int64, device=dev)
+    empty = None
+    if mem.shape[0] == 0:
+        empty = torch.full((tile_ids.numel(), G), float("nan"), device=dev), tile_ids, torch.zeros(n_tiles, dtype=torch.int64, device=dev)
+    return (rank, world, group), mem, feats, chunks, tile_ids, empty
+
+
+def _window_vote(win_vec, lists, stride, out):
+    """sq_window_vote: out[t] = the vectors win_vec[lists[t, :]] (int32, -1 = none) of tile t's windows combined by the rule of
+    visualize.py:87-100 -- stride 10: the last writer; stride < 10: the mean in visiting order; no window: NaN."""
+    dev = win_vec.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().sq_window_vote(_lib.ptr(win_vec), win_vec.shape[0], win_vec.shape[1], _lib.ptr(lists), lists.shape[0],
+                                             lists.shape[1], 1 if stride == WINDOW else 0, float("nan"), _lib.ptr(out), _lib.stream_ptr(dev)))
+
+
 @torch.no_grad()
 def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d=False, batch_windows=1024, shard=None,
                                      tile_projection=True):
@@ -152,17 +178,12 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
     _lib.require_gpu()
     if _is_he2rna(model):
         return _he2rna_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d, shard)
-    rank, world, group = _shard_info(shard)
     dev = model.flat.device
-    mem = enumerate_windows_device(xtf, ytf, stride, dev)           # nothing below waits for the device before the result is read
-    feats = tile_features.to(dev, torch.float32).contiguous()
-    n_tiles, D = feats.shape
     G = model.cfg.num_outputs
-    chunks = range(rank, -(-n_tiles // HEAD_CHUNK), world)
-    tile_ids = torch.cat([torch.arange(c * HEAD_CHUNK, min(n_tiles, (c + 1) * HEAD_CHUNK), device=dev) for c in chunks]) if len(chunks) \
-        else torch.zeros(0, dtype=torch.int64, device=dev)
-    if mem.shape[0] == 0:
-        return torch.full((tile_ids.numel(), G), float("nan"), device=dev), tile_ids, torch.zeros(n_tiles, dtype=torch.int64, device=dev)
+    (rank, world, group), mem, feats, _, tile_ids, empty = _slide_prologue(xtf, ytf, tile_features, stride, dev, G, shard)
+    if empty is not None:
+        return empty
+    n_tiles, D = feats.shape
     gather = (mem[:, 0:1].expand(-1, mem.shape[1]) if literal_2d else mem).to(torch.int32).contiguous()
     # literal_2d: the reference feeds a 2-D [100, D] tensor and takes row 0 -> the prediction depends on the window's
     # first tile only, replicated over the 100 positions
@@ -174,13 +195,13 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
     # launches, a second chain fills the ramp-up / store-drain phases of the first
     main = torch.cuda.current_stream(dev)
     ns = max(1, int(os.environ.get("SQ_SPATIAL_STREAMS", "2")))
-    streams = model.__dict__.setdefault("_spatial_streams", None)
+    streams = model._spatial_streams
     if streams is None or streams[0].device != dev or len(streams) != ns:
-        streams = model.__dict__["_spatial_streams"] = [torch.cuda.Stream(device=dev) for _ in range(ns)]
+        streams = model._spatial_streams = [torch.cuda.Stream(device=dev) for _ in range(ns)]
     model._params_lp()                              # refresh the bf16 shadow on the main stream BEFORE the hand-over event:
     # bf16 mode: layer 0's local projection once per TILE (linear in tile feature + position), gathered per window token
     # (sq_vis_forward_tiles) -- n_tiles rows through the product instead of 100 x n_windows
-    tile_proj = model.tile_projections(feats) if (tile_projection and model._C_FWD == "sq_vis_forward" and model.compute_dtype == _lib.SQ_BF16
+    tile_proj = model.tile_projections(feats) if (tile_projection and model.has_tile_projection and model.compute_dtype == _lib.SQ_BF16
                                                   and W * mem.shape[1] > n_tiles) else None
     start = torch.cuda.Event()                      # the window streams wait on `start` only and must see the finished cast
     start.record(main)
@@ -208,9 +229,7 @@ def sliding_window_all_genes_sharded(xtf, ytf, tile_features, model, stride, lit
         return torch.empty(0, G, dtype=torch.float32, device=dev), tile_ids, counts
     lists = lists[tile_ids].contiguous() if world > 1 else lists.contiguous()
     tile_vec = torch.empty(lists.shape[0], D, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().sq_window_vote(_lib.ptr(win_vec), win_vec.shape[0], D, _lib.ptr(lists), lists.shape[0], lists.shape[1],
-                                             1 if stride == WINDOW else 0, float("nan"), _lib.ptr(tile_vec), _lib.stream_ptr(dev)))
+    _window_vote(win_vec, lists, stride, tile_vec)
     return model.apply_head(tile_vec, chunk=HEAD_CHUNK), tile_ids, counts
 
 
@@ -232,17 +251,12 @@ def _he2rna_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d
     the rows are BIT-IDENTICAL to the one-rank result."""
     if literal_2d:
         raise ValueError("literal_2d is the ViS / ViT 2-D input quirk; the reference feeds HE2RNA a 3-D tensor (visualize.py:79-81)")
-    rank, world, _ = _shard_info(shard)
     dev = next(model.parameters()).device
-    mem = enumerate_windows_device(xtf, ytf, stride, dev)
-    feats = tile_features.to(dev, torch.float32).contiguous()
-    n_tiles = feats.shape[0]
     G = model.output_dim
-    chunks = range(rank, -(-n_tiles // HEAD_CHUNK), world)
-    tile_ids = torch.cat([torch.arange(c * HEAD_CHUNK, min(n_tiles, (c + 1) * HEAD_CHUNK), device=dev) for c in chunks]) if len(chunks) \
-        else torch.zeros(0, dtype=torch.int64, device=dev)
-    if mem.shape[0] == 0:
-        return torch.full((tile_ids.numel(), G), float("nan"), device=dev), tile_ids, torch.zeros(n_tiles, dtype=torch.int64, device=dev)
+    _, mem, feats, chunks, tile_ids, empty = _slide_prologue(xtf, ytf, tile_features, stride, dev, G, shard)
+    if empty is not None:
+        return empty
+    n_tiles = feats.shape[0]
     gather = mem.to(torch.int32).contiguous()
     V = max_votes_per_tile(stride)
     lists, counts = tile_window_lists(mem, n_tiles, dev, max_votes=V)
@@ -269,9 +283,7 @@ def _he2rna_all_genes_sharded(xtf, ytf, tile_features, model, stride, literal_2d
                 continue
             pred = model.window_predictions(scores, mask, gather[wins.long()])
             local = torch.where(cl >= 0, torch.searchsorted(wins, cl.clamp(min=0).to(wins.dtype)), -1).to(torch.int32).contiguous()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().sq_window_vote(_lib.ptr(pred), pred.shape[0], G, _lib.ptr(local), t1 - t0, V, 1 if stride == WINDOW else 0,
-                                                     float("nan"), _lib.ptr(dst), _lib.stream_ptr(dev)))
+            _window_vote(pred, local, stride, dst)
     return out, tile_ids, counts
 
 

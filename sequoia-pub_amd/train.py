@@ -34,7 +34,7 @@ def smape(A, F):
 def grad_buckets(model):
     """[(lo, hi)] element ranges of the flat gradient in the order the backward pass completes them
     (sq_vis_grad_buckets); models without bucket support (the ViT baseline) are one bucket."""
-    if model._C_BWD != "sq_vis_backward":
+    if not model.has_grad_buckets:
         return [(0, model.flat.numel())]
     cap = model.cfg.depth + 1
     lo, hi = (ctypes.c_int64 * cap)(), (ctypes.c_int64 * cap)()
@@ -42,6 +42,13 @@ def grad_buckets(model):
     if n < 0:
         _lib.check(n)
     return [(int(lo[i]), int(hi[i])) for i in range(n)]
+
+
+def _flat_grad(model):
+    """The model's flat gradient buffer (the backward pass writes all of it)."""
+    if model._gflat is None or model._gflat.shape != model.flat.shape or model._gflat.device != model.flat.device:
+        model._gflat = torch.zeros_like(model.flat.detach())
+    return model._gflat
 
 
 def vis_backward(model, grad_out, batch, need_x_grad, bucket_events=None):
@@ -52,18 +59,16 @@ def vis_backward(model, grad_out, batch, need_x_grad, bucket_events=None):
     need = getattr(_lib.lib(), model._C_BWS)(ctypes.byref(model.cfg), model.compute_dtype, batch)
     if need == 0:                # a shape the backward pass refuses (sq_last_error says why): nothing has been launched
         _lib.check(-1)
-    if getattr(model, "_bws", None) is None or model._bws.numel() < need or model._bws.device != dev:
+    if model._bws is None or model._bws.numel() < need or model._bws.device != dev:
         model._bws = torch.empty(need, dtype=torch.uint8, device=dev)
-    gflat = getattr(model, "_gflat", None)
-    if gflat is None or gflat.shape != model.flat.shape or gflat.device != dev:
-        gflat = model._gflat = torch.zeros_like(model.flat.detach())
+    gflat = _flat_grad(model)
     gx = torch.empty(batch, model.cfg.num_clusters, model._dim(), device=dev) if need_x_grad else None
     ws = model._ws
     with torch.cuda.device(dev):
         args = (ctypes.byref(model.cfg), model.compute_dtype, _lib.ptr(model.flat), _lib.ptr(model._params_lp()),
                 _lib.ptr(grad_out), _lib.ptr(gflat), _lib.ptr(gx), batch, _lib.ptr(ws), ws.numel(),
                 _lib.ptr(model._bws), model._bws.numel(), _lib.stream_ptr(dev))
-        if bucket_events is not None and model._C_BWD == "sq_vis_backward":
+        if bucket_events is not None and model.has_grad_buckets:
             handles = (ctypes.c_void_p * len(bucket_events))(*[e.cuda_event for e in bucket_events])
             _lib.check(_lib.lib().sq_vis_backward_buckets(*args, handles, len(bucket_events)))
         else:
@@ -153,7 +158,7 @@ class FusedTrainStep:
         # AdamW per bucket on the communication stream, as each bucket becomes final (SQ_ADAMW_BUCKETS=1; also switches the bucket
         # path on for one rank).  Opt-in: measured SLOWER on one MI355X -- the 1.6 GB HBM-bound update running beside the backward
         # pass's products costs them more than the 0.28 ms pass it removes (config 2: 3.26 ms without, 3.33 ms with)
-        self.adamw_buckets = os.environ.get("SQ_ADAMW_BUCKETS", "0") == "1" and model._C_BWD == "sq_vis_backward"
+        self.adamw_buckets = os.environ.get("SQ_ADAMW_BUCKETS", "0") == "1" and model.has_grad_buckets
         self.overlap = self.overlap or self.adamw_buckets
         if grad_exchange is None:
             grad_exchange = "fp32"
@@ -201,9 +206,7 @@ class FusedTrainStep:
         else:
             main = torch.cuda.current_stream(dev)
             if empty:
-                gflat = getattr(m, "_gflat", None)
-                if gflat is None or gflat.shape != m.flat.shape or gflat.device != dev:
-                    gflat = m._gflat = torch.zeros_like(m.flat.detach())
+                gflat = _flat_grad(m)
                 gflat.zero_()
                 for e in self.events:
                     e.record(main)

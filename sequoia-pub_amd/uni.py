@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._flat import FlatParams, numel
 
 SQ_UNI_MAX_DEPTH = 32
 _LAYER_FIELDS = ["ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2"]
@@ -61,13 +62,6 @@ def tensor_map(cfg, lay):
         m[p + "ls2.gamma"] = (L.ls2, (D,))
     m["norm.weight"] = (lay.norm_g, (D,)); m["norm.bias"] = (lay.norm_b, (D,))
     return m
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return n
 
 
 def _gemm_blocks(cfg, lay):
@@ -119,7 +113,7 @@ def split_exec_planes(flat, lay, cfg):
     return torch.cat([hi, lo]).view(torch.int16), torch.cat([bias, factor])
 
 
-class UniViT(nn.Module):
+class UniViT(nn.Module, FlatParams):
     """timm VisionTransformer subset: ViT with class token, learned position embedding, LayerScale, token pooling,
     no classifier head.  ``forward(x f32 [B, 3, S, S]) -> f32 [B, dim]``."""
 
@@ -140,7 +134,7 @@ class UniViT(nn.Module):
         # timm's init: trunc_normal(std .02) embeddings / Linear weights, zero biases, LayerNorm 1 / 0, LayerScale init_values
         g = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 31))
         for k, (off, shape) in self._tmap.items():
-            n = _numel(shape)
+            n = numel(shape)
             if k.endswith("gamma"):
                 flat[off:off + n] = init_values if init_values is not None else 1.0
             elif "norm" in k and k.endswith("weight"):
@@ -149,37 +143,10 @@ class UniViT(nn.Module):
                 pass
             else:
                 flat[off:off + n] = torch.nn.init.trunc_normal_(torch.empty(n), std=0.02, generator=g)
-        self.flat = nn.Parameter(flat, requires_grad=False)
+        self._install_flat(flat, requires_grad=False)
         self._exec = None
         self._exec_key = None
         self._ws = {}
-        self._register_state_dict_hook(UniViT._sd_hook)
-        self._register_load_state_dict_pre_hook(self._load_hook)
-
-    # ---- timm-keyed state_dict over the flat buffer -------------------------------------------------------------
-    @staticmethod
-    def _sd_hook(module, state_dict, prefix, local_metadata):
-        flat = state_dict.pop(prefix + "flat")
-        for k, (off, shape) in module._tmap.items():
-            state_dict[prefix + k] = flat.detach()[off:off + _numel(shape)].reshape(shape).clone()
-        return state_dict
-
-    def _load_hook(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        if prefix + "flat" in state_dict or not any(prefix + k in state_dict for k in self._tmap):
-            return
-        flat = self.flat.detach().to("cpu", torch.float32).clone()
-        for k, (off, shape) in self._tmap.items():
-            full = prefix + k
-            if full not in state_dict:
-                if strict:
-                    missing_keys.append(full)
-                continue
-            t = state_dict.pop(full).detach().to("cpu", torch.float32)
-            if tuple(t.shape) != tuple(shape):
-                error_msgs.append(f"size mismatch for {full}: {tuple(t.shape)} vs {tuple(shape)}")
-                continue
-            flat[off:off + t.numel()] = t.reshape(-1)
-        state_dict[prefix + "flat"] = flat
 
     # ---- execution copies: LayerScale folded into attn.proj / mlp.fc2 -------------------------------------------------
     def _exec_params(self):

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._flat import FlatParams
 from ._lib import HEAD_DIM, VisConfig, VisLayout
 
 try:  # the reference class mixes this in (tformer_lin.py:4,80)
@@ -108,18 +109,23 @@ class _VisFunction(torch.autograd.Function):
         return gflat, gx, None, None
 
 
-class ViS(nn.Module, PyTorchModelHubMixin):
-    # C entry points and config accessors (the ViT baseline subclasses this plumbing, vit.py)
-    _C_WS, _C_FWD, _C_BWS, _C_BWD = "sq_vis_workspace_bytes", "sq_vis_forward", "sq_vis_backward_workspace_bytes", "sq_vis_backward"
-
-    def _dim(self):
-        return self.cfg.input_dim
-
+class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
     """Drop-in for the reference ``ViS`` (tformer_lin.py:80-106); see module docstring.
 
     Extra keyword ``compute_dtype``: ``"fp32"`` (exact-fp32 MFMA, parity mode, default) or
     ``"bf16"`` (bf16 MFMA with fp32 accumulation and fp32 residual stream, perf mode).
     """
+    # What the ViT baseline (vit.py) overrides: C entry points, layout / tensor-map functions, the model width, and which of
+    # the optional device paths exist
+    _C_WS, _C_FWD, _C_FWD_EX = "sq_vis_workspace_bytes", "sq_vis_forward", "sq_vis_forward_ex"
+    _C_BWS, _C_BWD = "sq_vis_backward_workspace_bytes", "sq_vis_backward"
+    _layout_fn, _tmap_fn = staticmethod(vis_layout), staticmethod(tensor_map)
+    has_tile_projection = True      # layer 0's local projection is linear in the tile feature: tile_projections / sq_vis_forward_tiles
+    has_grad_buckets = True         # the backward pass reports gradient buckets as they become final: sq_vis_backward_buckets
+    _saved_gen = 0                  # generation of the activations saved in the slot-0 workspace (_VisFunction.backward's guard)
+
+    def _dim(self):
+        return self.cfg.input_dim
 
     def __init__(self, num_outputs, input_dim, depth, nheads,
                  dimensions_f, dimensions_s, dimensions_c,
@@ -128,20 +134,11 @@ class ViS(nn.Module, PyTorchModelHubMixin):
         if not (dimensions_f == dimensions_s == dimensions_c == HEAD_DIM):
             raise ValueError("the HIP kernels are specialised for dimensions_f = dimensions_s = dimensions_c = 64 "
                              "(the value every reference call site uses: src/main.py:147,167,202)")
-        self.cfg = VisConfig(int(input_dim), int(depth), int(nheads), int(num_outputs), int(num_clusters))
-        self.layout = vis_layout(self.cfg)
-        self._tmap = tensor_map(self.cfg, self.layout)
-        self.compute_dtype = _lib.DTYPES[compute_dtype]
-        self.device = device
         # Same RNG draw order as the reference constructor (tformer_lin.py:86-94: pos-emb randn, then
         # per layer per head s, f, c Linear, projection, FF Linears, head Linear) so that
         # torch.manual_seed(s); ViS(...) gives the reference's initial weights.
-        flat = torch.zeros(self.layout.total, dtype=torch.float32)
-
-        def put(key, t):
-            off, shape = self._tmap[key]
-            flat[off:off + t.numel()] = t.detach().reshape(-1)
-
+        flat, put = self._begin(VisConfig(int(input_dim), int(depth), int(nheads), int(num_outputs), int(num_clusters)),
+                                compute_dtype, device)
         put("pos_emb1D", torch.randn(num_clusters, input_dim))
         hd = HEAD_DIM
         for l in range(depth):
@@ -167,59 +164,35 @@ class ViS(nn.Module, PyTorchModelHubMixin):
         lin = nn.Linear(input_dim, num_outputs)
         put("linear_head.1.weight", lin.weight)
         put("linear_head.1.bias", lin.bias)
-        self.flat = nn.Parameter(flat)
-        self._lp = None            # bf16 shadow of `flat`
-        self._lp_version = -1
-        self._ws = None            # workspace (uint8) and what it was sized for
-        self._ws_key = None
-        self._register_state_dict_hook(ViS._sd_hook)
-        self._register_load_state_dict_pre_hook(self._load_hook)
+        self._install_flat(flat)
+        self._reset_caches()
 
-    # ---- reference-compatible state_dict -------------------------------------------------
-    @staticmethod
-    def _sd_hook(module, state_dict, prefix, local_metadata):
-        flat = state_dict.pop(prefix + "flat")
-        for k, (off, shape) in module._tmap.items():
-            n = int(torch.tensor(shape).prod())
-            state_dict[prefix + k] = flat.detach()[off:off + n].reshape(shape).clone()
-        return state_dict
+    def _set_config(self, cfg):
+        self.cfg, self.layout = cfg, self._layout_fn(cfg)
+        self._tmap = self._tmap_fn(cfg, self.layout)
 
-    def _load_hook(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        if prefix + "flat" in state_dict:
-            return
-        keys = [prefix + k for k in self._tmap]
-        if not any(k in state_dict for k in keys):
-            return
-        flat = self.flat.detach().to("cpu", torch.float32).clone()
-        for k, (off, shape) in self._tmap.items():
-            full = prefix + k
-            if full not in state_dict:
-                if strict:
-                    missing_keys.append(full)
-                continue
-            t = state_dict.pop(full).detach().to("cpu", torch.float32)
-            if tuple(t.shape) != tuple(shape):
-                error_msgs.append(f"size mismatch for {full}: {tuple(t.shape)} vs {tuple(shape)}")
-                continue
-            flat[off:off + t.numel()] = t.reshape(-1)
-        state_dict[prefix + "flat"] = flat
+    def _begin(self, cfg, compute_dtype, device):
+        """Head of a constructor: config -> layout and tensor map; returns the zeroed CPU buffer and ``put(key, tensor)`` into it."""
+        self._set_config(cfg)
+        self.compute_dtype = _lib.DTYPES[compute_dtype]
+        self.device = device
+        flat = torch.zeros(self.layout.total, dtype=torch.float32)
 
-    def named_reference_tensors(self):
-        """Views (not copies) of the flat buffer under the reference's parameter names."""
-        for k, (off, shape) in self._tmap.items():
-            n = 1
-            for s in shape:
-                n *= s
-            yield k, self.flat.detach()[off:off + n].view(shape)
+        def put(key, t):
+            off, _ = self._tmap[key]
+            flat[off:off + t.numel()] = t.detach().reshape(-1)
+        return flat, put
 
-    def grad_views(self, gflat):
-        out = OrderedDict()
-        for k, (off, shape) in self._tmap.items():
-            n = 1
-            for s in shape:
-                n *= s
-            out[k] = gflat[off:off + n].view(shape)
-        return out
+    def _reset_caches(self):
+        """The one home of everything derived from `flat` (its size, its device, its values): dropped by the constructors and
+        by replace_head, re-created on demand by whoever uses it."""
+        self._lp, self._lp_version = None, -1       # bf16 shadow of `flat` (_params_lp)
+        self._ws, self._ws_key = None, None         # slot-0 workspace (uint8) and what it was sized for (_workspace)
+        self._ws_extra = {}                         # slot -> (workspace, key): inference forwards in flight on several streams
+        self._saved_x = None
+        self._saved_gen += 1                        # whatever a forward saved in the slot-0 workspace is gone
+        self._bws, self._gflat = None, None         # backward workspace and flat gradient (train.vis_backward)
+        self._spatial_streams = None                # window streams of spatial.sliding_window_all_genes_sharded
 
     # fine-tuning replaces the head (src/main.py:155-157: model.linear_head = nn.Sequential(LN, Linear))
     def __setattr__(self, name, value):
@@ -230,21 +203,20 @@ class ViS(nn.Module, PyTorchModelHubMixin):
 
     def replace_head(self, head):
         ln, lin = head[0], head[1]
-        G = lin.out_features
-        old_cfg, old_lay = self.cfg, self.layout
-        cfg = VisConfig(old_cfg.input_dim, old_cfg.depth, old_cfg.nheads, int(G), old_cfg.num_clusters)
-        lay = vis_layout(cfg)
-        flat = torch.zeros(lay.total, dtype=torch.float32, device=self.flat.device)
-        flat[:old_lay.head_ln_g] = self.flat.detach()[:old_lay.head_ln_g]
-        D = cfg.input_dim
+        G, D = lin.out_features, self._dim()
+        old, body = self.flat.detach(), self.layout.head_ln_g
+        cfg = type(self.cfg).from_buffer_copy(self.cfg)
+        cfg.num_outputs = int(G)
+        self._set_config(cfg)
+        lay = self.layout
+        flat = torch.zeros(lay.total, dtype=torch.float32, device=old.device)
+        flat[:body] = old[:body]
         flat[lay.head_ln_g:lay.head_ln_g + D] = ln.weight.detach().to(flat.device)
         flat[lay.head_ln_b:lay.head_ln_b + D] = ln.bias.detach().to(flat.device)
         flat[lay.head_w:lay.head_w + G * D] = lin.weight.detach().reshape(-1).to(flat.device)
         flat[lay.head_b:lay.head_b + G] = lin.bias.detach().to(flat.device)
-        self.cfg, self.layout = cfg, lay
-        self._tmap = tensor_map(cfg, lay)
         self.flat = nn.Parameter(flat)
-        self._lp, self._lp_version, self._ws, self._ws_key = None, -1, None, None
+        self._reset_caches()
 
     # ---- device plumbing --------------------------------------------------------------------
     def _params_lp(self):
@@ -265,11 +237,10 @@ class ViS(nn.Module, PyTorchModelHubMixin):
         if need == 0:
             _lib.check(-1)
         if slot:                     # extra inference workspaces: forwards in flight on several streams
-            extra = self.__dict__.setdefault("_ws_extra", {})
-            ws, k = extra.get(slot, (None, None))
+            ws, k = self._ws_extra.get(slot, (None, None))
             if ws is None or k != key or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.uint8, device=self.flat.device)
-                extra[slot] = (ws, key)
+                self._ws_extra[slot] = (ws, key)
             return ws
         if self._ws is None or self._ws_key != key or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.flat.device)
@@ -294,7 +265,7 @@ class ViS(nn.Module, PyTorchModelHubMixin):
                                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
         self._saved_x = x if save else None
         if slot == 0:           # slot-0 workspace rewritten (or re-allocated): earlier saved activations are gone
-            self._saved_gen = self.__dict__.get("_saved_gen", 0) + 1
+            self._saved_gen += 1
         return out
 
     def tile_projections(self, cache):
@@ -303,7 +274,7 @@ class ViS(nn.Module, PyTorchModelHubMixin):
         tile feature + position, so a window token's f(x) is f_tile[tile] + f_pos[slot] -- what sq_vis_forward_tiles gathers
         instead of running the projection over every window token (bf16 mode; the exact fp32 mode keeps the per-token product)."""
         _lib.require_gpu()
-        if self._C_FWD != "sq_vis_forward" or self.compute_dtype != _lib.SQ_BF16:
+        if not self.has_tile_projection or self.compute_dtype != _lib.SQ_BF16:
             raise NotImplementedError("tile projections are the bf16 ViS sliding-window path's")
         lay, dev = self.layout, cache.device
         D, HD, N = self._dim(), self.cfg.nheads * 64, self.cfg.num_clusters
@@ -325,17 +296,21 @@ class ViS(nn.Module, PyTorchModelHubMixin):
         return f_tile, f_pos
 
     def _run_head_inputs(self, cache, members, slot=0, tile_proj=None):
-        """Sliding-window form (sq_vis_forward_ex): cache f32 [n_rows, D] on the device, members int32 [B, 100] rows of
-        the cache per window (-1 = zero padding).  Returns the linear head's input LayerNorm(mean_tokens X) f32 [B, D]
-        -- the window batch [B, 100, D] is gathered inside the first kernel and the head is left to the caller.
-        ``tile_proj`` = tile_projections(cache): the first layer's local projection is gathered per tile (sq_vis_forward_tiles)."""
+        """Sliding-window form (sq_vis_forward_ex / sq_vit_forward_ex): cache f32 [n_rows, D] on the device, members int32
+        [B, num_clusters] rows of the cache per window (-1 = zero padding).  Returns the linear head's input LayerNorm(mean_tokens X)
+        f32 [B, D] -- the window batch [B, num_clusters, D] is gathered inside the first kernel and the head is left to the caller
+        (``apply_head``).  ``tile_proj`` = tile_projections(cache): the first layer's local projection is gathered per tile
+        (sq_vis_forward_tiles; ViS only -- a ViT layer starts with LayerNorm(x + pos), which is not linear in the tile feature)."""
         _lib.require_gpu()
-        if self._C_FWD != "sq_vis_forward":
-            raise NotImplementedError("head inputs are implemented for ViS (the linear-attention aggregator)")
-        B, N = members.shape
-        if N != self.cfg.num_clusters or cache.shape[1] != self._dim():
-            raise ValueError(f"expected members [B, {self.cfg.num_clusters}] and a [rows, {self._dim()}] cache")
-        out = torch.empty(B, self._dim(), dtype=torch.float32, device=cache.device)
+        if tile_proj is not None and not self.has_tile_projection:
+            raise NotImplementedError("tile projections are the bf16 ViS sliding-window path's")
+        N, D = self.cfg.num_clusters, self._dim()
+        if members.dim() != 2 or members.shape[1] != N or cache.dim() != 2 or cache.shape[1] != D:
+            raise ValueError(f"expected members [B, {N}] and a [rows, {D}] cache")
+        if members.dtype != torch.int32 or not members.is_contiguous() or cache.dtype != torch.float32 or not cache.is_contiguous():
+            raise ValueError("members must be contiguous int32 and the cache contiguous float32")   # both reach the kernel as raw pointers
+        B = members.shape[0]
+        out = torch.empty(B, D, dtype=torch.float32, device=cache.device)
         ws = self._workspace(B, False, slot)
         lp = self._params_lp()
         with torch.cuda.device(cache.device):
@@ -347,9 +322,9 @@ class ViS(nn.Module, PyTorchModelHubMixin):
                                                            _lib.ptr(cache), _lib.ptr(members), cache.shape[0], _lib.ptr(f_tile), _lib.ptr(f_pos),
                                                            _lib.ptr(out), B, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
             else:
-                _lib.check(_lib.lib().sq_vis_forward_ex(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(lp), None,
-                                                        _lib.ptr(cache), _lib.ptr(members), cache.shape[0], None, _lib.ptr(out), B, 0,
-                                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
+                _lib.check(getattr(_lib.lib(), self._C_FWD_EX)(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(lp), None,
+                                                                _lib.ptr(cache), _lib.ptr(members), cache.shape[0], None, _lib.ptr(out), B, 0,
+                                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
         return out
 
     def apply_head(self, head_in, chunk=32768):

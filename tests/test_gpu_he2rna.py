@@ -60,6 +60,27 @@ def test_gradients_match_reference_golden():
     np.testing.assert_allclose(xg.grad.cpu().numpy(), d["grad_x"], rtol=1e-4, atol=1e-4 * np.abs(d["grad_x"]).max())
 
 
+@pytest.mark.parametrize("layers", [[16, 16], [1]], ids=["hidden16x16", "hidden_width_one"])
+def test_the_three_users_of_the_layer_stack_agree_bit_for_bit(layers):
+    """conv() (the inspection helper), tile_scores() (the sliding-window score table) and forward() run the same layer stack on
+    the same rows: in eval mode their bits are equal.  35 channels > input_dim 32: the channel slice of he2rna.py:102;
+    layers=[1]: a hidden width of one, zero-padded to 8 columns; M = 2 * 20 = 40 rows: one launch on every path."""
+    _lib.require_gpu()
+    torch.manual_seed(6)
+    D, G, B, C, N = 32, 12, 2, 35, 20
+    m = HE2RNA(input_dim=D, output_dim=G, layers=layers, ks=[1, 5, 20], dropout=0.5, device="cuda:0").eval()
+    x = torch.randn(B, C, N, generator=torch.Generator().manual_seed(7)).clamp_min(-0.2).cuda()
+    cache = x.transpose(1, 2).reshape(B * N, C).contiguous()         # one tile per row, as the spatial path holds them
+    with torch.no_grad():
+        per_tile = m.conv(x).transpose(1, 2).reshape(B * N, G)       # [B, G, N] -> [B * N, G]
+        scores, mask = m.tile_scores(cache)
+        assert torch.equal(per_tile, scores[:, :G])
+        members = torch.arange(B * N, dtype=torch.int32, device="cuda:0").view(B, N)
+        pred = m(x)
+        assert pred.shape == (B, G) and bool(torch.isfinite(pred).all())
+        assert torch.equal(pred, m.window_predictions(scores, mask, members))
+
+
 def test_full_size_against_oracle_and_training_step():
     """pretrain_gtex.py:102-105: layers [256, 256], ks [1, 2, 5, 10, 20, 50, 100], 2048-dim cluster features, 20 820 genes."""
     _lib.require_gpu()

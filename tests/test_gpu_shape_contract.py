@@ -188,6 +188,23 @@ def test_sliding_window_form_matches_the_oracle_on_the_gathered_tokens(cid, rows
     assert_allclose_rel(out, ref, tol, f"{cid} {mode} gather form")
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_vis_sliding_window_form_refuses_an_int64_member_table_before_any_launch(mode):
+    """The member table reaches the kernel as a raw pointer to int32 [B, num_clusters]: any other element type is refused by
+    message, nothing is launched, and the next valid call returns what it returned before."""
+    _lib.require_gpu()
+    case = sc.BY_ID["vis-D128-h2-L2-N7-B9-G40"]
+    cache, members = sc.gather_inputs(case, 41)
+    cache, members = cache.cuda().contiguous(), members.cuda().contiguous()
+    m = _model(case, mode)
+    with torch.no_grad():
+        first = m._run_head_inputs(cache, members).clone()
+        with pytest.raises(ValueError, match="int32"):
+            m._run_head_inputs(cache, members.long())
+        again = m._run_head_inputs(cache, members)
+    assert bool(torch.isfinite(first).all()) and torch.equal(first, again)
+
+
 def test_vis_combiner_in_the_epilogue_off_n100(monkeypatch):
     """bf16 inference large enough for the combiner to run in the f projection's epilogue (gemm_p8.hip) at N = 50: a row bias
     per 50 token rows, 5.12 slides per 256-row tile, 70 000 rows = 273 tiles and a ragged one.  Against the two launches

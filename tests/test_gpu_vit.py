@@ -45,6 +45,43 @@ def test_vit_tiny_forward_and_grads(golden_dir, mode, tol_f, tol_g):
     assert rel_err(x.grad.cpu().numpy(), xo.grad.numpy()) < tol_g
 
 
+def test_vit_head_replacement_and_checkpoint_round_trip(tmp_path):
+    """main.py:155-157 replaces `linear_head` for fine-tuning (--model_type vit takes the same branch); vit.py:213 saves
+    `model.state_dict()` and predict_independent_dataset.py:75-80 loads it back.  The ViT twin of
+    test_gpu_edges.py::test_head_replacement_and_checkpoint_round_trip."""
+    _lib.require_gpu()
+    cfg = dict(num_outputs=40, dim=128, depth=2, heads=2, mlp_dim=256)
+    sd = vis_oracle.perturb_norm_params(vis_oracle.init_vit_state_dict(**cfg, seed=3), seed=4)
+    m = ViT(**cfg, device="cuda:0")
+    m.load_state_dict(sd)
+    m.to("cuda:0")
+    x = torch.randn(2, 100, 128, generator=torch.Generator().manual_seed(5)).cuda()
+    m.linear_head = torch.nn.Sequential(torch.nn.LayerNorm(128), torch.nn.Linear(128, 17))
+    m.to("cuda:0")
+    out = m(x)
+    assert out.shape == (2, 17)
+    sd2 = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+    assert sd2["linear_head.1.weight"].shape == (17, 128)
+    with torch.no_grad():
+        ref = vis_oracle.vit_forward(sd2, x.cpu(), 2).numpy()
+    e = rel_err(out.detach().cpu().numpy(), ref)
+    print(f"vit head replacement fp32: forward rel err {e:.3e}")
+    assert e < 1e-4
+    path = os.path.join(tmp_path, "model_best.pt")
+    torch.save(m.state_dict(), path)
+    m2 = ViT(**dict(cfg, num_outputs=17), device="cuda:0")
+    m2.load_state_dict(torch.load(path, map_location="cpu"))
+    m2.to("cuda:0")
+    assert torch.equal(m2(x), out)
+    # the new head trains: one optimizer step changes it and leaves shapes alone
+    opt = torch.optim.AdamW(m.parameters(), lr=1e-2)
+    loss = torch.nn.functional.mse_loss(m(x), torch.zeros(2, 17, device="cuda"))
+    loss.backward()
+    opt.step()
+    after = m.state_dict()["linear_head.1.weight"].cpu()
+    assert after.shape == (17, 128) and not torch.equal(after, sd2["linear_head.1.weight"])
+
+
 def test_vit_real_shape_vs_oracle():
     """main.py:160-163 shape (dim 1024, 16 heads x 64, mlp 2048), 2 layers, G = 500, B = 3."""
     _lib.require_gpu()
