@@ -629,6 +629,69 @@ size_t sq_map_gene_corr_workspace_bytes(int n, int K);
 int sq_map_gene_corr(const float* pred, int n, int ld, const int32_t* cols, int K, double* out, void* workspace,
                      size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Ground-truth alignment: what spatial_vis/get_emd.py computes between a predicted slide and its spatial-transcriptomics
+ * spots before the EMD -- get_average (:27-38), median_filter (:41-51) and the np.unique counts of :204-205; the
+ * percentile step (:21-25,172,175) is sq_map_percentile above.  Tables are row-major with a leading dimension `ld` and an
+ * optional device list `cols` of int32 column indices, as in the map statistics.  Every argument is checked before the
+ * first launch; the calls are asynchronous on `stream` and never synchronise; no floating-point atomics, every sum in a
+ * fixed order: two calls give the same bytes.  Everything is integer work or a separately rounded f64 operation in a
+ * defined order (no fused multiply-add, a correctly rounded square root), so the results equal the reference's own
+ * calls bit for bit; the sign and payload of a NaN are not part of that.
+ *
+ *   sq_gt_nearest_spots : get_average's `sorted(range(n_spots), key=distances)[:num_tiles]` (:29-32) for every tile at once.
+ *                         xc, yc f64 [n_tiles] tile coordinates, sx, sy f64 [n_spots] spot coordinates;
+ *                         d = sqrt((sx - xc)(sx - xc) + (sy - yc)(sy - yc)).  idx int32 [n_tiles, k_eff], k_eff =
+ *                         min(k, n_spots): the first k_eff spots of a STABLE sort by d -- equal d goes to the lower spot
+ *                         index, and equality is judged on d, not on d^2 -- in that order; dist, when not NULL, f64 of the
+ *                         same shape.  1 <= n_tiles <= SQ_MAP_MAX_ROWS, 1 <= n_spots <= SQ_GT_MAX_SPOTS,
+ *                         1 <= k <= SQ_GT_MAX_K.  NaN coordinates are the caller's to refuse (Python's sorted has no
+ *                         defined order for them).  One thread per tile, the spots staged through LDS in chunks of
+ *                         sq_gt_spot_chunk(), the k best in registers.
+ *   sq_gt_spot_means    : np.mean of the kept spots' expression (:34-38).  idx int32 [n_tiles, k_eff] as above; expr f32
+ *                         (expr_f64 = 0; widened to f64 first) or f64 (1) [n_spots, ld]; out f64 [n_tiles, C] =
+ *                         (((0.0 + e0) + e1) + ...) / k_eff in kept order for k_eff <= 7 and numpy's pairwise block
+ *                         (0.0 + (((e0 + e1) + (e2 + e3)) + ((e4 + e5) + (e6 + e7)))) / 8 for k_eff = 8.  A NaN or an
+ *                         infinity propagates.  A spot index outside [0, n_spots) is not followed: that mean is NaN.
+ *   sq_gt_median_filter : median_filter(df, col, x, y, r) (:41-51) for every row of every column.  values f64 [n, ld];
+ *                         xtf, ytf int32 [n] grid coordinates in [0, grid_w) x [0, grid_h), grid_w grid_h <=
+ *                         SQ_GT_MAX_GRID_CELLS; r in 1..SQ_GT_MAX_RADIUS.  The window of a row is the rows with
+ *                         |xtf - x| <= r and |ytf - y| <= r, c of them; if 2 c > (2 r + 1)^2 the result is np.median of
+ *                         the window -- NaN if a member is NaN, else 0.0 + the middle of the sorted members (odd c) or
+ *                         ((0.0 + a) + b) / 2.0 of the two middle ones (even c), infinities and overflow as that
+ *                         expression has them -- otherwise the row's own value.  nan_absent = 1: a NaN in column c means
+ *                         the row is absent from column c (the per-gene dropna of :166): it is counted in no window of
+ *                         that column and its own result is NaN.  out f64 [n, C]; counts, when not NULL, int32 [n, C]:
+ *                         the windows' c.  Two rows in one grid cell are not supported: `flag`, one caller-zeroed
+ *                         device byte, is set to 1 when a row does not find its own number in its cell or a coordinate
+ *                         lies outside the grid (such a row reads nothing and its result is NaN); the results are then
+ *                         not to be used.  A first kernel scatters the row numbers into the workspace's int32 grid, a
+ *                         second sorts each window in a per-thread column of LDS.
+ *   sq_gt_count_unique  : len(np.unique(column)) (:204-205) of C columns of values f64 [n, ld]: out int32 [C].  -0.0 and
+ *                         0.0 are one value, all NaNs together are one.  1 <= n <= SQ_MAP_MAX_ROWS,
+ *                         1 <= C <= SQ_GT_MAX_UNIQUE_COLS.  Chunks of sq_gt_unique_chunk_rows() rows are sorted in LDS;
+ *                         a value counts in the first chunk that holds it.
+ *   The two *_workspace_bytes functions return 0 for a refused shape.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_GT_MAX_SPOTS 1048576
+#define SQ_GT_MAX_K 8
+#define SQ_GT_MAX_RADIUS 3
+#define SQ_GT_MAX_GRID_CELLS 16777216
+#define SQ_GT_MAX_UNIQUE_COLS 65536
+int sq_gt_spot_chunk(void);
+int sq_gt_unique_chunk_rows(void);
+int sq_gt_nearest_spots(const double* xc, const double* yc, int n_tiles, const double* sx, const double* sy, int n_spots, int k,
+                        int32_t* idx, double* dist, sq_stream_t stream);
+int sq_gt_spot_means(const int32_t* idx, int n_tiles, int k_eff, const void* expr, int expr_f64, int n_spots, int ld,
+                     const int32_t* cols, int C, double* out, sq_stream_t stream);
+size_t sq_gt_median_filter_workspace_bytes(int n, int grid_w, int grid_h);
+int sq_gt_median_filter(const double* values, int n, int ld, const int32_t* cols, int C, const int32_t* xtf, const int32_t* ytf,
+                        int grid_w, int grid_h, int r, int nan_absent, double* out, int32_t* counts, uint8_t* flag,
+                        void* workspace, size_t workspace_bytes, sq_stream_t stream);
+size_t sq_gt_count_unique_workspace_bytes(int n, int C);
+int sq_gt_count_unique(const double* values, int n, int ld, const int32_t* cols, int C, int32_t* out, void* workspace,
+                       size_t workspace_bytes, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

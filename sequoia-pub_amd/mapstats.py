@@ -5,7 +5,8 @@
 The table these scripts read is the f32 ``[n_tiles, G]`` prediction table ``spatial.sliding_window_all_genes`` leaves on
 the device.  The reference ranks every tile with one ``scipy.stats.percentileofscore`` call per row (O(n) each) and
 correlates the genes with ``DataFrame.corr()`` on one core; here both are one library call.  Tensors live on the device
-and there is no CPU fallback.  Figures, EMD and the spatial-transcriptomics ground truth stay out."""
+and there is no CPU fallback.  The alignment with the spatial-transcriptomics ground truth is gtalign.py; figures and the EMD stay out
+(DESIGN.md section 7)."""
 import ctypes
 from collections import OrderedDict
 
