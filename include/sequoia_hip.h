@@ -588,8 +588,12 @@ int sq_tile_grid_valid(const uint8_t* mask_u8, int mask_w, int mask_h, int n_col
  * from a slide's prediction table (f32 [n_tiles, G], as spatial.sliding_window_all_genes leaves it on the device).
  * Tables are row-major with a leading dimension `ld` (elements); `cols` is a device list of int32 column indices in
  * [0, ld), NULL = columns 0..C-1 (C <= ld): gene columns are read in place.  n <= SQ_MAP_MAX_ROWS tiles.  Every argument
- * is checked before the first launch; the calls are asynchronous on `stream` and never synchronise; no atomics, every
- * sum in a fixed order: two calls give the same bytes.
+ * is checked before the first launch; the calls are asynchronous on `stream` and never synchronise; no floating-point
+ * atomics, every sum in a fixed order: two calls give the same bytes.
+ * Invariant of every *_workspace_bytes function here and under "Ground-truth alignment": it returns 0 exactly when one
+ * of its own arguments is outside the range its entry admits, the entry then refuses the same arguments with SQ_ERR_ARG,
+ * and every refusal precedes the first launch.  A caller need not test the size: it makes the call with non-null
+ * pointers and a workspace of at least that size (any, if 0), and the entry's own message says what is wrong.
  *
  *   sq_map_percentile   : score2percentile of gbm_celltype_analysis.py:12-16,107 and get_emd.py:21-25,172,175 for every
  *                         element of every column: scipy.stats.percentileofscore(column, x) with the default kind='rank',
@@ -600,8 +604,9 @@ int sq_tile_grid_valid(const uint8_t* mask_u8, int mask_w, int mask_h, int n_col
  *                         not NULL, is int32 [n]: the first column holding the row's largest percentile, NaN skipped, -1
  *                         for a row of NaN (df[[... '_perc']].idxmax(axis=1) of :109, ties to the earlier column).
  *                         1 <= n <= SQ_MAP_MAX_ROWS, C >= 1.  A column is cut into chunks of sq_map_rank_chunk_rows()
- *                         rows; one workgroup sorts a chunk's keys in LDS, every element is then searched in every sorted
- *                         chunk of its column (counts add over chunks).
+ *                         rows; one workgroup sorts a chunk's keys in LDS (csrc/colsort.hip, shared with
+ *                         sq_gt_count_unique), every element is then searched in every sorted chunk of its column with the
+ *                         lower- and upper-bound search of csrc/colsort.h (counts add over chunks).
  *   sq_map_category_means : df[genes of a category].mean(axis=1) of :105.  pred f32 [n, ld]; members int32 [offsets[n_cat]]
  *                         gene (column) indices, category c owns members[offsets[c] .. offsets[c + 1]) (both on the device,
  *                         indices in [0, ld) -- the caller validates them); out f64 [n, n_cat] = the f64 sum of the
@@ -615,7 +620,6 @@ int sq_tile_grid_valid(const uint8_t* mask_u8, int mask_w, int mask_h, int n_col
  *                         first) gives NaN in its row and column, the diagonal included (as pandas).  A NaN VALUE makes
  *                         its column's row and column NaN (pandas would drop the pair's rows: not done here, the tables
  *                         of :72 have had their NaN rows dropped).  2 <= n <= SQ_MAP_MAX_ROWS, 1 <= K <= SQ_MAP_MAX_CORR_COLS.
- *   The two *_workspace_bytes functions return 0 for a refused shape.
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_MAP_MAX_ROWS 262144
 #define SQ_MAP_MAX_CORR_COLS 32768
@@ -669,9 +673,10 @@ int sq_map_gene_corr(const float* pred, int n, int ld, const int32_t* cols, int 
  *                         second sorts each window in a per-thread column of LDS.
  *   sq_gt_count_unique  : len(np.unique(column)) (:204-205) of C columns of values f64 [n, ld]: out int32 [C].  -0.0 and
  *                         0.0 are one value, all NaNs together are one.  1 <= n <= SQ_MAP_MAX_ROWS,
- *                         1 <= C <= SQ_GT_MAX_UNIQUE_COLS.  Chunks of sq_gt_unique_chunk_rows() rows are sorted in LDS;
- *                         a value counts in the first chunk that holds it.
- *   The two *_workspace_bytes functions return 0 for a refused shape.
+ *                         1 <= C <= SQ_GT_MAX_UNIQUE_COLS.  Chunks of sq_gt_unique_chunk_rows() rows (the percentile's
+ *                         chunk: sq_map_rank_chunk_rows()) are sorted in LDS by the percentile's kernel (csrc/colsort.hip); a
+ *                         value counts in the first chunk that holds it, found with the lower-bound search of csrc/colsort.h.
+ *   The two *_workspace_bytes functions return 0 exactly for the refused shapes (the invariant stated above).
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_GT_MAX_SPOTS 1048576
 #define SQ_GT_MAX_K 8

@@ -74,6 +74,10 @@ class SequoiaHipError(RuntimeError):
     pass
 
 
+class SequoiaHipArgError(SequoiaHipError, ValueError):
+    """The library refused an argument (SQ_ERR_ARG)."""
+
+
 _lib = None
 
 
@@ -209,7 +213,8 @@ def lib():
 
 def check(rc):
     if rc != 0:
-        raise SequoiaHipError(f"libsequoia_hip error {rc}: {lib().sq_last_error().decode()}")
+        kind = SequoiaHipArgError if rc == -1 else SequoiaHipError      # SQ_ERR_ARG
+        raise kind(f"libsequoia_hip error {rc}: {lib().sq_last_error().decode()}")
 
 
 def require_gpu(device=None):

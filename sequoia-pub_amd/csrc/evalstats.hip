@@ -6,8 +6,9 @@
 //
 // Layout: the [n, G] tables are row-major, so the moment kernel gives one gene to each lane (coalesced across
 // genes) and walks the n rows; the quantiles need each column sorted: real is transposed to [G, n] once and a
-// workgroup bitonic-sorts one column in LDS.
+// workgroup sorts one column in LDS with the bitonic sort of colsort.h.
 #include "../../include/sequoia_hip.h"
+#include "colsort.h"
 #include "elementwise.h"
 
 namespace {
@@ -51,18 +52,7 @@ __global__ __launch_bounds__(256) void gene_quantile_kernel(const float* __restr
     const int g = blockIdx.x;
     for (int i = threadIdx.x; i < npow2; i += 256) col[i] = i < n ? realT[(size_t)g * ldt + i] : INFINITY;
     __syncthreads();
-    for (int k = 2; k <= npow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < npow2; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float a = col[i], b = col[l];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) { col[i] = b; col[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    cs_sort<float, 256>(col, npow2);
     if (threadIdx.x < 2) {
         // numpy.quantile(method="linear"): virtual index q*(n-1); lerp a + (b-a)*t, taken from the b side when t >= 0.5
         const double q = threadIdx.x == 0 ? 0.25 : 0.75;
@@ -88,11 +78,7 @@ extern "C" int sq_gene_eval_stats(const float* real, const float* pred, const fl
     hipStream_t st = (hipStream_t)stream_;
     SQ_REQUIRE(real && pred && random_pred && out9 && workspace, "gene_eval_stats: null pointer");
     SQ_REQUIRE(n >= 2 && n <= MAX_N && G >= 1, "gene_eval_stats: n=%d samples (2..%d), G=%d", n, MAX_N, G);
-    const size_t need = sq_gene_eval_workspace_bytes(n, G);
-    if (workspace_bytes < need) {
-        sq_set_error("gene_eval_stats: workspace %zu < required %zu", workspace_bytes, need);
-        return SQ_ERR_WORKSPACE;
-    }
+    SQ_REQUIRE_WORKSPACE("gene_eval_stats", workspace_bytes, sq_gene_eval_workspace_bytes(n, G));
     hipLaunchKernelGGL(gene_moments_kernel, dim3((G + 255) / 256), dim3(256), 0, st, real, pred, random_pred, n, G, out9);
     SQ_LAUNCH_CHECK();
     const int ldt = (n + 3) / 4 * 4;

@@ -13,13 +13,13 @@
 //   median filter  median_filter (:41-51): a first kernel scatters the row numbers into an int32 grid (-1 = empty cell), a
 //                  second reads the (2r+1)^2 neighbour cells of every row and insertion-sorts the members' values in a
 //                  per-thread column of LDS (element s of thread t at [s][t]: no bank conflict, no scratch).
-//   unique         len(np.unique(column)) (:204-205): chunks of GT_UQ_CHUNK rows bitonic-sorted in LDS (as the percentile's,
-//                  mapstats.hip), then a value counts where it first appears in its chunk and no EARLIER chunk holds it
-//                  (earlier chunks walk through LDS, a binary search each).
+//   unique         len(np.unique(column)) (:204-205): chunks of CS_CHUNK rows sorted by cs_sort_chunks (colsort.h, colsort.hip:
+//                  the LDS bitonic sort the percentile shares), then a value counts where it first appears in its chunk and no
+//                  EARLIER chunk holds it (earlier chunks walk through LDS, a binary search of colsort.h each).
 // Integer work and separately rounded f64 operations in a fixed order; the only atomics are integer counters in LDS.  Two
 // calls give the same bytes.
 #include "../../include/sequoia_hip.h"
-#include "sq_common.h"
+#include "colsort.h"
 
 #pragma clang fp contract(off)      // dx dx + dy dy and every sum are separately rounded operations, as numpy's are
 
@@ -27,10 +27,7 @@ namespace {
 
 constexpr int GT_SPOT_CHUNK = 2048;       // spots of one LDS chunk: 2048 x (x, y) f64 = 32 KiB
 constexpr int GT_NS_THREADS = 64;         // one wave: a slide of a few thousand tiles still spreads over many CUs
-constexpr int GT_MAX_BLOCKS = 1 << 20;    // grid-stride beyond
 constexpr int GT_MF_THREADS = 128;        // r = 3: 49 x 128 x 8 B = 49 KiB of LDS
-constexpr int GT_UQ_CHUNK = 4096;         // keys of one sorted chunk: 32 KiB of LDS
-constexpr int GT_UQ_SORT_THREADS = 512;
 constexpr int GT_UQ_COUNT_THREADS = 256;
 
 // ------------------------------------------------------------------------------------------
@@ -201,55 +198,12 @@ __global__ __launch_bounds__(GT_MF_THREADS) void gt_median_kernel(const double* 
 // ------------------------------------------------------------------------------------------
 // 4. number of distinct values of a column
 // ------------------------------------------------------------------------------------------
-// grid (C, chunks).  A NaN is stored as +inf, as the pad keys of a short chunk are, and counted: the chunk's first
-// `len - #NaN` sorted keys are its numbers (a real +inf is among them; which +inf is which does not matter to a count).
-__global__ __launch_bounds__(GT_UQ_SORT_THREADS) void gt_unique_sort_kernel(const double* __restrict__ values, int n, int ld,
-                                                                            const int32_t* __restrict__ cols, double* __restrict__ sorted, int npad,
-                                                                            int chunks, int32_t* __restrict__ valid, int32_t* __restrict__ nan_flag) {
-    __shared__ double key[GT_UQ_CHUNK];
-    __shared__ int n_nan;
-    const int c = blockIdx.x, r0 = blockIdx.y * GT_UQ_CHUNK, tid = threadIdx.x;
-    const int len = min(GT_UQ_CHUNK, n - r0);
-    int npow2 = 1;
-    while (npow2 < len) npow2 <<= 1;
-    const size_t col = (size_t)(cols ? cols[c] : c);
-    if (tid == 0) n_nan = 0;
-    __syncthreads();
-    int mine = 0;
-    for (int i = tid; i < npow2; i += GT_UQ_SORT_THREADS) {
-        double v = INFINITY;
-        if (i < len) {
-            v = values[(size_t)(r0 + i) * (size_t)ld + col];
-            if (v != v) { ++mine; v = INFINITY; }
-        }
-        key[i] = v;
-    }
-    if (mine) {
-        atomicAdd(&n_nan, mine);                              // an integer counter in LDS
-        nan_flag[c] = 1;                                      // every writer stores the same value
-    }
-    __syncthreads();
-    for (int k = 2; k <= npow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (npow2 >> 1); t += GT_UQ_SORT_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;      // i has bit j clear; i, l < npow2
-                const double a = key[i], b = key[l];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) { key[i] = b; key[l] = a; }
-            }
-            __syncthreads();
-        }
-    double* const dst = sorted + (size_t)c * (size_t)npad + (size_t)r0;
-    for (int i = tid; i < len; i += GT_UQ_SORT_THREADS) dst[i] = key[i];
-    if (tid == 0) valid[(size_t)c * (size_t)chunks + blockIdx.y] = len - n_nan;
-}
-
-// grid (C, chunks): the block of chunk k holds its sorted keys in registers (GT_UQ_CHUNK / 256 per thread), marks the first
+// grid (C, chunks): the block of chunk k holds its sorted keys in registers (CS_CHUNK / 256 per thread), marks the first
 // of every run of equal keys, and strikes those that an earlier chunk holds.
 __global__ __launch_bounds__(GT_UQ_COUNT_THREADS) void gt_unique_count_kernel(const double* __restrict__ sorted, int npad, int chunks,
                                                                               const int32_t* __restrict__ valid, int32_t* __restrict__ partial) {
-    constexpr int Q = GT_UQ_CHUNK / GT_UQ_COUNT_THREADS;
-    __shared__ double key[GT_UQ_CHUNK];
+    constexpr int Q = CS_CHUNK / GT_UQ_COUNT_THREADS;
+    __shared__ double key[CS_CHUNK];
     __shared__ int total;
     const int c = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
     const double* const col = sorted + (size_t)c * (size_t)npad;
@@ -262,24 +216,20 @@ __global__ __launch_bounds__(GT_UQ_COUNT_THREADS) void gt_unique_count_kernel(co
         const int p = q * GT_UQ_COUNT_THREADS + tid;
         x[q] = 0.0;
         if (p < len) {
-            x[q] = col[(size_t)k * GT_UQ_CHUNK + p];
-            if (p == 0 || col[(size_t)k * GT_UQ_CHUNK + p - 1] != x[q]) alive |= 1u << q;
+            x[q] = col[(size_t)k * CS_CHUNK + p];
+            if (p == 0 || col[(size_t)k * CS_CHUNK + p - 1] != x[q]) alive |= 1u << q;
         }
     }
     if (tid == 0) total = 0;
     for (int e = 0; e < k; ++e) {
         const int elen = vl[e];
         __syncthreads();                                      // the previous chunk's searches are done
-        for (int i = tid; i < elen; i += GT_UQ_COUNT_THREADS) key[i] = col[(size_t)e * GT_UQ_CHUNK + i];
+        for (int i = tid; i < elen; i += GT_UQ_COUNT_THREADS) key[i] = col[(size_t)e * CS_CHUNK + i];
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             if (!(alive & (1u << q))) continue;
-            int lo = 0, hi = elen;
-            while (lo < hi) {                                 // first key >= x
-                const int mid = (lo + hi) >> 1;
-                if (key[mid] < x[q]) lo = mid + 1; else hi = mid;
-            }
+            const int lo = cs_first_ge(key, elen, x[q]);
             if (lo < elen && key[lo] == x[q]) alive &= ~(1u << q);
         }
     }
@@ -305,8 +255,8 @@ struct UqPlan {
 
 UqPlan uq_plan(int n, int C) {
     UqPlan p;
-    p.chunks = (n + GT_UQ_CHUNK - 1) / GT_UQ_CHUNK;
-    p.npad = p.chunks * GT_UQ_CHUNK;
+    p.chunks = cs_chunks(n);
+    p.npad = p.chunks * CS_CHUNK;
     size_t o = sq_align_up((size_t)C * (size_t)p.npad * 8, 256);
     p.off_valid = o;   o += sq_align_up((size_t)C * (size_t)p.chunks * 4, 256);
     p.off_partial = o; o += sq_align_up((size_t)C * (size_t)p.chunks * 4, 256);
@@ -315,20 +265,15 @@ UqPlan uq_plan(int n, int C) {
     return p;
 }
 
-unsigned gt_blocks(size_t items, int threads) {
-    const size_t b = (items + (size_t)threads - 1) / (size_t)threads;
-    return (unsigned)(b < (size_t)GT_MAX_BLOCKS ? b : (size_t)GT_MAX_BLOCKS);
-}
-
 }  // namespace
 
 static_assert(GT_SPOT_CHUNK * sizeof(double2) <= 32768, "a chunk of spots fits half the static LDS limit");
 static_assert((2 * SQ_GT_MAX_RADIUS + 1) * (2 * SQ_GT_MAX_RADIUS + 1) * GT_MF_THREADS * sizeof(double) <= 65536, "the widest window's values fit LDS");
-static_assert((GT_UQ_CHUNK & (GT_UQ_CHUNK - 1)) == 0 && GT_UQ_CHUNK / GT_UQ_COUNT_THREADS <= 32, "a thread's keys fit its bit mask");
+static_assert(CS_CHUNK % GT_UQ_COUNT_THREADS == 0 && CS_CHUNK / GT_UQ_COUNT_THREADS <= 32, "a thread's keys fit its bit mask");
 static_assert(SQ_GT_MAX_K == 8, "the mean's pairwise form and the launch table are written for k <= 8");
 
 extern "C" int sq_gt_spot_chunk(void) { return GT_SPOT_CHUNK; }
-extern "C" int sq_gt_unique_chunk_rows(void) { return GT_UQ_CHUNK; }
+extern "C" int sq_gt_unique_chunk_rows(void) { return CS_CHUNK; }
 
 extern "C" int sq_gt_nearest_spots(const double* xc, const double* yc, int n_tiles, const double* sx, const double* sy, int n_spots, int k,
                                    int32_t* idx, double* dist, sq_stream_t stream_) {
@@ -360,14 +305,12 @@ extern "C" int sq_gt_spot_means(const int32_t* idx, int n_tiles, int k_eff, cons
     SQ_REQUIRE(n_spots >= 1 && n_spots <= SQ_GT_MAX_SPOTS, "gt_spot_means: n_spots = %d, must be in 1..%d", n_spots, SQ_GT_MAX_SPOTS);
     SQ_REQUIRE(k_eff >= 1 && k_eff <= SQ_GT_MAX_K && k_eff <= n_spots, "gt_spot_means: k_eff = %d, must be in 1..min(%d, n_spots = %d)", k_eff,
                SQ_GT_MAX_K, n_spots);
-    SQ_REQUIRE(C >= 1, "gt_spot_means: C = %d columns, must be at least 1", C);
+    SQ_REQUIRE_COLUMNS("gt_spot_means", "C", C, 0, ld, cols);
     SQ_REQUIRE(expr_f64 == 0 || expr_f64 == 1, "gt_spot_means: expr_f64 = %d, must be 0 (f32) or 1 (f64)", expr_f64);
-    SQ_REQUIRE(ld >= 1 && (cols || C <= ld), "gt_spot_means: leading dimension ld = %d for C = %d columns%s", ld, C,
-               cols ? "" : " (no column list: C <= ld)");
     SQ_REQUIRE(idx && expr && out, "gt_spot_means: null idx, expr or out pointer");
     SQ_REQUIRE(((uintptr_t)expr & (expr_f64 ? 7 : 3)) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)cols & 3) == 0 && ((uintptr_t)idx & 3) == 0,
                "gt_spot_means: misaligned pointer");
-    const unsigned blocks = gt_blocks((size_t)n_tiles * (size_t)C, 256);
+    const unsigned blocks = cs_blocks((size_t)n_tiles * (size_t)C, 256);
     hipStream_t st = (hipStream_t)stream_;
     if (expr_f64)
         hipLaunchKernelGGL(gt_spot_means_kernel<double>, dim3(blocks), dim3(256), 0, st, idx, n_tiles, k_eff, (const double*)expr, n_spots, ld, cols,
@@ -387,10 +330,7 @@ extern "C" size_t sq_gt_median_filter_workspace_bytes(int n, int grid_w, int gri
 extern "C" int sq_gt_median_filter(const double* values, int n, int ld, const int32_t* cols, int C, const int32_t* xtf, const int32_t* ytf,
                                    int grid_w, int grid_h, int r, int nan_absent, double* out, int32_t* counts, uint8_t* flag,
                                    void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
-    SQ_REQUIRE(n >= 1 && n <= SQ_MAP_MAX_ROWS, "gt_median_filter: n = %d rows, must be in 1..%d", n, SQ_MAP_MAX_ROWS);
-    SQ_REQUIRE(C >= 1, "gt_median_filter: C = %d columns, must be at least 1", C);
-    SQ_REQUIRE(ld >= 1 && (cols || C <= ld), "gt_median_filter: leading dimension ld = %d for C = %d columns%s", ld, C,
-               cols ? "" : " (no column list: C <= ld)");
+    SQ_REQUIRE_TABLE("gt_median_filter", n, 1, SQ_MAP_MAX_ROWS, "C", C, 0, ld, cols);
     SQ_REQUIRE(grid_w >= 1 && grid_h >= 1 && (long long)grid_w * (long long)grid_h <= SQ_GT_MAX_GRID_CELLS,
                "gt_median_filter: grid %d x %d, both extents must be at least 1 and their product at most %d", grid_w, grid_h, SQ_GT_MAX_GRID_CELLS);
     SQ_REQUIRE(r >= 1 && r <= SQ_GT_MAX_RADIUS, "gt_median_filter: radius r = %d, must be in 1..%d", r, SQ_GT_MAX_RADIUS);
@@ -398,17 +338,13 @@ extern "C" int sq_gt_median_filter(const double* values, int n, int ld, const in
     SQ_REQUIRE(values && xtf && ytf && out && flag && workspace, "gt_median_filter: null values, xtf, ytf, out, flag or workspace pointer");
     SQ_REQUIRE((((uintptr_t)values | (uintptr_t)out | (uintptr_t)workspace) & 7) == 0 &&
                (((uintptr_t)cols | (uintptr_t)xtf | (uintptr_t)ytf | (uintptr_t)counts) & 3) == 0, "gt_median_filter: misaligned pointer");
-    const size_t need = sq_gt_median_filter_workspace_bytes(n, grid_w, grid_h);
-    if (workspace_bytes < need) {
-        sq_set_error("gt_median_filter: workspace %zu < required %zu", workspace_bytes, need);
-        return SQ_ERR_WORKSPACE;
-    }
+    SQ_REQUIRE_WORKSPACE("gt_median_filter", workspace_bytes, sq_gt_median_filter_workspace_bytes(n, grid_w, grid_h));
     hipStream_t st = (hipStream_t)stream_;
     int32_t* const grid = (int32_t*)workspace;
     SQ_HIP_CHECK(hipMemsetAsync(grid, 0xFF, (size_t)grid_w * (size_t)grid_h * 4, st));          // every cell -1
     hipLaunchKernelGGL(gt_grid_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xtf, ytf, n, grid_w, grid_h, grid, flag);
     SQ_LAUNCH_CHECK();
-    const unsigned blocks = gt_blocks((size_t)n * (size_t)C, GT_MF_THREADS);
+    const unsigned blocks = cs_blocks((size_t)n * (size_t)C, GT_MF_THREADS);
     if (r == 1)
         hipLaunchKernelGGL(gt_median_kernel<1>, dim3(blocks), dim3(GT_MF_THREADS), 0, st, values, n, ld, cols, C, xtf, ytf, grid_w, grid_h,
                            (const int32_t*)grid, nan_absent, out, counts, flag);
@@ -429,28 +365,19 @@ extern "C" size_t sq_gt_count_unique_workspace_bytes(int n, int C) {
 
 extern "C" int sq_gt_count_unique(const double* values, int n, int ld, const int32_t* cols, int C, int32_t* out, void* workspace,
                                   size_t workspace_bytes, sq_stream_t stream_) {
-    SQ_REQUIRE(n >= 1 && n <= SQ_MAP_MAX_ROWS, "gt_count_unique: n = %d rows, must be in 1..%d", n, SQ_MAP_MAX_ROWS);
-    SQ_REQUIRE(C >= 1 && C <= SQ_GT_MAX_UNIQUE_COLS, "gt_count_unique: C = %d columns, must be in 1..%d", C, SQ_GT_MAX_UNIQUE_COLS);
-    SQ_REQUIRE(ld >= 1 && (cols || C <= ld), "gt_count_unique: leading dimension ld = %d for C = %d columns%s", ld, C,
-               cols ? "" : " (no column list: C <= ld)");
+    SQ_REQUIRE_TABLE("gt_count_unique", n, 1, SQ_MAP_MAX_ROWS, "C", C, SQ_GT_MAX_UNIQUE_COLS, ld, cols);
     SQ_REQUIRE(values && out && workspace, "gt_count_unique: null values, out or workspace pointer");
     SQ_REQUIRE((((uintptr_t)values | (uintptr_t)workspace) & 7) == 0 && (((uintptr_t)cols | (uintptr_t)out) & 3) == 0,
                "gt_count_unique: misaligned pointer");
     const UqPlan p = uq_plan(n, C);
-    if (workspace_bytes < p.bytes) {
-        sq_set_error("gt_count_unique: workspace %zu < required %zu", workspace_bytes, p.bytes);
-        return SQ_ERR_WORKSPACE;
-    }
+    SQ_REQUIRE_WORKSPACE("gt_count_unique", workspace_bytes, p.bytes);
     hipStream_t st = (hipStream_t)stream_;
     char* const ws = (char*)workspace;
     double* const sorted = (double*)ws;
     int32_t* const valid = (int32_t*)(ws + p.off_valid);
     int32_t* const partial = (int32_t*)(ws + p.off_partial);
     int32_t* const nan_flag = (int32_t*)(ws + p.off_flag);
-    SQ_HIP_CHECK(hipMemsetAsync(nan_flag, 0, (size_t)C * sizeof(int32_t), st));
-    hipLaunchKernelGGL(gt_unique_sort_kernel, dim3((unsigned)C, (unsigned)p.chunks), dim3(GT_UQ_SORT_THREADS), 0, st, values, n, ld, cols, sorted,
-                       p.npad, p.chunks, valid, nan_flag);
-    SQ_LAUNCH_CHECK();
+    if (int e = cs_sort_chunks(values, 1, n, ld, cols, C, sorted, valid, nan_flag, st)) return e;
     hipLaunchKernelGGL(gt_unique_count_kernel, dim3((unsigned)C, (unsigned)p.chunks), dim3(GT_UQ_COUNT_THREADS), 0, st, (const double*)sorted,
                        p.npad, p.chunks, (const int32_t*)valid, partial);
     SQ_LAUNCH_CHECK();

@@ -2,13 +2,14 @@
 // spatial_vis/gbm_celltype_analysis.py and the percentile step of spatial_vis/get_emd.py.
 //   percentile   score2percentile (gbm_celltype_analysis.py:12-16,107; get_emd.py:21-25,172,175): the reference calls
 //                scipy.stats.percentileofscore(column, x) once per row, O(n) each.  Here a column is cut into chunks of
-//                MR_CHUNK rows; one workgroup bitonic-sorts a chunk's keys in LDS (keys only, no index payload) and writes
-//                them to the workspace; every element then takes a lower- and an upper-bound binary search in every sorted
-//                chunk of its column (a workgroup stages the chunk in LDS for 1024 elements).  #(column < x) and #(column <= x) add over chunks, so nothing is merged.  Keys keep the
-//                input's type (f32 or f64) and are compared as IEEE numbers, so -0.0 ties with 0.0 as it does in numpy.  A
-//                NaN is stored as +inf, as the pad keys of a short chunk are, and raises the column's flag: the sort network
-//                only ever sees ordered keys, a search only looks at the chunk's first `len` keys (pads sort behind or
-//                beside every real key), and a flagged column comes back all NaN (scipy's nan_policy='propagate').
+//                CS_CHUNK rows that cs_sort_chunks (colsort.h, colsort.hip: the LDS bitonic sort, keys only) sorts into the
+//                workspace; every element then takes a lower- and an upper-bound binary search (colsort.h) in every sorted
+//                chunk of its column (a workgroup stages the chunk in LDS for 1024 elements).  #(column < x) and
+//                #(column <= x) add over chunks, so nothing is merged.  Keys keep the input's type (f32 or f64) and are
+//                compared as IEEE numbers, so -0.0 ties with 0.0 as it does in numpy.  A NaN is stored as +inf, as the pad
+//                keys of a short chunk are, and raises the column's flag: a search only looks at the chunk's first `len`
+//                keys (pads sort behind or beside every real key), and a flagged column comes back all NaN (scipy's
+//                nan_policy='propagate').
 //   means        df[genes of category].mean(axis=1) (:105): one thread per (tile, category), f64 sum in list order.
 //   correlation  df[all_genes].corr() (:75): f64 column means (row slices added in slice order), then C = Z^T Z of the
 //                centred columns on v_mfma_f64_16x16x4_f64 -- the TN form of km_dgemm_nt_kernel (kmeans.hip): a chunk of 32
@@ -16,9 +17,10 @@
 //                above the diagonal only; the rows are cut into slices (grid z) when there are few blocks, each slice
 //                writes its partial C plane and the last kernel adds the planes in slice order, divides by
 //                sqrt(C_ii) sqrt(C_jj), clips, and stores [i][j] and [j][i] from the same value.
-// No atomics and no order that depends on scheduling: two calls give the same bytes.
+// No floating-point atomics (the chunk sort counts a chunk's NaNs with an integer add in LDS) and no order that depends on
+// scheduling: two calls give the same bytes.
 #include "../../include/sequoia_hip.h"
-#include "sq_common.h"
+#include "colsort.h"
 
 #pragma clang fp contract(off)      // the sums and quotients the tests hold to numpy are separately rounded operations
 
@@ -27,55 +29,16 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // 1. percentile of score
 // ------------------------------------------------------------------------------------------
-constexpr int MR_CHUNK = 4096;            // keys of one sorted chunk: 16 KiB (f32) / 32 KiB (f64) of LDS
-constexpr int MR_THREADS = 512;
 constexpr int MR_QROWS = 1024;            // query rows of one workgroup of the rank kernel
-constexpr int MR_MAX_BLOCKS = 1 << 20;    // grid-stride beyond (category means)
-
-// grid (C, chunks): neighbouring blocks read neighbouring columns of the same rows (the table is row-major)
-template <typename T>
-__global__ __launch_bounds__(MR_THREADS) void map_sort_chunks_kernel(const T* __restrict__ values, int n, int ld,
-                                                                     const int32_t* __restrict__ cols, T* __restrict__ sorted,
-                                                                     int npad, int32_t* __restrict__ nan_flag) {
-    __shared__ T key[MR_CHUNK];
-    const int c = blockIdx.x, r0 = blockIdx.y * MR_CHUNK, tid = threadIdx.x;
-    const int len = min(MR_CHUNK, n - r0);
-    int npow2 = 1;
-    while (npow2 < len) npow2 <<= 1;
-    const int col = cols ? cols[c] : c;
-    bool nan = false;
-    for (int i = tid; i < npow2; i += MR_THREADS) {
-        T v = (T)INFINITY;
-        if (i < len) {
-            v = values[(size_t)(r0 + i) * (size_t)ld + (size_t)col];
-            if (v != v) { nan = true; v = (T)INFINITY; }
-        }
-        key[i] = v;
-    }
-    if (nan) nan_flag[c] = 1;             // every writer stores the same value
-    __syncthreads();
-    for (int k = 2; k <= npow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (npow2 >> 1); t += MR_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;      // i has bit j clear; i, l < npow2
-                const T a = key[i], b = key[l];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) { key[i] = b; key[l] = a; }
-            }
-            __syncthreads();
-        }
-    T* const dst = sorted + (size_t)c * (size_t)npad + (size_t)r0;
-    for (int i = tid; i < len; i += MR_THREADS) dst[i] = key[i];
-}
 
 // grid (C, row blocks): a workgroup takes MR_QROWS rows of one column as queries (MR_QROWS / 256 per thread, in registers) and
 // walks the column's sorted chunks through LDS, so every step of a search is an LDS read and a chunk is read from memory once
-// per MR_QROWS queries (coalesced).  Neighbouring blocks hold neighbouring columns of the same rows, as in the sort.
+// per MR_QROWS queries (coalesced).  Neighbouring blocks hold neighbouring columns of the same rows, as in the chunk sort.
 template <typename T>
 __global__ __launch_bounds__(256) void map_rank_kernel(const T* __restrict__ values, int n, int ld, const int32_t* __restrict__ cols,
                                                        int C, const T* __restrict__ sorted, int npad,
                                                        const int32_t* __restrict__ nan_flag, double scale, double* __restrict__ out) {
-    __shared__ T key[MR_CHUNK];
+    __shared__ T key[CS_CHUNK];
     constexpr int Q = MR_QROWS / 256;
     const int c = blockIdx.x, row0 = blockIdx.y * MR_QROWS, tid = threadIdx.x;
     const bool flagged = nan_flag[c] != 0;                  // the same for the whole workgroup
@@ -89,25 +52,16 @@ __global__ __launch_bounds__(256) void map_rank_kernel(const T* __restrict__ val
         left[q] = right[q] = 0;
     }
     const T* const s = sorted + (size_t)c * (size_t)npad;
-    for (int r0 = 0; r0 < n && !flagged; r0 += MR_CHUNK) {
-        const int len = min(MR_CHUNK, n - r0);
+    for (int r0 = 0; r0 < n && !flagged; r0 += CS_CHUNK) {
+        const int len = min(CS_CHUNK, n - r0);
         __syncthreads();                                    // the previous chunk's searches are done
         for (int i = tid; i < len; i += 256) key[i] = s[r0 + i];
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            int lo = 0, hi = len;
-            while (lo < hi) {                               // first key >= x
-                const int mid = (lo + hi) >> 1;
-                if (key[mid] < x[q]) lo = mid + 1; else hi = mid;
-            }
+            const int lo = cs_first_ge(key, len, x[q]);
             left[q] += lo;
-            hi = len;
-            while (lo < hi) {                               // first key > x, from there on
-                const int mid = (lo + hi) >> 1;
-                if (key[mid] <= x[q]) lo = mid + 1; else hi = mid;
-            }
-            right[q] += lo;
+            right[q] += cs_first_gt(key, lo, len, x[q]);
         }
     }
 #pragma unroll
@@ -132,18 +86,14 @@ __global__ __launch_bounds__(256) void map_row_argmax_kernel(const double* __res
     argmax[i] = best;
 }
 
+// workspace: the sorted chunks of the C columns, then the columns' NaN flags
+size_t mr_sorted_bytes(int n, int C, int values_f64) { return sq_align_up((size_t)C * (size_t)cs_chunks(n) * CS_CHUNK * (values_f64 ? 8 : 4), 256); }
+
 template <typename T>
-int mr_run(const void* values_, int n, int ld, const int32_t* cols, int C, double scale, double* out, void* workspace, hipStream_t st) {
-    const T* values = (const T*)values_;
-    const int chunks = (n + MR_CHUNK - 1) / MR_CHUNK, npad = chunks * MR_CHUNK;
-    T* sorted = (T*)workspace;
-    int32_t* nan_flag = (int32_t*)((char*)workspace + sq_align_up((size_t)C * (size_t)npad * sizeof(T), 256));
-    SQ_HIP_CHECK(hipMemsetAsync(nan_flag, 0, (size_t)C * sizeof(int32_t), st));
-    hipLaunchKernelGGL(map_sort_chunks_kernel<T>, dim3((unsigned)C, (unsigned)chunks), dim3(MR_THREADS), 0, st, values, n, ld, cols, sorted,
-                       npad, nan_flag);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(map_rank_kernel<T>, dim3((unsigned)C, (unsigned)((n + MR_QROWS - 1) / MR_QROWS)), dim3(256), 0, st, values, n, ld, cols, C,
-                       (const T*)sorted, npad, (const int32_t*)nan_flag, scale, out);
+int mr_rank(const void* values, int n, int ld, const int32_t* cols, int C, double scale, double* out, const void* sorted,
+            const int32_t* nan_flag, hipStream_t st) {
+    hipLaunchKernelGGL(map_rank_kernel<T>, dim3((unsigned)C, (unsigned)((n + MR_QROWS - 1) / MR_QROWS)), dim3(256), 0, st, (const T*)values, n, ld,
+                       cols, C, (const T*)sorted, cs_chunks(n) * CS_CHUNK, nan_flag, scale, out);
     SQ_LAUNCH_CHECK();
     return SQ_OK;
 }
@@ -348,36 +298,29 @@ __global__ __launch_bounds__(256) void map_corr_finish_kernel(const double* part
 
 }  // namespace
 
-static_assert((MR_CHUNK & (MR_CHUNK - 1)) == 0 && MR_CHUNK * sizeof(double) <= 32768, "a chunk's keys fit the static LDS limit");
 static_assert(MC_KC % 4 == 0 && 256 / 64 * (MC_KC / 4) == MC_KC, "the loader's 4 rows x 64 columns per pass cover a chunk");
 
-extern "C" int sq_map_rank_chunk_rows(void) { return MR_CHUNK; }
+extern "C" int sq_map_rank_chunk_rows(void) { return CS_CHUNK; }
 
 extern "C" size_t sq_map_percentile_workspace_bytes(int n, int C, int values_f64) {
     if (n < 1 || n > SQ_MAP_MAX_ROWS || C < 1 || (values_f64 != 0 && values_f64 != 1)) return 0;
-    const size_t npad = (size_t)((n + MR_CHUNK - 1) / MR_CHUNK) * MR_CHUNK;
-    return sq_align_up((size_t)C * npad * (values_f64 ? 8 : 4), 256) + sq_align_up((size_t)C * 4, 256);
+    return mr_sorted_bytes(n, C, values_f64) + sq_align_up((size_t)C * 4, 256);
 }
 
 extern "C" int sq_map_percentile(const void* values, int values_f64, int n, int ld, const int32_t* cols, int C, double scale,
                                  double* out, int32_t* argmax, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
-    SQ_REQUIRE(n >= 1 && n <= SQ_MAP_MAX_ROWS, "map_percentile: n = %d rows, must be in 1..%d", n, SQ_MAP_MAX_ROWS);
-    SQ_REQUIRE(C >= 1, "map_percentile: C = %d columns, must be at least 1", C);
+    SQ_REQUIRE_TABLE("map_percentile", n, 1, SQ_MAP_MAX_ROWS, "C", C, 0, ld, cols);
     SQ_REQUIRE(values_f64 == 0 || values_f64 == 1, "map_percentile: values_f64 = %d, must be 0 (f32) or 1 (f64)", values_f64);
-    SQ_REQUIRE(ld >= 1 && (cols || C <= ld), "map_percentile: leading dimension ld = %d for C = %d columns%s", ld, C,
-               cols ? "" : " (no column list: C <= ld)");
     SQ_REQUIRE(scale == scale, "map_percentile: scale is not a number");
     SQ_REQUIRE(values && out && workspace, "map_percentile: null values, out or workspace pointer");
     SQ_REQUIRE(((uintptr_t)values & (values_f64 ? 7 : 3)) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)cols & 3) == 0 &&
                ((uintptr_t)argmax & 3) == 0 && ((uintptr_t)workspace & 7) == 0, "map_percentile: misaligned pointer");
-    const size_t need = sq_map_percentile_workspace_bytes(n, C, values_f64);
-    if (workspace_bytes < need) {
-        sq_set_error("map_percentile: workspace %zu < required %zu", workspace_bytes, need);
-        return SQ_ERR_WORKSPACE;
-    }
+    SQ_REQUIRE_WORKSPACE("map_percentile", workspace_bytes, sq_map_percentile_workspace_bytes(n, C, values_f64));
     hipStream_t st = (hipStream_t)stream_;
-    if (int e = values_f64 ? mr_run<double>(values, n, ld, cols, C, scale, out, workspace, st)
-                           : mr_run<float>(values, n, ld, cols, C, scale, out, workspace, st)) return e;
+    int32_t* const nan_flag = (int32_t*)((char*)workspace + mr_sorted_bytes(n, C, values_f64));
+    if (int e = cs_sort_chunks(values, values_f64, n, ld, cols, C, workspace, nullptr, nan_flag, st)) return e;
+    if (int e = values_f64 ? mr_rank<double>(values, n, ld, cols, C, scale, out, workspace, nan_flag, st)
+                           : mr_rank<float>(values, n, ld, cols, C, scale, out, workspace, nan_flag, st)) return e;
     if (argmax) {
         hipLaunchKernelGGL(map_row_argmax_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)out, n, C, argmax);
         SQ_LAUNCH_CHECK();
@@ -387,15 +330,14 @@ extern "C" int sq_map_percentile(const void* values, int values_f64, int n, int 
 
 extern "C" int sq_map_category_means(const float* pred, int n, int ld, const int32_t* members, int n_members, const int32_t* offsets,
                                      int n_cat, double* out, sq_stream_t stream_) {
-    SQ_REQUIRE(n >= 1 && n <= SQ_MAP_MAX_ROWS, "map_category_means: n = %d rows, must be in 1..%d", n, SQ_MAP_MAX_ROWS);
+    SQ_REQUIRE_ROWS("map_category_means", n, 1, SQ_MAP_MAX_ROWS);
     SQ_REQUIRE(n_cat >= 1 && n_members >= 0 && ld >= 1, "map_category_means: n_cat = %d (at least 1), n_members = %d (at least 0), ld = %d (at least 1)",
                n_cat, n_members, ld);
     SQ_REQUIRE(pred && offsets && out && (members || n_members == 0), "map_category_means: null pred, members, offsets or out pointer");
     SQ_REQUIRE(((uintptr_t)pred & 3) == 0 && ((uintptr_t)members & 3) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)out & 7) == 0,
                "map_category_means: misaligned pointer");
-    const size_t blocks = ((size_t)n * (size_t)n_cat + 255) / 256;
-    hipLaunchKernelGGL(map_category_means_kernel, dim3((unsigned)(blocks < (size_t)MR_MAX_BLOCKS ? blocks : (size_t)MR_MAX_BLOCKS)), dim3(256), 0,
-                       (hipStream_t)stream_, pred, n, ld, members, offsets, n_cat, out);
+    hipLaunchKernelGGL(map_category_means_kernel, dim3(cs_blocks((size_t)n * (size_t)n_cat, 256)), dim3(256), 0, (hipStream_t)stream_, pred, n, ld,
+                       members, offsets, n_cat, out);
     SQ_LAUNCH_CHECK();
     return SQ_OK;
 }
@@ -407,18 +349,12 @@ extern "C" size_t sq_map_gene_corr_workspace_bytes(int n, int K) {
 
 extern "C" int sq_map_gene_corr(const float* pred, int n, int ld, const int32_t* cols, int K, double* out, void* workspace,
                                 size_t workspace_bytes, sq_stream_t stream_) {
-    SQ_REQUIRE(n >= 2 && n <= SQ_MAP_MAX_ROWS, "map_gene_corr: n = %d rows, must be in 2..%d", n, SQ_MAP_MAX_ROWS);
-    SQ_REQUIRE(K >= 1 && K <= SQ_MAP_MAX_CORR_COLS, "map_gene_corr: K = %d columns, must be in 1..%d", K, SQ_MAP_MAX_CORR_COLS);
-    SQ_REQUIRE(ld >= 1 && (cols || K <= ld), "map_gene_corr: leading dimension ld = %d for K = %d columns%s", ld, K,
-               cols ? "" : " (no column list: K <= ld)");
+    SQ_REQUIRE_TABLE("map_gene_corr", n, 2, SQ_MAP_MAX_ROWS, "K", K, SQ_MAP_MAX_CORR_COLS, ld, cols);
     SQ_REQUIRE(pred && out && workspace, "map_gene_corr: null pred, out or workspace pointer");
     SQ_REQUIRE(((uintptr_t)pred & 3) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)cols & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
                "map_gene_corr: misaligned pointer");
     const McPlan p = mc_plan(n, K);
-    if (workspace_bytes < p.bytes) {
-        sq_set_error("map_gene_corr: workspace %zu < required %zu", workspace_bytes, p.bytes);
-        return SQ_ERR_WORKSPACE;
-    }
+    SQ_REQUIRE_WORKSPACE("map_gene_corr", workspace_bytes, p.bytes);
     hipStream_t st = (hipStream_t)stream_;
     char* const ws = (char*)workspace;
     double* const mean = (double*)(ws + p.off_mean);

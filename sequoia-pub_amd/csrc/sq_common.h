@@ -53,6 +53,41 @@ struct SqDevOnce {
         }                                                                         \
     } while (0)
 
+// The table contract of the slide analytics (mapstats.hip, gtalign.hip): n rows in lo..hi; `count` columns, called `cname` in
+// the entry's signature, at least 1 and at most cmax (0: no maximum); a row-major table of leading dimension ld >= 1 that,
+// without a column list, holds the columns (count <= ld).  One wording for every entry: the tests match these messages.
+static inline bool sq_rows_ok(const char* name, int n, int lo, int hi) {
+    if (n >= lo && n <= hi) return true;
+    sq_set_error("%s: n = %d rows, must be in %d..%d", name, n, lo, hi);
+    return false;
+}
+static inline bool sq_columns_ok(const char* name, const char* cname, int count, int cmax, int ld, const void* cols) {
+    if (count < 1 || (cmax && count > cmax)) {
+        if (cmax) sq_set_error("%s: %s = %d columns, must be in 1..%d", name, cname, count, cmax);
+        else sq_set_error("%s: %s = %d columns, must be at least 1", name, cname, count);
+        return false;
+    }
+    if (ld >= 1 && (cols || count <= ld)) return true;
+    if (cols) sq_set_error("%s: leading dimension ld = %d for %s = %d columns", name, ld, cname, count);
+    else sq_set_error("%s: leading dimension ld = %d for %s = %d columns (no column list: %s <= ld)", name, ld, cname, count, cname);
+    return false;
+}
+#define SQ_REQUIRE_ROWS(...) do { if (!sq_rows_ok(__VA_ARGS__)) return SQ_ERR_ARG; } while (0)
+#define SQ_REQUIRE_COLUMNS(...) do { if (!sq_columns_ok(__VA_ARGS__)) return SQ_ERR_ARG; } while (0)
+#define SQ_REQUIRE_TABLE(name, n, lo, hi, cname, count, cmax, ld, cols)           \
+    do {                                                                          \
+        SQ_REQUIRE_ROWS(name, n, lo, hi);                                         \
+        SQ_REQUIRE_COLUMNS(name, cname, count, cmax, ld, cols);                   \
+    } while (0)
+
+#define SQ_REQUIRE_WORKSPACE(name, have, need)                                    \
+    do {                                                                          \
+        if ((size_t)(have) < (size_t)(need)) {                                    \
+            sq_set_error("%s: workspace %zu < required %zu", name, (size_t)(have), (size_t)(need)); \
+            return SQ_ERR_WORKSPACE;                                              \
+        }                                                                         \
+    } while (0)
+
 #define SQ_LAUNCH_CHECK()                                                         \
     do {                                                                          \
         hipError_t _e = hipGetLastError();                                        \

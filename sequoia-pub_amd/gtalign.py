@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mapstats import MAX_ROWS, _columns, _table, percentile_of_score
+from ._tables import call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table, vector as _vector
+from .mapstats import MAX_ROWS, percentile_of_score
 
 MAX_SPOTS = 1 << 20               # SQ_GT_MAX_SPOTS
 MAX_K = 8                         # SQ_GT_MAX_K
@@ -45,24 +46,6 @@ def unique_chunk_rows():
     return int(_lib.lib().sq_gt_unique_chunk_rows())
 
 
-def _check(rc):
-    """A refused argument (SQ_ERR_ARG) is a ValueError carrying the library's message; anything else a SequoiaHipError."""
-    if rc == -1:
-        raise ValueError(_lib.lib().sq_last_error().decode())
-    _lib.check(rc)
-
-
-def _vector(t, dtype, what):
-    """A device vector [n] of the given dtype, contiguous; integer and float inputs are converted."""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: a torch tensor on the device is expected, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise _lib.SequoiaHipError(f"{what}: the tensor is on {t.device}; it must be a CUDA (ROCm) tensor -- there is no CPU fallback")
-    if t.dim() != 1:
-        raise ValueError(f"{what}: a vector is expected, got shape {tuple(t.shape)}")
-    return t.to(dtype).contiguous()
-
-
 def _neighbour_count(num_tiles):
     if not isinstance(num_tiles, (int, np.integer)) or isinstance(num_tiles, bool) or not 1 <= int(num_tiles) <= MAX_K:
         raise ValueError(f"nearest_spots: num_tiles = {num_tiles!r}, must be an integer in 1..{MAX_K}")
@@ -88,11 +71,9 @@ def nearest_spots(xcoord, ycoord, spot_x, spot_y, num_tiles=4, return_distances=
     if n_tiles and n_spots and bool(torch.stack([torch.isnan(xc).any(), torch.isnan(yc).any(), torch.isnan(sx).any(), torch.isnan(sy).any()]).any()):
         raise ValueError("nearest_spots: a coordinate is NaN")
     k_eff = max(1, min(k, n_spots))
-    idx = torch.empty(max(n_tiles, 1), k_eff, dtype=torch.int32, device=xc.device)[:n_tiles]
-    dist = torch.empty(max(n_tiles, 1), k_eff, dtype=torch.float64, device=xc.device)[:n_tiles] if return_distances else None
-    with torch.cuda.device(xc.device):
-        _check(_lib.lib().sq_gt_nearest_spots(_lib.ptr(xc), _lib.ptr(yc), n_tiles, _lib.ptr(sx), _lib.ptr(sy), n_spots, k, _lib.ptr(idx),
-                                              _lib.ptr(dist), _lib.stream_ptr(xc.device)))
+    idx = _empty(torch.int32, xc.device, n_tiles, k_eff)
+    dist = _empty(torch.float64, xc.device, n_tiles, k_eff) if return_distances else None
+    _call(_lib.lib().sq_gt_nearest_spots, xc.device, xc, yc, n_tiles, sx, sy, n_spots, k, idx, dist)
     return (idx, dist) if return_distances else idx
 
 
@@ -110,10 +91,8 @@ def spot_means(idx, expr, cols=None):
     col_t, C = _columns(cols, width, t.device, "spot_means")
     idx = idx.contiguous()
     n_tiles, k_eff = int(idx.shape[0]), int(idx.shape[1])
-    out = torch.empty(max(n_tiles, 1), max(C, 1), dtype=torch.float64, device=t.device)[:n_tiles, :C]
-    with torch.cuda.device(t.device):
-        _check(_lib.lib().sq_gt_spot_means(_lib.ptr(idx), n_tiles, k_eff, _lib.ptr(t), int(t.dtype == torch.float64), n_spots, ld,
-                                           _lib.ptr(col_t), C, _lib.ptr(out), _lib.stream_ptr(t.device)))
+    out = _empty(torch.float64, t.device, n_tiles, C)
+    _call(_lib.lib().sq_gt_spot_means, t.device, idx, n_tiles, k_eff, t, int(t.dtype == torch.float64), n_spots, ld, col_t, C, out)
     return out
 
 
@@ -152,15 +131,11 @@ def median_filter(values, xtf, ytf, num_neighbors=1, nan_absent=False, cols=None
     xt, yt, grid_w, grid_h = _grid_coordinates(xtf, ytf, n, t.device, "median_filter")
     r = int(num_neighbors)
     L = _lib.lib()
-    need = int(L.sq_gt_median_filter_workspace_bytes(n, grid_w, grid_h))
-    out = torch.empty(max(n, 1), max(C, 1), dtype=torch.float64, device=t.device)[:n, :C]
-    counts = torch.empty(max(n, 1), max(C, 1), dtype=torch.int32, device=t.device)[:n, :C] if return_counts else None
+    out = _empty(torch.float64, t.device, n, C)
+    counts = _empty(torch.int32, t.device, n, C) if return_counts else None
     flag = torch.zeros(8, dtype=torch.uint8, device=t.device)
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        # a refused shape has a workspace size of 0: the call then launches nothing and carries the library's message
-        _check(L.sq_gt_median_filter(_lib.ptr(t), n, ld, _lib.ptr(col_t), C, _lib.ptr(xt), _lib.ptr(yt), grid_w, grid_h, r, int(bool(nan_absent)),
-                                     _lib.ptr(out), _lib.ptr(counts), _lib.ptr(flag), _lib.ptr(ws), need, _lib.stream_ptr(t.device)))
+    _call(L.sq_gt_median_filter, t.device, t, n, ld, col_t, C, xt, yt, grid_w, grid_h, r, int(bool(nan_absent)), out, counts, flag,
+          workspace=int(L.sq_gt_median_filter_workspace_bytes(n, grid_w, grid_h)))
     if int(flag[0].item()):
         raise ValueError("median_filter: two rows share a grid cell (one row per tile is expected)")
     if torch.is_tensor(values) and values.dim() == 1:
@@ -176,11 +151,8 @@ def count_unique(values, cols=None):
     t, n, width, ld = _table(values, (torch.float64,), "count_unique")
     col_t, C = _columns(cols, width, t.device, "count_unique")
     L = _lib.lib()
-    need = int(L.sq_gt_count_unique_workspace_bytes(n, C))
-    out = torch.empty(max(C, 1), dtype=torch.int32, device=t.device)[:C]
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        _check(L.sq_gt_count_unique(_lib.ptr(t), n, ld, _lib.ptr(col_t), C, _lib.ptr(out), _lib.ptr(ws), need, _lib.stream_ptr(t.device)))
+    out = _empty(torch.int32, t.device, C)
+    _call(L.sq_gt_count_unique, t.device, t, n, ld, col_t, C, out, workspace=int(L.sq_gt_count_unique_workspace_bytes(n, C)))
     return out
 
 
@@ -218,20 +190,9 @@ def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_
     gene_cols = _gene_columns(gene_names, genes)
     if not torch.is_tensor(spot_expr) or spot_expr.dim() != 2 or spot_expr.shape[1] != len(genes):
         raise ValueError(f"align_ground_truth: spot_expr does not have one column per requested gene ({len(genes)})")
-    n = int(pred.shape[0])
-    keep = ~torch.isnan(pred).any(dim=1)
-    coords = []
-    for name, c in (("xcoord", xcoord), ("ycoord", ycoord), ("xcoord_tf", xtf), ("ycoord_tf", ytf)):
-        c = torch.as_tensor(np.array(c)) if not torch.is_tensor(c) else c
-        c = c.to(pred.device)
-        if c.shape != (n,):
-            raise ValueError(f"align_ground_truth: {name} has shape {tuple(c.shape)}, expected ({n},)")
-        if c.is_floating_point():
-            keep &= ~torch.isnan(c)
-        coords.append((name, c))
-    rows = torch.nonzero(keep).squeeze(1)
-    m = int(rows.numel())
-    frame = OrderedDict((name, c[rows].cpu().numpy()) for name, c in coords)
+    rows, named = _kept_rows(pred, (("xcoord", xcoord), ("ycoord", ycoord), ("xcoord_tf", xtf), ("ycoord_tf", ytf)), "align_ground_truth")
+    n, m = int(pred.shape[0]), int(rows.numel())
+    frame = OrderedDict((name, c[rows].cpu().numpy()) for name, c in named.items())
     if m == 0:
         for g in genes:
             for col in (g, g + "_ground_truth", g + "_ground_truth_filt", g + "_filt"):
@@ -239,7 +200,6 @@ def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_
         counts = pd.DataFrame({"gene": genes, "nr_gt_vals": [0] * len(genes), "nr_gt_vals_filt": [0] * len(genes)})
         return pd.DataFrame(frame, index=rows.cpu().numpy()), counts
     kept = pred if m == n else pred[rows]
-    named = dict(coords)
     idx = nearest_spots(named["xcoord"][rows], named["ycoord"][rows], spot_x, spot_y, num_tiles=k)
     gt = spot_means(idx, spot_expr)
     filt = median_filter(gt, named["xcoord_tf"][rows], named["ycoord_tf"][rows], num_neighbors=1, nan_absent=True)

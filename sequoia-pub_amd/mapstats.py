@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tables import call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table
 
 MAX_ROWS = 262144                 # SQ_MAP_MAX_ROWS
 MAX_CORR_COLS = 32768             # SQ_MAP_MAX_CORR_COLS
@@ -35,46 +36,6 @@ def rank_chunk_rows():
     return int(_lib.lib().sq_map_rank_chunk_rows())
 
 
-def _table(t, dtypes, what):
-    """A device tensor [n, C] whose rows are contiguous -> (tensor, n, C, ld); a column becomes [n, 1]."""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{what}: a torch tensor on the device is expected, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise _lib.SequoiaHipError(f"{what}: the tensor is on {t.device}; it must be a CUDA (ROCm) tensor -- there is no CPU fallback")
-    if t.dtype not in dtypes:
-        raise ValueError(f"{what}: dtype {t.dtype}, expected one of {[str(d) for d in dtypes]}")
-    if t.dim() == 1:
-        t = t.unsqueeze(1)
-    if t.dim() != 2:
-        raise ValueError(f"{what}: a [n, C] table is expected, got shape {tuple(t.shape)}")
-    n, C = t.shape
-    if n > 0 and C > 0 and not (t.stride(1) == 1 and (n == 1 or t.stride(0) >= C)):
-        t = t.contiguous()
-    ld = max(int(t.stride(0)), C, 1) if n > 1 else max(C, 1)
-    return t, int(n), int(C), ld
-
-
-def _columns(cols, width, device, what):
-    """A column list -> (int32 device tensor or None, count); every index is checked against the table's width first."""
-    if cols is None:
-        return None, width
-    idx = cols.detach().cpu().numpy() if torch.is_tensor(cols) else np.asarray(cols)
-    if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
-        raise ValueError(f"{what}: cols must be a 1-D list of integer column indices")
-    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= width):
-        bad = int(idx[(idx < 0) | (idx >= width)][0])
-        raise ValueError(f"{what}: column index {bad} is outside the table's {width} columns")
-    return torch.as_tensor(idx.astype(np.int32)).to(device), int(idx.size)
-
-
-def _refused(call, t):
-    """A shape whose workspace size is 0 is one the library refuses: make the call with a workspace of 0 bytes -- nothing can
-    be launched -- so that the error carries the library's own message."""
-    dummy = torch.empty(8, dtype=torch.uint8, device=t.device)
-    _lib.check(call(_lib.ptr(dummy)))
-    raise _lib.SequoiaHipError("the library reports no workspace size for this shape")
-
-
 def percentile_of_score(values, cols=None, return_argmax=False):
     """``scipy.stats.percentileofscore(column, x)`` (kind='rank') for every element x of every column, bit-equal to scipy
     (gbm_celltype_analysis.py:12-16,107; get_emd.py:21-25,172,175).  values: f32 or f64 device tensor [n, width] (or [n]);
@@ -86,15 +47,10 @@ def percentile_of_score(values, cols=None, return_argmax=False):
     col_t, C = _columns(cols, width, t.device, "percentile_of_score")
     f64 = int(t.dtype == torch.float64)
     L = _lib.lib()
-    need = int(L.sq_map_percentile_workspace_bytes(n, C, f64))
-    if not need:
-        _refused(lambda d: L.sq_map_percentile(_lib.ptr(t), f64, n, ld, _lib.ptr(col_t), C, 0.0, d, None, d, 0, _lib.stream_ptr(t.device)), t)
-    out = torch.empty(n, C, dtype=torch.float64, device=t.device)
-    arg = torch.empty(n, dtype=torch.int32, device=t.device) if return_argmax else None
-    ws = torch.empty(need, dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(L.sq_map_percentile(_lib.ptr(t), f64, n, ld, _lib.ptr(col_t), C, 50.0 / n, _lib.ptr(out), _lib.ptr(arg),
-                                       _lib.ptr(ws), need, _lib.stream_ptr(t.device)))
+    out = _empty(torch.float64, t.device, n, C)
+    arg = _empty(torch.int32, t.device, n) if return_argmax else None
+    scale = 50.0 / n if n else 0.0                          # no rows: the call is refused whatever the scale
+    _call(L.sq_map_percentile, t.device, t, f64, n, ld, col_t, C, scale, out, arg, workspace=int(L.sq_map_percentile_workspace_bytes(n, C, f64)))
     return (out, arg) if return_argmax else out
 
 
@@ -124,10 +80,8 @@ def category_means(pred, categories):
     n_cat = len(offsets) - 1
     mem_t = torch.as_tensor(members).to(t.device) if members.size else None
     off_t = torch.as_tensor(offsets).to(t.device)
-    out = torch.empty(n, n_cat, dtype=torch.float64, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.lib().sq_map_category_means(_lib.ptr(t), n, ld, _lib.ptr(mem_t), int(members.size), _lib.ptr(off_t), n_cat,
-                                                    _lib.ptr(out), _lib.stream_ptr(t.device)))
+    out = _empty(torch.float64, t.device, n, n_cat)
+    _call(_lib.lib().sq_map_category_means, t.device, t, n, ld, mem_t, int(members.size), off_t, n_cat, out)
     return out
 
 
@@ -139,12 +93,8 @@ def gene_correlation(pred, cols=None):
     col_t, K = _columns(cols, width, t.device, "gene_correlation")
     L = _lib.lib()
     need = int(L.sq_map_gene_corr_workspace_bytes(n, K))
-    if not need:
-        _refused(lambda d: L.sq_map_gene_corr(_lib.ptr(t), n, ld, _lib.ptr(col_t), K, d, d, 0, _lib.stream_ptr(t.device)), t)
-    out = torch.empty(K, K, dtype=torch.float64, device=t.device)
-    ws = torch.empty(need, dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(L.sq_map_gene_corr(_lib.ptr(t), n, ld, _lib.ptr(col_t), K, _lib.ptr(out), _lib.ptr(ws), need, _lib.stream_ptr(t.device)))
+    out = _empty(torch.float64, t.device, *((K, K) if need else (1, 1)))      # a refused K may be too many columns to square
+    _call(L.sq_map_gene_corr, t.device, t, n, ld, col_t, K, out, workspace=need)
     return out
 
 
@@ -170,19 +120,8 @@ def celltype_maps(pred, gene_names, categories, xtf=None, ytf=None, colors=None)
     index_lists = category_indices(gene_names, categories)
     if pred.dim() != 2 or pred.shape[1] != len(gene_names):
         raise ValueError(f"celltype_maps: pred {tuple(pred.shape)} does not have one column per gene name ({len(gene_names)})")
-    keep = ~torch.isnan(pred).any(dim=1)
-    coords = []
-    for name, c in (("xcoord_tf", xtf), ("ycoord_tf", ytf)):
-        if c is not None:
-            c = torch.as_tensor(np.asarray(c)) if not torch.is_tensor(c) else c
-            c = c.to(pred.device)
-            if c.shape != (pred.shape[0],):
-                raise ValueError(f"celltype_maps: {name} has shape {tuple(c.shape)}, expected ({pred.shape[0]},)")
-            if c.is_floating_point():
-                keep &= ~torch.isnan(c)
-            coords.append((name, c))
-    rows = torch.nonzero(keep).squeeze(1)
-    frame = OrderedDict((name, c[rows].cpu().numpy()) for name, c in coords)
+    rows, coords = _kept_rows(pred, (("xcoord_tf", xtf), ("ycoord_tf", ytf)), "celltype_maps")
+    frame = OrderedDict((name, c[rows].cpu().numpy()) for name, c in coords.items())
     if rows.numel() == 0:
         for label in labels:
             frame[label] = np.zeros(0)

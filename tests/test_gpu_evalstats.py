@@ -50,6 +50,24 @@ def test_full_gene_panel_vs_oracle_columns(n):
         np.testing.assert_allclose(s[0][cols][ok], ref[ok], rtol=1e-9, atol=1e-12)
 
 
+@pytest.mark.parametrize("n", [2, 3, 256, 257, 512, 513, 8192])
+def test_quantiles_at_the_edges_of_the_sort_network(n):
+    """256 threads take one pair each up to n = 512; 8192 samples are the most a column may have (32 KiB of LDS).  Few
+    distinct values, so most compare-exchanges meet a tie, and -0.0 beside 0.0."""
+    _lib.require_gpu()
+    G = 8
+    rs = np.random.RandomState(1000 + n)
+    real = (rs.randint(-3, 4, size=(n, G)) * 0.25).astype(np.float32)
+    real[rs.rand(n, G) < 0.3] = -0.0
+    real[0, :4], real[1, :4] = 0.0, -0.0
+    pred, rnd = rs.rand(n, G).astype(np.float32), rs.rand(n, G).astype(np.float32)
+    s, _ = evalstats.device_stats(real, pred, rnd)
+    r64 = real.astype(np.float64)
+    assert np.signbit(real[real == 0]).any() and not np.signbit(real[real == 0]).all() and np.isfinite(real).all()
+    np.testing.assert_allclose(s[6], np.quantile(r64, 0.25, axis=0), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(s[7], np.quantile(r64, 0.75, axis=0), rtol=1e-12, atol=1e-12)
+
+
 def test_rejects_oversized_or_mismatched_tables():
     _lib.require_gpu()
     a = np.zeros((9000, 8), np.float32)

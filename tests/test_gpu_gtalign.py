@@ -120,6 +120,18 @@ def test_count_unique_of_several_columns_through_a_column_list():
     assert gtalign.count_unique(t[:, :3]).cpu().numpy().tolist() == gc.count_unique(table[:, :3]).tolist()          # ld = 5 > C = 3
 
 
+@pytest.mark.parametrize("name", ["many", "border"])
+def test_count_unique_equals_the_distinct_percentiles_across_chunk_borders(name):
+    """Both calls sort the same chunks with the same kernel; a value's percentile is strictly increasing in the value."""
+    _lib.require_gpu()
+    from sequoia_pub_amd import mapstats
+    v = gc.unique_cases()[name]
+    x = _dev(v[~np.isnan(v)])
+    assert len(x) > gtalign.unique_chunk_rows() == mapstats.rank_chunk_rows()
+    perc = mapstats.percentile_of_score(x)[:, 0].cpu().numpy()
+    assert int(gtalign.count_unique(x)[0]) == len(np.unique(perc)) == len(np.unique(v[~np.isnan(v)]))
+
+
 def _whole_frames():
     w = gc.whole_case()
     return gtalign.align_ground_truth(_dev(w["pred"]), gc.WHOLE_NAMES, _dev(w["xcoord"]), _dev(w["ycoord"]), w["xtf"], w["ytf"],

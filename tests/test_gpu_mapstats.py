@@ -255,6 +255,17 @@ def test_refusals_come_from_the_library_and_launch_nothing():
         mapstats.gene_correlation(x.double())
 
 
+def test_a_refused_shape_is_the_same_error_from_every_wrapper():
+    _lib.require_gpu()
+    from sequoia_pub_amd import gtalign
+    empty = torch.zeros(0, dtype=torch.float64, device="cuda")
+    for call, message in ((lambda: mapstats.percentile_of_score(empty), "n = 0 rows"), (lambda: gtalign.count_unique(empty), "n = 0 rows"),
+                          (lambda: mapstats.gene_correlation(torch.zeros(2, 32769, device="cuda")), "K = 32769")):
+        with pytest.raises(_lib.SequoiaHipArgError, match=message) as err:
+            call()
+        assert isinstance(err.value, _lib.SequoiaHipError) and isinstance(err.value, ValueError)
+
+
 def test_non_default_stream_and_the_largest_row_count():
     _lib.require_gpu()
     x = mc.percentile_input(2 * mapstats.rank_chunk_rows() + 37, 2, np.float32, 56)

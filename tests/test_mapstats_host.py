@@ -244,6 +244,17 @@ def test_cpu_tensor_raises_not_falls_back():
             call()
 
 
+def test_a_refused_argument_is_a_library_error_and_a_value_error():
+    assert issubclass(_lib.SequoiaHipArgError, _lib.SequoiaHipError) and issubclass(_lib.SequoiaHipArgError, ValueError)
+    L = _lib.lib()
+    assert L.sq_map_category_means(None, 0, 1, None, 0, None, 1, None, None) == -1          # refused before any pointer is looked at
+    with pytest.raises(_lib.SequoiaHipArgError, match="libsequoia_hip error -1: map_category_means: n = 0 rows"):
+        _lib.check(-1)
+    with pytest.raises(_lib.SequoiaHipError) as other:
+        _lib.check(-3)
+    assert not isinstance(other.value, ValueError)
+
+
 def test_library_exports_the_map_statistics():
     L = _lib.lib()
     for name in ("sq_map_rank_chunk_rows", "sq_map_percentile_workspace_bytes", "sq_map_percentile", "sq_map_category_means",
