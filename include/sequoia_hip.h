@@ -697,6 +697,77 @@ size_t sq_gt_count_unique_workspace_bytes(int n, int C);
 int sq_gt_count_unique(const double* values, int n, int ld, const int32_t* cols, int C, int32_t* out, void* workspace,
                        size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Earth mover's distance: the number spatial_vis/get_emd.py exists for (get_emd.py:54-90,180-189) -- the grid fill and
+ * shift of :180-188, calculate_emd's conventions and normalisation (:71-82) and, in place of cv2.EMD (:86), the optimum of
+ * the balanced transportation problem between the two weighted cell sets, in f64, with an optimality certificate: a
+ * feasible flow and feasible duals of equal objective.  cv2.EMD casts its signatures to float32 and stops at its own
+ * epsilon: it approximates this number and does not define it.  P independent problems per call, ONE WORKGROUP PER
+ * PROBLEM, no workgroup ever waits on another; every sum in a fixed order, no floating-point atomics: two calls give the
+ * same bytes.  Every argument is checked before the first launch; the calls are asynchronous on `stream` and never
+ * synchronise.  sq_emd_workspace_bytes keeps the invariant stated under "Map statistics".
+ * Every pointer is a device pointer, with ONE exception: sq_emd_status_check reads the statuses from HOST memory (the
+ * caller has downloaded them, which is the synchronisation the entries themselves never make) and only formats
+ * sq_last_error.
+ *
+ *   sq_emd_fill  : :180-188 for P problems over one slide's table rows.  Problem p compares column cols_a[p] of a f64
+ *                  [n, lda] with column cols_b[p] of b f64 [n, ldb] (NULL: column p); xtf, ytf int32 [n] grid coordinates
+ *                  in [0, grid_h) x [0, grid_w) (arr[x, y]: x indexes the grid's rows).  nan_absent = 1: a row that is NaN
+ *                  in either column is absent from that problem (the per-gene dropna of :166).  Over the present rows:
+ *                  H = max x + 1, W = max y + 1 -> dims[p] = (H, W); both grids start from zeros, arr[x, y] = value, then
+ *                  arr + abs(min(arr)) with the min over the WHOLE H x W grid, empty cells included -- with a negative
+ *                  minimum every empty cell becomes positive; literal, not guarded.  grids f64 [P, 2, cells] (cells >=
+ *                  grid_h grid_w, row-major H_p x W_p at the front of each plane).  No present row: dims (0, 0).  Two
+ *                  present rows in one cell, or a coordinate outside the grid, set the caller-zeroed byte flag[0]; the
+ *                  results are then not to be used.  workspace: P cells int32 (the owners' row numbers).
+ *   sq_emd_solve : calculate_emd (:67-90) for P pairs of dense non-negative f64 grids [P, 2, cells] with dims int32 [P, 2]
+ *                  = (H_p, W_p), H_p, W_p <= SQ_EMD_MAX_DIM (a device-side check; status below).  Both grids all zero ->
+ *                  0.0; exactly one -> NaN (:71-79; an empty grid is all zero).  Otherwise each grid is divided by its f64
+ *                  sum and the cells with weight > 0 are kept in row-major order (cv2 skips zero-weight entries): na
+ *                  source cells, nb sink cells, each <= cap_cells <= SQ_EMD_MAX_CELLS.  The ground distance of two cells is
+ *                  sqrt((double)(dx dx + dy dy)) of their integer indices, computed on the fly (no n x m matrix).
+ *                  Successive shortest augmenting paths: duals u = 0, v_j = min_i c_ij; Dijkstra from a source with supply
+ *                  left over the sink columns, sq_emd_column_chunk() columns per pass of the workgroup, the columns'
+ *                  labels, duals and arc lists' heads and the rows' duals in LDS -- relax every column from the newly scanned rows, argmin
+ *                  over the unfinalised columns (lowest index on ties), follow that column's flow arcs back to unscanned
+ *                  rows; stop at the first column with demand left, add D - dist to the potentials, augment by the
+ *                  minimum of the remaining supply, the remaining demand and the backward flows of the path.
+ *                  Bounded work: at most max_aug augmentations (0: SQ_EMD_DEFAULT_AUGMENTATIONS (na + nb)) and arc_cap live arcs; reaching either
+ *                  ends THAT problem with its status, and the entry's caller reads the text from sq_emd_status_text.
+ *                  Outputs per problem (row strides cap_cells / arc_cap): value f64 (:88-89's norm is the caller's);
+ *                  status int32 (SQ_EMD_OK, or the first bound met); counts int32 [P, 8] = (na, nb, augmentations, arc
+ *                  slots used, search steps, 0, 0, 0 -- all eight written by the kernel); cell_a, cell_b int32 (the kept cells' row-major indices x W + y); w_a, w_b f64 weights;
+ *                  u, v f64 duals; arc_i, arc_j int32 and arc_f f64: slot s holds a flow arc (source i, sink j, flow) if
+ *                  arc_f > 0 and is free if 0.0.  u_i + v_j <= c_ij for all pairs, equality on the arcs, and
+ *                  value = sum flow c = u . w_a + v . w_b, all up to f64 rounding.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_EMD_MAX_CELLS 4096          /* positive cells per map */
+#define SQ_EMD_MAX_DIM 16384           /* grid extent (a cell's coordinates pack into 2 x 16 bits with room) */
+#define SQ_EMD_MAX_GRID_CELLS 16777216 /* H x W of one dense grid */
+#define SQ_EMD_MAX_PROBLEMS 65536
+#define SQ_EMD_DEFAULT_AUGMENTATIONS 256 /* x (na + nb): the default cap on augmentations of one problem */
+#define SQ_EMD_MAX_ARCS 16384          /* arc slots per problem: 2 (na + nb) at the cell limit */
+#define SQ_EMD_OK 0
+#define SQ_EMD_TOO_MANY_CELLS 1        /* a map has more than cap_cells cells of positive weight */
+#define SQ_EMD_AUGMENTATION_CAP 2      /* max_aug augmentations made and supply is left */
+#define SQ_EMD_ARC_CAP 3               /* the flow needs more than arc_cap arcs */
+#define SQ_EMD_BAD_GRID 4              /* an extent outside 0..SQ_EMD_MAX_DIM, H W > cells, or a negative / non-finite sum */
+#define SQ_EMD_NO_PATH 5               /* a search ended without reaching demand (not reachable with finite weights) */
+int sq_emd_column_chunk(void);
+const char* sq_emd_status_text(int status);
+/* status_host: the P statuses copied to the HOST.  SQ_OK if all are SQ_EMD_OK; otherwise SQ_ERR_UNSUPPORTED, and
+ * sq_last_error names the first problem that is not and says why. */
+int sq_emd_status_check(const int32_t* status_host, int P);
+size_t sq_emd_fill_workspace_bytes(int P, int cells);
+int sq_emd_fill(const double* a, int lda, const int32_t* cols_a, const double* b, int ldb, const int32_t* cols_b, int n,
+                const int32_t* xtf, const int32_t* ytf, int P, int nan_absent, int grid_h, int grid_w, int cells, double* grids,
+                int32_t* dims, uint8_t* flag, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+size_t sq_emd_workspace_bytes(int P, int cap_cells, int arc_cap);
+int sq_emd_solve(const double* grids, int cells, const int32_t* dims, int P, int cap_cells, int arc_cap, int max_aug,
+                 double* value, int32_t* status, int32_t* counts, int32_t* cell_a, double* w_a, int32_t* cell_b, double* w_b,
+                 double* u, double* v, int32_t* arc_i, int32_t* arc_j, double* arc_f, void* workspace, size_t workspace_bytes,
+                 sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

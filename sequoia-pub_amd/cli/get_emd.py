@@ -1,4 +1,4 @@
-"""Counterpart of the reference's spatial_vis/get_emd.py (whose paths are hard-coded) up to the EMD: a predicted slide's
+"""Counterpart of the reference's spatial_vis/get_emd.py (whose paths are hard-coded): a predicted slide's
 ``stride-1.csv`` (what cli.visualize writes) is aligned with the slide's spatial-transcriptomics spots on the device
 (gtalign.py) -- per gene the mean expression of every tile's four nearest spots, its 3 x 3 median over the tile grid, the
 percentiles of both and of the prediction within the slide, and the number of distinct ground-truth values.
@@ -9,9 +9,12 @@ percentiles of both and of the prediction within the slide, and the number of di
 Keeps the reference's four flags (with its path conventions as defaults) and adds --pred_csv and --out as explicit paths
 and --ground_truth: a CSV with the columns ``x``, ``y`` and one ALREADY NORMALISED column per gene (the reference reads an
 .h5ad and normalises it with scanpy: normalize_total, log1p, scale -- that stays with the caller).  Writes
-``<out>/metrics.csv`` (gene, nr_gt_vals, nr_gt_vals_filt: the reference's file without its two emd columns) and
-``<out>/aligned.csv``, the per-tile frame of ``gtalign.align_ground_truth``.  The EMD itself and the figures stay out
-(DESIGN.md section 7)."""
+``<out>/metrics.csv`` (gene, nr_gt_vals, nr_gt_vals_filt) and ``<out>/aligned.csv``, the per-tile frame of
+``gtalign.align_ground_truth``.  With --emd, metrics.csv is the reference's file: gene, emd, nr_gt_vals, emd_filt,
+nr_gt_vals_filt -- the earth mover's distance between the predicted and the measured map, raw and as median-filtered
+percentiles (emd.py: the optimum of the transportation problem in f64, where the reference calls cv2.EMD) -- and the
+reference's line of ``slide_info.txt`` (:198-201: slide, grid rows squared, tiles of the first gene) is appended under
+--out.  The figures stay out."""
 import argparse
 import os
 
@@ -34,6 +37,8 @@ def build_parser():
     ap.add_argument("--pred_csv", default=None, help="the slide's stride-1.csv (default: from --slide_nr and --pred_folder, as the reference)")
     ap.add_argument("--out", default=None, help="output folder (default: from --slide_nr and --save_folder, as the reference)")
     ap.add_argument("--ground_truth", required=True, help="CSV with the columns x, y and one already-normalised column per gene")
+    ap.add_argument("--emd", action="store_true", help="also compute emd and emd_filt per gene and append the slide's line to slide_info.txt")
+    ap.add_argument("--max_augmentations", type=int, default=None, help="with --emd: the cap on augmenting paths of one problem (default: 256 per cell of the two maps)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -59,6 +64,16 @@ def gene_list(gene_names):
     return gene_names.split(",")
 
 
+def write_slide_info(args, pred_csv, out, tiles, first_gene):
+    """get_emd.py:198-201, once per slide: its name, arr0.shape[0] * arr1.shape[0] of the first gene's grid and that gene's
+    number of tiles."""
+    name = "HRI_" + str(args.slide_nr) + "_T.tif" if args.slide_nr is not None else os.path.basename(os.path.dirname(os.path.abspath(pred_csv)))
+    present = tiles[~np.isnan(tiles[first_gene + "_ground_truth"].values)]
+    height = int(present["xcoord_tf"].max()) + 1 if len(present) else 0
+    with open(os.path.join(out, "slide_info.txt"), "a") as file:
+        file.write(f"{name} \t {height * height} \t {len(present)} \n")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     pred_csv, out = resolve_paths(args)
@@ -75,8 +90,11 @@ def main(argv=None):
     tiles, metrics = gtalign.align_ground_truth(
         dev(pred[names].values, np.float32), names, dev(pred["xcoord"].values, np.float64), dev(pred["ycoord"].values, np.float64),
         dev(pred["xcoord_tf"].values, np.float64), dev(pred["ycoord_tf"].values, np.float64),
-        dev(truth["x"].values, np.float64), dev(truth["y"].values, np.float64), dev(truth[genes].values, np.float64), genes, num_tiles=NUM_TILES)
+        dev(truth["x"].values, np.float64), dev(truth["y"].values, np.float64), dev(truth[genes].values, np.float64), genes, num_tiles=NUM_TILES,
+        emd=args.emd, max_augmentations=args.max_augmentations)
     os.makedirs(out, exist_ok=True)
+    if args.emd:
+        write_slide_info(args, pred_csv, out, tiles, genes[0])
     metrics.to_csv(os.path.join(out, "metrics.csv"))
     tiles.to_csv(os.path.join(out, "aligned.csv"))
     print("Done")

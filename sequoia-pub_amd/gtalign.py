@@ -7,8 +7,9 @@ for every gene, and filters the result with a pandas scan per row.  The nearest 
 are found once (``nearest_spots``) and serve every gene through a gather (``spot_means``); the 3 x 3 median over the
 sparse tile grid (``median_filter``) and the distinct-value counts (``count_unique``) take all genes in one call.  Every
 result equals the reference's own call bit for bit (NaN signs and payloads aside).  Tensors live on the device and there
-is no CPU fallback.  The EMD itself (cv2.EMD, with the grid fill and the normalisation in front of it) and the figures
-stay out."""
+is no CPU fallback.  The EMD itself -- the grid fill, the normalisation and the transportation problem the reference hands
+to cv2.EMD -- is emd.py (csrc/emd.hip); ``align_ground_truth(..., emd=True)`` adds its two columns.  The figures stay out
+(DESIGN.md section 7)."""
 import ctypes
 from collections import OrderedDict
 
@@ -166,7 +167,7 @@ def _gene_columns(gene_names, genes):
     return [where[g] for g in genes]
 
 
-def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_y, spot_expr, genes, num_tiles=4):
+def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_y, spot_expr, genes, num_tiles=4, emd=False, max_augmentations=None):
     """get_emd.py:163-175 and :204-205 for all requested genes of one slide at once.
 
     pred: f32 device tensor [n_tiles, G] whose columns are ``gene_names``; xcoord, ycoord: the tiles' pixel coordinates and
@@ -179,7 +180,13 @@ def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_
     Returns two DataFrames: per tile, indexed by the kept rows' positions, xcoord, ycoord, xcoord_tf, ycoord_tf and per
     gene ``<gene>`` (the prediction), ``<gene>_ground_truth``, ``<gene>_ground_truth_filt`` (the percentile of the filtered
     ground truth) and ``<gene>_filt`` (the percentile of the prediction), NaN where the gene's ground truth is NaN; and
-    per gene ``gene, nr_gt_vals, nr_gt_vals_filt``: the distinct values of the two ground-truth columns."""
+    per gene ``gene, nr_gt_vals, nr_gt_vals_filt``: the distinct values of the two ground-truth columns.
+
+    emd=True: the second frame carries the reference's columns in its merge order (:213-222), ``gene, emd, nr_gt_vals,
+    emd_filt, nr_gt_vals_filt``: ``emd`` is the earth mover's distance (emd.emd_maps: :177-194) between the prediction and
+    ``ground_truth`` over the gene's rows, ``emd_filt`` between ``<gene>_filt`` and ``ground_truth_filt``; all genes and
+    both variants are solved in one batched call; max_augmentations is emd_maps' cap on the augmenting paths of one problem
+    (None: its default).  Without emd every output is what it was."""
     import pandas as pd
     k = _neighbour_count(num_tiles)
     genes = list(genes)
@@ -198,6 +205,9 @@ def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_
             for col in (g, g + "_ground_truth", g + "_ground_truth_filt", g + "_filt"):
                 frame[col] = np.zeros(0)
         counts = pd.DataFrame({"gene": genes, "nr_gt_vals": [0] * len(genes), "nr_gt_vals_filt": [0] * len(genes)})
+        if emd:
+            counts.insert(1, "emd", np.nan)
+            counts.insert(3, "emd_filt", np.nan)
         return pd.DataFrame(frame, index=rows.cpu().numpy()), counts
     kept = pred if m == n else pred[rows]
     idx = nearest_spots(named["xcoord"][rows], named["ycoord"][rows], spot_x, spot_y, num_tiles=k)
@@ -236,4 +246,11 @@ def align_ground_truth(pred, gene_names, xcoord, ycoord, xtf, ytf, spot_x, spot_
         frame[g + "_ground_truth_filt"] = pg_h[:, j]
         frame[g + "_filt"] = pp_h[:, j]
     counts = pd.DataFrame({"gene": genes, "nr_gt_vals": nr_gt, "nr_gt_vals_filt": nr_filt})
+    if emd:                                                 # raw and percentile maps of every gene: 2 G problems, one call
+        from .emd import emd_maps
+        G = len(genes)
+        dist = emd_maps(torch.cat([pred_cols, perc_pred], dim=1), torch.cat([gt, perc_gt], dim=1), named["xcoord_tf"][rows],
+                        named["ycoord_tf"][rows], nan_absent=True, max_augmentations=max_augmentations).cpu().numpy()
+        counts.insert(1, "emd", dist[:G])
+        counts.insert(3, "emd_filt", dist[G:])
     return pd.DataFrame(frame, index=rows.cpu().numpy()), counts
