@@ -256,8 +256,31 @@ int sq_kmeans_fit_large(const float* X, int n_samples, int dim, int n_clusters, 
                         int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
                         int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
+/* The same fit for n_slides slides of DIFFERENT patch counts in one call: what the loop over slides of
+ * kmean_features.py:65-108 computes, one fit per slide, for a whole group of them (compute_features_hdf5.py writes however
+ * many patches passed the tissue filter, so the slides of a cohort never share a count and sq_kmeans_fit cannot batch them).
+ * X f32 [sum n_samples, dim] holds the slides' rows back to back in list order, labels i32 [sum n_samples] likewise;
+ * cluster_features f32 [S, k, dim], seed_indices i32 [S, k], n_iter i32 [S] (each may be NULL).
+ * n_samples and first_centers are HOST arrays [S] (first_centers[s] = RandomState(seed).choice(n_samples[s])); uniforms is
+ * the ONE device table f64 [n_clusters-1, n_local_trials] -- the MT19937 uniforms do not depend on the patch count.  The
+ * entry sizes its grids and offsets from the host arrays and copies them into a descriptor table of its own before it
+ * returns: both may be reused or freed as soon as the call returns.
+ * Contract: for every slide, labels, seed_indices, n_iter and cluster_features are bit-equal to those of sq_kmeans_fit
+ * (n_slides = 1) on that slide alone, whatever the other slides of the call are and wherever it sits in the list (each
+ * slide is seeded with the kernel layout sq_kmeans_fit picks for its own n_samples; no padding rows exist).
+ * Valid for 1 <= n_slides <= 4096, n_clusters <= n_samples[s] <= 4096 for every slide, n_clusters <= 256, dim % 4 == 0,
+ * 0 <= first_centers[s] < n_samples[s], 1 <= n_local_trials <= 8; anything else is refused before anything is launched with
+ * an sq_last_error message that names the bound (the sizes are checked before the device pointers, so a caller can ask
+ * with NULL data), a short workspace with SQ_ERR_WORKSPACE.  sq_kmeans_ragged_workspace_bytes returns 0 for a shape the
+ * entry refuses.  Synchronises the stream between Lloyd bursts, once for all slides of the call. */
+size_t sq_kmeans_ragged_workspace_bytes(int n_slides, const int32_t* n_samples /*host [S]*/, int dim, int n_clusters);
+int sq_kmeans_fit_ragged(const float* X, int n_slides, const int32_t* n_samples /*host [S]*/, int dim, int n_clusters,
+                         const int32_t* first_centers /*host [S]*/, const double* uniforms, int n_local_trials, int max_iter,
+                         double tol, int32_t* labels, float* cluster_features, int32_t* seed_indices, int32_t* n_iter,
+                         void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
 /* ------------------------------------------------------------------------------
- * ResNet-50 patch embedding  (src/resnet.py:155-170 forward_extract; :73-93 Bottleneck;
+ * ResNet-50 patch embedding (src/resnet.py:155-170 forward_extract; :73-93 Bottleneck;
  * :98-136 topology; eval-mode BN; patch transform pre_processing/compute_features_hdf5.py:49-51,119-120)
  * Weights are packed by the caller per sq_resnet50_layout: conv i at w_off (elements) as
  * [cout][kh][kw][cin] (conv 0: K = 147 zero-padded to k_padded = 152) with eval-mode BatchNorm

@@ -129,6 +129,10 @@ def _declare(lib):
     lib.sq_kmeans_large_workspace_bytes.argtypes = [i32, i32, i32]
     lib.sq_kmeans_fit_large.restype = i32
     lib.sq_kmeans_fit_large.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, ctypes.c_double, vp, vp, vp, vp, vp, sz, vp]
+    lib.sq_kmeans_ragged_workspace_bytes.restype = sz
+    lib.sq_kmeans_ragged_workspace_bytes.argtypes = [i32, vp, i32, i32]
+    lib.sq_kmeans_fit_ragged.restype = i32
+    lib.sq_kmeans_fit_ragged.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, i32, ctypes.c_double, vp, vp, vp, vp, vp, sz, vp]
     lib.sq_resnet50_layout_init.restype = i32
     lib.sq_resnet50_layout_init.argtypes = [ctypes.POINTER(ResNet50Layout)]
     lib.sq_resnet50_workspace_bytes.restype = sz

@@ -1,7 +1,8 @@
 """Cluster tokens -- counterpart of /root/reference/pre_processing/kmean_features.py (same flags; appends
 dataset ``cluster_features`` [num_clusters, D] to the slide's feature file, skipping slides that have it or
 have fewer patches than clusters).  KMeans + the per-label means run in ``sq_kmeans_fit`` (``sq_kmeans_fit_large``
-for a slide of more than 4096 patches)."""
+for a slide of more than 4096 patches); ``--batch_slides N`` clusters up to N slides of any patch counts per call
+(``sq_kmeans_fit_ragged``) and writes the same bytes."""
 import argparse
 import os
 
@@ -10,7 +11,7 @@ import torch
 
 from .. import store
 from ..data import shard_rows
-from ..kmeans import kmeans_fit
+from ..kmeans import kmeans_fit, kmeans_fit_ragged
 from .common import init_distributed, ref_frame, seed_everything
 
 
@@ -27,6 +28,8 @@ def main(argv=None):
     parser.add_argument('--gtex_tissue', type=str, default=None)
     parser.add_argument('--seed', type=int, default=99)
     parser.add_argument('--feat_name', type=str, default='resnet_features', help="dataset to cluster (the reference hard-codes 'resnet_features', :80)")
+    parser.add_argument('--batch_slides', type=int, default=1,
+                        help="slides clustered per k-Means call (1: one call per slide; N > 1: up to N slides of any patch counts in one call, same output)")
     args = parser.parse_args(argv)
     seed_everything(args.seed)
     rank, world, device = init_distributed()
@@ -34,6 +37,24 @@ def main(argv=None):
     first_project = df.iloc[0]['tcga_project'] if len(df) else None
     lo, hi = shard_rows(df.shape[0], rank, world)
     df = df.iloc[lo:hi]
+    pending = []                                         # --batch_slides > 1: (WSI, open file, features) waiting for their call
+
+    def write(WSI, f, cluster_features):
+        try:
+            f.create_dataset("cluster_features", data=cluster_features)
+        except Exception as e:
+            print(f"{WSI}: Error in creating cluster_feauture")
+            print(e)
+        f.close()
+
+    def flush():
+        if pending:
+            r = kmeans_fit_ragged([torch.from_numpy(x).to(device) for _, _, x in pending], args.num_clusters, random_state=0)
+            means = r["cluster_features"].cpu().numpy()
+            for i, (name, f, _) in enumerate(pending):
+                write(name, f, means[i])
+            pending.clear()
+
     for _, row in df.iterrows():
         WSI = row['wsi_file_name']
         if args.gtex:
@@ -61,13 +82,16 @@ def main(argv=None):
             print(f'{WSI}: Cluster feature already available')
             f.close()
             continue
+        if args.batch_slides > 1:
+            if pending and pending[0][2].shape[1:] != features.shape[1:]:
+                flush()                                  # one call takes one feature width
+            pending.append((WSI, f, features))
+            if len(pending) >= args.batch_slides:
+                flush()
+            continue
         r = kmeans_fit(torch.from_numpy(features).to(device), args.num_clusters, random_state=0)
-        try:
-            f.create_dataset("cluster_features", data=r["cluster_features"][0].cpu().numpy())
-        except Exception as e:
-            print(f"{WSI}: Error in creating cluster_feauture")
-            print(e)
-        f.close()
+        write(WSI, f, r["cluster_features"][0].cpu().numpy())
+    flush()
     print('Done!')
 
 

@@ -2,6 +2,8 @@
 uses (``sklearn.cluster.KMeans(n_clusters, random_state=0).fit(X).labels_``) plus the cluster-mean
 step of :99-108, on the HIP k-means kernels (``sq_kmeans_fit``; ``sq_kmeans_fit_large`` for slides of more
 than ``GRAM_MAX_ROWS`` patches, which a raised ``--max_patch_number`` produces: compute_features_hdf5.py:26,112-113).
+``kmeans_fit_ragged`` is the loop over slides around it (kmean_features.py:65-108): slides of different patch counts in one
+``sq_kmeans_fit_ragged`` call, every slide bit-equal to its own ``kmeans_fit``.
 
 The only host arithmetic is the data-independent MT19937 draw sequence of scikit-learn's
 ``_kmeans_plusplus`` (``RandomState(random_state).choice(n, p=uniform)`` then ``uniform(size=2+log k)``
@@ -114,6 +116,119 @@ def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_m
     if not large:
         return kmeans_fit_batch(X.unsqueeze(0), n_clusters, random_state, max_iter, tol, want_means)
     return _fit_large(X, n_clusters, random_state, max_iter, tol, want_means)
+
+
+RAGGED_MAX_SLIDES = 4096      # slides per sq_kmeans_fit_ragged call
+
+_first_cache = {}
+
+
+def _first_center(n_samples, n_clusters, random_state):
+    """The first centre of a slide of n_samples patches: the only draw of seeding_draws that depends on the patch count
+    (the uniforms behind it are the same table for every n), cached per n on the host."""
+    key = (int(n_samples), int(n_clusters), int(random_state))
+    hit = _first_cache.get(key)
+    if hit is None:
+        if len(_first_cache) >= 8192:
+            _first_cache.clear()
+        hit = _first_cache[key] = seeding_draws(n_samples, n_clusters, random_state)[0]
+    return hit
+
+
+def _ragged_bytes(counts, D, k):
+    arr = np.ascontiguousarray(counts, dtype=np.int32)
+    return int(_lib.lib().sq_kmeans_ragged_workspace_bytes(len(arr), arr.ctypes.data, int(D), int(k)))
+
+
+def ragged_plan(counts, D, n_clusters, max_workspace_bytes):
+    """Pure host: cut a list of patch counts, in order, into consecutive groups (lo, hi, route), slides lo..hi-1 per call.
+    route "gram": one sq_kmeans_fit_ragged call whose workspace (sq_kmeans_ragged_workspace_bytes) fits
+    max_workspace_bytes -- a single slide that alone exceeds the budget is still run, alone; route "large": ONE slide of
+    more than GRAM_MAX_ROWS patches, which goes through sq_kmeans_fit_large by itself."""
+    counts = [int(c) for c in counts]
+    groups = []
+    lo = 0
+    while lo < len(counts):
+        if counts[lo] > GRAM_MAX_ROWS:
+            groups.append((lo, lo + 1, "large"))
+            lo += 1
+            continue
+        if _ragged_bytes(counts[lo:lo + 1], D, n_clusters) == 0:
+            raise ValueError(f"kmeans (ragged): slide {lo} with n_samples={counts[lo]}, dim={D}, n_clusters={n_clusters} is outside "
+                             f"what sq_kmeans_fit_ragged takes (n_clusters <= n_samples, n_clusters <= 256, dim % 4 == 0)")
+        hi = lo + 1
+        while (hi < len(counts) and hi - lo < RAGGED_MAX_SLIDES and counts[hi] <= GRAM_MAX_ROWS
+               and 0 < _ragged_bytes(counts[lo:hi + 1], D, n_clusters) <= max_workspace_bytes):
+            hi += 1
+        groups.append((lo, hi, "gram"))
+        lo = hi
+    return groups
+
+
+def kmeans_fit_ragged(slides, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_means=True,
+                      max_workspace_bytes=4 << 30):
+    """Many slides of DIFFERENT patch counts in one call (the loop over slides of kmean_features.py:65-108).
+    slides: a list of f32 [n_i, D] CUDA tensors, or a pair (X_cat [sum n_i, D], counts).  Returns, in the order of the
+    input: labels -- a list of i32 [n_i] views of one buffer; cluster_features f32 [S, k, D] (None without want_means);
+    indices i32 [S, k]; n_iter i32 [S].  Every slide's results are bit-equal to kmeans_fit of that slide alone.
+
+    ragged_plan cuts the list into consecutive groups whose workspace fits max_workspace_bytes, one
+    sq_kmeans_fit_ragged call per group; a slide of more than GRAM_MAX_ROWS patches runs alone through the large-slide
+    entry.  The 4 GiB default is a choice, not a measurement: the Gram and distance tables take 12 bytes per pair of
+    patches, about 0.2 GB for a 4000-patch slide, so the default holds some twenty of the largest slides
+    compute_features_hdf5.py writes, or hundreds of ordinary ones."""
+    _lib.require_gpu()
+    if isinstance(slides, tuple) and len(slides) == 2 and torch.is_tensor(slides[0]):
+        X, counts = slides[0], [int(c) for c in slides[1]]
+        if not X.is_cuda:
+            raise _lib.SequoiaHipError("kmeans_fit_ragged needs CUDA tensors (no CPU fallback)")
+        if X.dim() != 2 or sum(counts) != X.shape[0]:
+            raise ValueError(f"kmeans_fit_ragged: X_cat {tuple(X.shape)} does not hold counts summing to {sum(counts)}")
+    else:
+        slides = list(slides)
+        for t in slides:
+            if not t.is_cuda:
+                raise _lib.SequoiaHipError("kmeans_fit_ragged needs CUDA tensors (no CPU fallback)")
+            if t.dim() != 2:
+                raise ValueError(f"kmeans_fit_ragged takes slides [n_i, D], got shape {tuple(t.shape)}")
+        if len({int(t.shape[1]) for t in slides}) > 1:
+            raise ValueError(f"kmeans_fit_ragged: slides of different feature widths {sorted({int(t.shape[1]) for t in slides})}")
+        counts = [int(t.shape[0]) for t in slides]
+        X = torch.cat([t.to(torch.float32) for t in slides]) if slides else None
+    if not counts:
+        raise ValueError("kmeans_fit_ragged: empty list of slides")
+    for i, n in enumerate(counts):
+        if n < n_clusters:
+            raise ValueError(f"slide {i}: n_samples={n} should be >= n_clusters={n_clusters}.")
+    X = X.to(torch.float32).contiguous()
+    S, D, k, dev = len(counts), int(X.shape[1]), int(n_clusters), X.device
+    plan = ragged_plan(counts, D, k, max_workspace_bytes)
+    rows = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    labels = torch.empty(int(rows[-1]), dtype=torch.int32, device=dev)
+    means = torch.empty(S, k, D, dtype=torch.float32, device=dev) if want_means else None
+    seeds = torch.empty(S, k, dtype=torch.int32, device=dev)
+    n_iter = torch.empty(S, dtype=torch.int32, device=dev)
+    _, u_dev, trials = _device_draws(counts[0], k, random_state, dev)      # one table: the uniforms do not depend on n
+    L = _lib.lib()
+    for lo, hi, route in plan:
+        r0, r1 = int(rows[lo]), int(rows[hi])
+        if route == "large":
+            r = _fit_large(X[r0:r1], k, random_state, max_iter, tol, want_means)
+            labels[r0:r1] = r["labels"][0]
+            seeds[lo] = r["indices"][0]
+            n_iter[lo] = r["n_iter"][0]
+            if want_means:
+                means[lo] = r["cluster_features"][0]
+            continue
+        ns = np.ascontiguousarray(counts[lo:hi], dtype=np.int32)
+        firsts = np.array([_first_center(n, k, random_state) for n in ns], dtype=np.int32)
+        need = int(L.sq_kmeans_ragged_workspace_bytes(hi - lo, ns.ctypes.data, D, k))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.sq_kmeans_fit_ragged(_lib.ptr(X[r0:r1]), hi - lo, ns.ctypes.data, D, k, firsts.ctypes.data, _lib.ptr(u_dev), trials,
+                                              max_iter, float(tol), _lib.ptr(labels[r0:r1]), _lib.ptr(means[lo:hi]) if want_means else None,
+                                              _lib.ptr(seeds[lo:hi]), _lib.ptr(n_iter[lo:hi]), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+    return dict(labels=[labels[int(rows[i]):int(rows[i + 1])] for i in range(S)], cluster_features=means, indices=seeds, n_iter=n_iter)
 
 
 class KMeans:

@@ -9,7 +9,7 @@ kept on the device between stages (BASELINE config 3)."""
 import torch
 
 from . import _lib
-from .kmeans import GRAM_MAX_ROWS, kmeans_fit, kmeans_fit_batch
+from .kmeans import GRAM_MAX_ROWS, kmeans_fit, kmeans_fit_batch, kmeans_fit_ragged
 
 
 class SlidePipeline:
@@ -28,7 +28,12 @@ class SlidePipeline:
     @torch.no_grad()
     def cluster(self, features):
         """[S, n, D] f32 -> (cluster_features [S, 100, D], labels [S, n]).  Slides of more than GRAM_MAX_ROWS patches go
-        through kmeans_fit one at a time (the large-slide kernels take one slide per call)."""
+        through kmeans_fit one at a time (the large-slide kernels take one slide per call).
+        A list of [n_i, D] tensors (slides of different patch counts) goes through kmeans_fit_ragged and returns
+        (cluster_features [S, 100, D], list of labels [n_i])."""
+        if isinstance(features, (list, tuple)):
+            r = kmeans_fit_ragged(list(features), self.n_clusters, random_state=0)
+            return r["cluster_features"], r["labels"]
         if features.dim() == 3 and features.shape[1] > GRAM_MAX_ROWS:
             rs = [kmeans_fit(f, self.n_clusters, random_state=0) for f in features]
             return torch.cat([r["cluster_features"] for r in rs]), torch.cat([r["labels"] for r in rs])
