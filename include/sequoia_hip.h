@@ -234,6 +234,11 @@ int sq_window_vote(const float* win_pred, int n_windows, int num_outputs, const 
  * Outputs (device): labels i32 [S, n]; cluster_features f32 [S, k, dim] (may be NULL);
  * seed_indices i32 [S, k] (may be NULL); n_iter i32 [S] (may be NULL).
  * Synchronises the stream between Lloyd bursts (the stop decision is read on the host).
+ * The three entries below share one driver and one set of kernels: a call's slides lie back to back and a slide table
+ * in the workspace says where each starts.  They differ in how that table is filled -- n_slides equal slides, one slide
+ * of up to 65536 patches, or slides of different patch counts -- and in their bounds.  Common to all: n_clusters <= 256,
+ * dim a multiple of 4, 1 <= n_local_trials <= 8; the sizes are checked before the device pointers and anything refused
+ * leaves an sq_last_error message that names the bound; a short workspace gives SQ_ERR_WORKSPACE.
  * ---------------------------------------------------------------------------- */
 size_t sq_kmeans_workspace_bytes(int n_slides, int n_samples, int dim, int n_clusters);
 int sq_kmeans_fit(const float* X, int n_slides, int n_samples, int dim, int n_clusters, int first_center,
@@ -244,9 +249,8 @@ int sq_kmeans_fit(const float* X, int n_slides, int n_samples, int dim, int n_cl
 /* The same fit for ONE slide of any size up to SQ_KMEANS_LARGE_MAX_SAMPLES = 65536 patches (kmean_features.py:96-108 on
  * a slide made with a raised --max_patch_number, compute_features_hdf5.py:26,112-113; sq_kmeans_fit stops at 4096).
  * Same arithmetic, arguments and outputs as sq_kmeans_fit with n_slides = 1; the k-means++ seeding forms only the
- * distances of a step's candidates (no n x n Gram matrix) and the member lists come from a chunked counting sort,
- * the Lloyd iteration is the one sq_kmeans_fit runs.  Valid for every n_clusters <= n_samples <= 65536 (small slides
- * included), n_clusters <= 256, dim % 4 == 0; anything else is refused with an sq_last_error message that names the bound.
+ * distances of a step's candidates (no n x n Gram matrix) and the member lists come from a chunked counting sort.
+ * Valid for every n_clusters <= n_samples <= 65536 (small slides included).
  * sq_kmeans_large_workspace_bytes returns 0 when n_samples is outside [1, 65536] (or dim / n_clusters < 1).
  * Synchronises the stream between Lloyd bursts (the stop decision is read on the host); the seeding adds no
  * synchronisation. */
@@ -263,16 +267,14 @@ int sq_kmeans_fit_large(const float* X, int n_samples, int dim, int n_clusters, 
  * cluster_features f32 [S, k, dim], seed_indices i32 [S, k], n_iter i32 [S] (each may be NULL).
  * n_samples and first_centers are HOST arrays [S] (first_centers[s] = RandomState(seed).choice(n_samples[s])); uniforms is
  * the ONE device table f64 [n_clusters-1, n_local_trials] -- the MT19937 uniforms do not depend on the patch count.  The
- * entry sizes its grids and offsets from the host arrays and copies them into a descriptor table of its own before it
- * returns: both may be reused or freed as soon as the call returns.
+ * entry copies the host arrays into its slide table before it returns: both may be reused or freed as soon as the call
+ * returns.
  * Contract: for every slide, labels, seed_indices, n_iter and cluster_features are bit-equal to those of sq_kmeans_fit
- * (n_slides = 1) on that slide alone, whatever the other slides of the call are and wherever it sits in the list (each
- * slide is seeded with the kernel layout sq_kmeans_fit picks for its own n_samples; no padding rows exist).
- * Valid for 1 <= n_slides <= 4096, n_clusters <= n_samples[s] <= 4096 for every slide, n_clusters <= 256, dim % 4 == 0,
- * 0 <= first_centers[s] < n_samples[s], 1 <= n_local_trials <= 8; anything else is refused before anything is launched with
- * an sq_last_error message that names the bound (the sizes are checked before the device pointers, so a caller can ask
- * with NULL data), a short workspace with SQ_ERR_WORKSPACE.  sq_kmeans_ragged_workspace_bytes returns 0 for a shape the
- * entry refuses.  Synchronises the stream between Lloyd bursts, once for all slides of the call. */
+ * (n_slides = 1) on that slide alone, whatever the other slides of the call are and wherever it sits in the list (the
+ * seeding kernel's layout follows each slide's own n_samples; no padding rows exist).
+ * Valid for 1 <= n_slides <= 4096, n_clusters <= n_samples[s] <= 4096 and 0 <= first_centers[s] < n_samples[s] for every
+ * slide; a caller can ask with NULL data why a shape is refused.  sq_kmeans_ragged_workspace_bytes returns 0 for a shape
+ * the entry refuses.  Synchronises the stream between Lloyd bursts, once for all slides of the call. */
 size_t sq_kmeans_ragged_workspace_bytes(int n_slides, const int32_t* n_samples /*host [S]*/, int dim, int n_clusters);
 int sq_kmeans_fit_ragged(const float* X, int n_slides, const int32_t* n_samples /*host [S]*/, int dim, int n_clusters,
                          const int32_t* first_centers /*host [S]*/, const double* uniforms, int n_local_trials, int max_iter,

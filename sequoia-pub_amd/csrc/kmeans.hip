@@ -13,12 +13,13 @@
 //     sums in index order, fl32(sum/count), empty-cluster relocation, centre-shift / label stop rule
 //   * cluster means of the ORIGINAL features: member rows added in index order in fp32, / count
 // One workgroup per slide runs the whole seeding loop; slides are independent (grid dimension).
-// Slides of more than 4096 points (compute_features_hdf5.py:26,112-113: --max_patch_number is the user's) take
-// sq_kmeans_fit_large: the same arithmetic without the n x n Gram matrix -- a seeding step forms only its candidates'
-// distances, `closest` lives in global memory, member lists come from a chunked counting sort (section 5 below); the
-// Lloyd loop is one function for both entries.
-// Slides of DIFFERENT row counts (each <= 4096) share one call through sq_kmeans_fit_ragged (section 6): rows back to
-// back, a per-slide descriptor table instead of the uniform n, the same kernels and the same Lloyd function.
+// A call's slides lie back to back and are described by ONE slide table in device memory (KmSlide), which every kernel
+// that touches per-point data reads.  One driver (km_fit, section 6) stands behind the three entries, which differ in
+// how the table is filled: sq_kmeans_fit S equal slides, sq_kmeans_fit_ragged slides of different row counts (each
+// <= 4096), sq_kmeans_fit_large one slide of up to 65536 points (compute_features_hdf5.py:26,112-113:
+// --max_patch_number is the user's).  The large route keeps the arithmetic without the n x n Gram matrix -- a seeding
+// step forms only its candidates' distances, `closest` lives in global memory, member lists come from a chunked
+// counting sort (section 5); centring, the centre gather and the Lloyd loop are the same launches for all three.
 #include "../../include/sequoia_hip.h"
 #include "sq_common.h"
 
@@ -40,31 +41,26 @@ struct KmState {          // per slide, device memory
     double shift;         // sum of squared centre shifts of the current iteration
 };
 
-// Where slide s keeps its rows and its n x n tables.  Every kernel that touches per-point data takes one of the two:
-// KmUniform: S slides of n rows each at strides s * n (sq_kmeans_fit, sq_kmeans_fit_large);
-// KmRagged:  slides of different row counts back to back, described by a device table (sq_kmeans_fit_ragged).
-// Buffers linear in n (Xc, labels, labels_old, members, dist, the dots planes) start at row(s) times their row width,
-// G and dist32 at gram(s); buffers sized per slide ([S][k]...) are indexed by s alone in both.
-struct KmSlide {          // one entry of the ragged descriptor table, device memory
+// Where slide s keeps its rows and its n x n tables: one entry of the call's slide table (device memory), which every
+// kernel that touches per-point data reads.  The slides lie back to back: buffers linear in n (Xc, labels, labels_old,
+// members, dist, the dots planes) start at `row` times their row width, G and dist32 at `gram`; buffers sized per slide
+// ([S][k]...) are indexed by s alone.
+struct KmSlide {
     int n;                // rows of the slide
     int first;            // its first centre
-    long long row;        // rows of the slides before it
-    long long gram;       // elements of their n x n tables (each rounded up to 4: 16-byte rows for the seeding loads)
+    size_t row;           // rows of the slides before it
+    size_t gram;          // elements of their n x n tables (each rounded up to 4: 16-byte rows for the seeding loads)
 };
-struct KmUniform {
-    static constexpr bool ragged = false;
-    int rows;
-    __device__ __forceinline__ int n(int) const { return rows; }
-    __device__ __forceinline__ size_t row(int s) const { return (size_t)s * rows; }
-    __device__ __forceinline__ size_t gram(int s) const { return (size_t)s * rows * rows; }
-};
-struct KmRagged {
-    static constexpr bool ragged = true;
-    const KmSlide* tab;
-    __device__ __forceinline__ int n(int s) const { return tab[s].n; }
-    __device__ __forceinline__ size_t row(int s) const { return (size_t)tab[s].row; }
-    __device__ __forceinline__ size_t gram(int s) const { return (size_t)tab[s].gram; }
-};
+static inline size_t km_gram_elems(int n) { return sq_align_up((size_t)n * n, 4); }
+
+// The table of S equal slides and, behind it, the identity list (every slide is of one seeding class), filled where
+// they are read: a lone slide's call is too short to pay for a host block and its copy.
+__global__ void km_equal_table_kernel(KmSlide* __restrict__ tab, int* __restrict__ list, int S, int n, int first, size_t gram) {
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {
+        tab[s] = KmSlide{n, first, (size_t)s * n, (size_t)s * gram};
+        list[s] = s;
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // block-wide helpers (blockDim.x multiple of 64, <= 1024)
@@ -144,16 +140,16 @@ __device__ __forceinline__ void block_reduce_sum_n_int(int (&v)[T], int* sh /*[1
 // fp32 sum is then taken by one wave from LDS, row after row.  The fp64 moments only feed `tol`: every thread sums
 // its own rows, the four row-lanes of a column are combined in a fixed order.
 constexpr int KC_ROWS = 128, KC_COLS = 64;
-template <class Geo>
-__global__ __launch_bounds__(256) void km_center_kernel(const float* __restrict__ X, float* __restrict__ Xc, double* __restrict__ colvar, Geo geo, int D) {
+__global__ __launch_bounds__(256) void km_center_kernel(const float* __restrict__ X, float* __restrict__ Xc, double* __restrict__ colvar,
+                                                        const KmSlide* __restrict__ tab, int D) {
     __shared__ float tile[KC_ROWS][KC_COLS];
     __shared__ double part[4][KC_COLS];
     __shared__ float mean_s[KC_COLS];
     const int col = threadIdx.x & 63, rl = threadIdx.x >> 6;        // column inside the block, row-lane 0..3
     const int d = blockIdx.x * KC_COLS + col;
     const bool dok = d < D;
-    const int n = geo.n(blockIdx.y);
-    const size_t base = geo.row(blockIdx.y) * D;
+    const int n = tab[blockIdx.y].n;
+    const size_t base = tab[blockIdx.y].row * D;
     float acc = 0.f;                                                 // wave 0 only: the fp32 column sum, rows in order
     double s64 = 0.0;
     for (int r0 = 0; r0 < n; r0 += KC_ROWS) {
@@ -220,28 +216,23 @@ __global__ void km_tol_kernel(const double* __restrict__ colvar, KmState* __rest
 // ksl > 1: the contraction is cut into ksl slices (grid z = slide * ksl + slice), slice partials land in consecutive
 // C planes and the consumer adds them in slice order (short products -- 100 centres x 1000 points -- otherwise run on
 // 32 blocks with 64 dependent K steps each).
-// Ragged geometry: B holds the slides' rows back to back and N is the grid's (largest) row count; slide s multiplies
-// its own n_s rows -- with themselves into its Gram matrix (sym), or with its M centres (A, stride sA) into its ksl
-// planes of [M][n_s] behind those of the slides before it -- and blocks beyond n_s return at once.
-template <class Geo>
+// B holds the slides' rows back to back and N is the grid's (largest) row count; slide s multiplies its own n_s rows --
+// with themselves into its Gram matrix (sym), or with its M centres (A, stride sA) into its ksl planes of [M][n_s]
+// behind those of the slides before it -- and blocks beyond n_s return at once.
 __global__ __launch_bounds__(256) void km_dgemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                           double* __restrict__ C, int M, int N, int K, long long sA,
-                                                          long long sB, long long sC, int ksl, int sym, Geo geo) {
+                                                          int ksl, int sym, const KmSlide* __restrict__ tab) {
     // sym: A == B (Gram matrix): only the blocks on and above the diagonal are computed, each also stores its mirror
     // image -- bit-exact, the products commute and the K order is the same on both sides of the diagonal
     if (sym && blockIdx.x < blockIdx.y) return;
     __shared__ double sa[32][64 + 2];
     __shared__ double sb[32][64 + 2];
     const int slide = blockIdx.z / ksl, slice = blockIdx.z - slide * ksl;
-    if constexpr (Geo::ragged) {
-        N = geo.n(slide);
-        B += geo.row(slide) * K;
-        if (sym) { M = N; A = B; C += geo.gram(slide); }
-        else { A += (long long)slide * sA; C += (size_t)ksl * M * geo.row(slide) + (size_t)slice * M * N; }
-        if ((int)blockIdx.x * 64 >= N || (int)blockIdx.y * 64 >= M) return;
-    } else {
-        A += (long long)slide * sA; B += (long long)slide * sB; C += (long long)blockIdx.z * sC;
-    }
+    N = tab[slide].n;
+    B += tab[slide].row * K;
+    if (sym) { M = N; A = B; C += tab[slide].gram; }
+    else { A += (long long)slide * sA; C += (size_t)ksl * M * tab[slide].row + (size_t)slice * M * N; }
+    if ((int)blockIdx.x * 64 >= N || (int)blockIdx.y * 64 >= M) return;
     const int kper = ((K + ksl - 1) / ksl + 31) / 32 * 32;
     const int k_lo = slice * kper, k_hi = min(K, k_lo + kper);
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
@@ -318,12 +309,12 @@ __global__ __launch_bounds__(256) void km_dgemm_nt_kernel(const float* __restric
 // (d = -2 X.Y^T; d += XX; d += YY in fp64 from the Gram matrix; cast fp32; max(., 0)), row c = distances from point c.
 // The seeding kernel then reads 4-byte distances (16 bytes per thread and candidate) instead of rebuilding them from
 // 8-byte Gram entries inside its 99 dependent steps.
-template <class Geo>
-__global__ __launch_bounds__(256) void km_dist_f32_kernel(const double* __restrict__ Gall, float* __restrict__ Dall, Geo geo) {
-    const int c = blockIdx.x, n = geo.n(blockIdx.y);
+__global__ __launch_bounds__(256) void km_dist_f32_kernel(const double* __restrict__ Gall, float* __restrict__ Dall,
+                                                          const KmSlide* __restrict__ tab) {
+    const int c = blockIdx.x, n = tab[blockIdx.y].n;
     if (c >= n) return;
-    const double* G = Gall + geo.gram(blockIdx.y);
-    float* Dm = Dall + geo.gram(blockIdx.y);
+    const double* G = Gall + tab[blockIdx.y].gram;
+    float* Dm = Dall + tab[blockIdx.y].gram;
     const double gcc = G[(size_t)c * n + c];
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
         double d = -2.0 * G[(size_t)c * n + j];
@@ -339,11 +330,29 @@ __global__ __launch_bounds__(256) void km_dist_f32_kernel(const double* __restri
 // step parity, so each costs a single barrier; the candidate distances stay in registers and the winner's are reused
 // for the `closest` update (no second read of G).  Arithmetic (scan association, reduction orders) is unchanged from
 // the first version of this kernel, results are bit-identical.
-// The loop itself is km_seed_slide: one slide's distance table and output row; the two kernels below only say which
-// slide a block seeds.
+// Block b seeds slide list[b].  The fp64 partial sums behind fl32(potential) associate by PTS and the block size, so a
+// launch covers the slides of ONE seeding class: the row of KM_SEED_LAYOUTS their row count selects.
+struct KmSeedLayout { int max_rows, pts, threads; };
+constexpr KmSeedLayout KM_SEED_LAYOUTS[] = {
+    {1024, 4, 256},       // 4 waves x 4 points per thread: cheaper barriers and wave exchanges than 16 waves
+    {2048, 2, 1024},
+    {4096, 4, 1024},
+};
+constexpr int KM_SEED_CLASSES = sizeof(KM_SEED_LAYOUTS) / sizeof(KM_SEED_LAYOUTS[0]);
+int km_seed_class(int n) {          // the first row that holds n rows; larger slides (the large route) are not seeded from a list
+    int c = 0;
+    while (c < KM_SEED_CLASSES - 1 && n > KM_SEED_LAYOUTS[c].max_rows) ++c;
+    return c;
+}
+
 template <int PTS>   // points per thread (n <= PTS * blockDim.x)
-__device__ __forceinline__ void km_seed_slide(const float* __restrict__ Dm, const double* __restrict__ uniforms, int first, int n,
-                                              int k, int trials, int* __restrict__ out) {
+__global__ __launch_bounds__(KM_THREADS) void km_seed_kernel(const float* __restrict__ Dall, const double* __restrict__ uniforms,
+                                                             const KmSlide* __restrict__ tab, const int* __restrict__ list, int k,
+                                                             int trials, int* __restrict__ seeds) {
+    const int slide = list[blockIdx.x];
+    const float* __restrict__ Dm = Dall + tab[slide].gram;
+    const int first = tab[slide].first, n = tab[slide].n;
+    int* __restrict__ out = seeds + (size_t)slide * k;
     __shared__ double sh[2][16 * KM_MAX_TRIALS];
     __shared__ int shi[2][16 * KM_MAX_TRIALS];
     __shared__ double scan_w[2][16];
@@ -477,29 +486,12 @@ __device__ __forceinline__ void km_seed_slide(const float* __restrict__ Dm, cons
     }
 }
 
-template <int PTS>
-__global__ __launch_bounds__(KM_THREADS) void km_seed_kernel(const float* __restrict__ Dall, const double* __restrict__ uniforms,
-                                                             int first, int n, int k, int trials, int* __restrict__ seeds) {
-    km_seed_slide<PTS>(Dall + (size_t)blockIdx.x * n * n, uniforms, first, n, k, trials, seeds + (size_t)blockIdx.x * k);
-}
-
-// Ragged call: block b seeds slide list[b].  The fp64 partial sums behind fl32(potential) associate by PTS and the block
-// size, so a launch covers the slides of ONE seeding class (km_seed_class) with the layout sq_kmeans_fit gives them.
-template <int PTS>
-__global__ __launch_bounds__(KM_THREADS) void km_seed_ragged_kernel(const float* __restrict__ Dall, const double* __restrict__ uniforms,
-                                                                    const KmSlide* __restrict__ tab, const int* __restrict__ list, int k,
-                                                                    int trials, int* __restrict__ seeds) {
-    const int s = list[blockIdx.x];
-    km_seed_slide<PTS>(Dall + (size_t)tab[s].gram, uniforms, tab[s].first, tab[s].n, k, trials, seeds + (size_t)s * k);
-}
-
-template <class Geo>
 __global__ void km_gather_centers_kernel(const float* __restrict__ Xc, const int* __restrict__ seeds, float* __restrict__ centers,
-                                         Geo geo, int D, int k) {
+                                         const KmSlide* __restrict__ tab, int D, int k) {
     const int c = blockIdx.x, s = blockIdx.y;
     const int src = seeds[(size_t)s * k + c];
     for (int d = threadIdx.x; d < D; d += blockDim.x)
-        centers[((size_t)s * k + c) * D + d] = Xc[(geo.row(s) + src) * D + d];
+        centers[((size_t)s * k + c) * D + d] = Xc[(tab[s].row + src) * D + d];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -528,9 +520,9 @@ __global__ __launch_bounds__(64) void km_center_norms_kernel(const float* __rest
 
 // labels[j] = argmin_c (|c|^2 - 2 x_j.c), strict '<' (first minimum); dots from the fp64 GEMM as ksl planes of
 // [k centres][n points] (a thread walks the centres of ITS point: consecutive threads read consecutive doubles)
-template <class Geo>
 __global__ __launch_bounds__(1024) void km_assign_kernel(const double* __restrict__ dots, const double* __restrict__ cnorm, int* __restrict__ labels,
-                                                         const KmState* __restrict__ st, Geo geo, int D, int k, int force, int ksl) {
+                                                         const KmState* __restrict__ st, const KmSlide* __restrict__ tab, int D, int k,
+                                                         int force, int ksl) {
     // block = 64 points x 16 centre groups (wave g walks centres [g*k/16, (g+1)*k/16) of its 64 points, all of their
     // slice loads in flight together); the partial minima are merged in centre order, which keeps the first minimum
     constexpr int G = 16, CB = 7;
@@ -539,7 +531,7 @@ __global__ __launch_bounds__(1024) void km_assign_kernel(const double* __restric
     __shared__ int blab[G][64];
     const int s = blockIdx.y;
     if (st[s].done && !force) return;
-    const int n = geo.n(s);
+    const int n = tab[s].n;
     if ((int)blockIdx.x * 64 >= n) return;
     for (int c = threadIdx.x; c < k; c += blockDim.x) cn[c] = cnorm[(size_t)s * k + c];
     __syncthreads();
@@ -547,7 +539,7 @@ __global__ __launch_bounds__(1024) void km_assign_kernel(const double* __restric
     const int j = blockIdx.x * 64 + lane;
     const int c_lo = g * k / G, c_hi = (g + 1) * k / G;
     const size_t plane = (size_t)k * n;
-    const double* dr = dots + (size_t)ksl * k * geo.row(s) + (j < n ? j : 0);
+    const double* dr = dots + (size_t)ksl * k * tab[s].row + (j < n ? j : 0);
     double best = 0.0;
     int lab = -1;
     for (int c0 = c_lo; c0 < c_hi; c0 += CB) {
@@ -577,22 +569,21 @@ __global__ __launch_bounds__(1024) void km_assign_kernel(const double* __restric
 #pragma unroll
         for (int q = 1; q < G; ++q)
             if (blab[q][lane] >= 0 && (l < 0 || bval[q][lane] < b)) { b = bval[q][lane]; l = blab[q][lane]; }
-        labels[geo.row(s) + j] = l;
+        labels[tab[s].row + j] = l;
     }
 }
 
 // counting sort of point ids by label, stable in the point index: members[off[c] .. off[c+1])
 // (n <= 4096: one workgroup, labels in LDS; larger slides: km_lg_hist / km_lg_offsets / km_lg_scatter)
-template <class Geo>
 __global__ __launch_bounds__(KM_THREADS) void km_members_kernel(const int* __restrict__ labels, int* __restrict__ members,
-                                                                int* __restrict__ offsets, const KmState* __restrict__ st, Geo geo,
-                                                                int k, int force) {
+                                                                int* __restrict__ offsets, const KmState* __restrict__ st,
+                                                                const KmSlide* __restrict__ tab, int k, int force) {
     __shared__ int slab[4096];
     __shared__ int soff[KM_MAX_K + 1];
     const int s = blockIdx.x;
     if (st[s].done && !force) return;
-    const int n = geo.n(s);
-    const size_t r0 = geo.row(s);
+    const int n = tab[s].n;
+    const size_t r0 = tab[s].row;
     for (int j = threadIdx.x; j < n; j += blockDim.x) slab[j] = labels[r0 + j];
     __syncthreads();
     for (int c = threadIdx.x; c < k; c += blockDim.x) {
@@ -616,13 +607,12 @@ __global__ __launch_bounds__(KM_THREADS) void km_members_kernel(const int* __res
 }
 
 // sums[c, d] = sum over members (index order) of Xc in fp64
-template <class Geo>
 __global__ void km_sums_kernel(const float* __restrict__ Xc, const int* __restrict__ members, const int* __restrict__ offsets,
-                               double* __restrict__ sums, const KmState* __restrict__ st, Geo geo, int D, int k) {
+                               double* __restrict__ sums, const KmState* __restrict__ st, const KmSlide* __restrict__ tab, int D, int k) {
     const int c = blockIdx.x, s = blockIdx.y;
     if (st[s].done) return;
     const int lo = offsets[(size_t)s * (k + 1) + c], hi = offsets[(size_t)s * (k + 1) + c + 1];
-    const size_t r0 = geo.row(s);
+    const size_t r0 = tab[s].row;
     const int* mem = members + r0;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         double a = 0.0;
@@ -640,19 +630,18 @@ __global__ void km_sums_kernel(const float* __restrict__ Xc, const int* __restri
 }
 
 // _relocate_empty_clusters_dense (_k_means_common.pyx:167-211), one workgroup per slide; rare path
-template <class Geo>
 __global__ __launch_bounds__(KM_THREADS) void km_relocate_kernel(const float* __restrict__ Xc, const float* __restrict__ centers,
                                                                  const int* __restrict__ labels, int* __restrict__ offsets,
                                                                  double* __restrict__ sums, double* __restrict__ weights,
                                                                  double* __restrict__ dist_ws, const KmState* __restrict__ st,
-                                                                 Geo geo, int D, int k) {
+                                                                 const KmSlide* __restrict__ tab, int D, int k) {
     __shared__ int empty[KM_MAX_K];
     __shared__ int n_empty;
     __shared__ int far_idx;
     const int s = blockIdx.x;
     if (st[s].done) return;
-    const int n = geo.n(s);
-    const size_t r0 = geo.row(s);
+    const int n = tab[s].n;
+    const size_t r0 = tab[s].row;
     const int* off = offsets + (size_t)s * (k + 1);
     double* w = weights + (size_t)s * k;
     for (int c = threadIdx.x; c < k; c += blockDim.x) w[c] = (double)(off[c + 1] - off[c]);
@@ -738,15 +727,14 @@ __global__ __launch_bounds__(256) void km_update_centers_kernel(const float* __r
 }
 
 // the stop rule of _kmeans_single_lloyd; one workgroup per slide
-template <class Geo>
 __global__ __launch_bounds__(KM_THREADS) void km_finish_iter_kernel(const double* __restrict__ shift_part, const int* __restrict__ labels,
-                                                                    int* __restrict__ labels_old, KmState* __restrict__ st, Geo geo, int k,
-                                                                    int max_iter) {
+                                                                    int* __restrict__ labels_old, KmState* __restrict__ st,
+                                                                    const KmSlide* __restrict__ tab, int k, int max_iter) {
     __shared__ int shi[16];
     const int s = blockIdx.x;
     if (st[s].done) return;
-    const int n = geo.n(s);
-    const size_t r0 = geo.row(s);
+    const int n = tab[s].n;
+    const size_t r0 = tab[s].row;
     int diff = 0;
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
         const int l = labels[r0 + j];
@@ -766,12 +754,12 @@ __global__ __launch_bounds__(KM_THREADS) void km_finish_iter_kernel(const double
     }
 }
 
-template <class Geo>
-__global__ void km_restore_strict_kernel(int* __restrict__ labels, const int* __restrict__ labels_old, const KmState* __restrict__ st, Geo geo) {
+__global__ void km_restore_strict_kernel(int* __restrict__ labels, const int* __restrict__ labels_old, const KmState* __restrict__ st,
+                                         const KmSlide* __restrict__ tab) {
     const int s = blockIdx.y;
     if (!st[s].strict) return;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < geo.n(s)) labels[geo.row(s) + j] = labels_old[geo.row(s) + j];
+    if (j < tab[s].n) labels[tab[s].row + j] = labels_old[tab[s].row + j];
 }
 
 __global__ void km_count_done_kernel(const KmState* __restrict__ st, int S, int* __restrict__ out) {
@@ -789,12 +777,11 @@ __global__ void km_report_kernel(const KmState* __restrict__ st, int S, int* __r
 }
 
 // kmean_features.py:99-105: np.mean(features[labels == c], axis=0): fp32 adds in index order, / count
-template <class Geo>
 __global__ void km_cluster_means_kernel(const float* __restrict__ X, const int* __restrict__ members, const int* __restrict__ offsets,
-                                        float* __restrict__ out, Geo geo, int D, int k) {
+                                        float* __restrict__ out, const KmSlide* __restrict__ tab, int D, int k) {
     const int c = blockIdx.x, s = blockIdx.y;
     const int lo = offsets[(size_t)s * (k + 1) + c], hi = offsets[(size_t)s * (k + 1) + c + 1];
-    const size_t r0 = geo.row(s);
+    const size_t r0 = tab[s].row;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float a = 0.f;
         for (int i = lo; i < hi; ++i) a += X[(r0 + members[r0 + i]) * D + d];
@@ -1094,14 +1081,57 @@ struct KmBufs {
     float* Xc; double* colvar; double* G; float* centers; float* centers2; double* shift_part; double* dots; double* sums; double* weights; double* dist;
     int* seeds; int* labels_old; int* members; int* offsets; int* done_count; KmState* st;
     float* dist32;
-    KmSlide* tab; int* cls_list;      // ragged call only: the descriptor table [S] and the slide indices by seeding class [S], one block
+    KmSlide* tab; int* cls_list;      // the slide table [S] and the slide indices by seeding class [S], one block
     size_t bytes;
 };
 
-// The workspace of S slides with `rows` rows and `gram` n x n elements in all (uniform: S * n and S * n * n).
+// The slides of a call as its entry names them: slide s has ns[s * stride] rows and first centre firsts[s * stride].
+// stride 0: S equal slides (sq_kmeans_fit), or the one of sq_kmeans_fit_large; stride 1: the lists of sq_kmeans_fit_ragged.
+struct KmCounts {
+    int S;
+    const int32_t* ns;
+    const int32_t* firsts;
+    int stride;
+    int n(int s) const { return ns[(size_t)s * stride]; }
+    int first(int s) const { return firsts[(size_t)s * stride]; }
+};
+
+struct KmExtents {
+    size_t rows, gram;                // rows and n x n elements (each slide's rounded up to 4) of all slides
+    int n_max;                        // the largest slide: sizes the grids
+    int cls_n[KM_SEED_CLASSES];       // slides per seeding class
+};
+
+// The one walk over the counts: the extents and, with `host`, the block the device reads -- the slide table and behind
+// it the slide indices grouped by seeding class, in slide order inside a class.
+KmExtents km_walk(const KmCounts& c, std::vector<char>* host) {
+    KmExtents e{};
+    KmSlide* tab = nullptr;
+    if (host) {
+        host->resize((size_t)c.S * (sizeof(KmSlide) + 4));
+        tab = (KmSlide*)host->data();
+    }
+    for (int s = 0; s < c.S; ++s) {
+        const int n = c.n(s);
+        if (tab) tab[s] = KmSlide{n, c.first(s), e.rows, e.gram};
+        e.rows += (size_t)n;
+        e.gram += km_gram_elems(n);
+        if (n > e.n_max) e.n_max = n;
+        ++e.cls_n[km_seed_class(n)];
+    }
+    if (tab) {
+        int* list = (int*)(tab + c.S);
+        int fill[KM_SEED_CLASSES];
+        for (int q = 0, at = 0; q < KM_SEED_CLASSES; at += e.cls_n[q++]) fill[q] = at;
+        for (int s = 0; s < c.S; ++s) list[fill[km_seed_class(tab[s].n)]++] = s;
+    }
+    return e;
+}
+
+// The workspace of S slides of the extents e.
 // lg != nullptr: the large-slide route (no Gram matrix, no n^2 distances; its own seeding / sort buffers behind the rest).
-// ragged: the descriptor table and the class lists behind everything else.
-void km_bufs_rows(int S, size_t rows, size_t gram, int D, int k, char* base, KmBufs* o, KmLgBufs* lg, bool ragged) {
+void km_carve(int S, const KmExtents& e, int D, int k, char* base, KmBufs* o, KmLgBufs* lg) {
+    const size_t rows = e.rows, gram = e.gram;
     size_t off = 0;
     auto take = [&](size_t bytes) { off = sq_align_up(off, 256); char* p = base ? base + off : nullptr; off += bytes; return (void*)p; };
     o->Xc = (float*)take(rows * D * 4);
@@ -1133,30 +1163,21 @@ void km_bufs_rows(int S, size_t rows, size_t gram, int D, int k, char* base, KmB
         lg->pot = (float*)take(4);
         lg->hist = (int*)take((size_t)KM_LG_MAX_CHUNKS * KM_MAX_K * 4);
     }
-    o->tab = nullptr;
-    o->cls_list = nullptr;
-    if (ragged) {
-        o->tab = (KmSlide*)take((size_t)S * (sizeof(KmSlide) + 4));
-        o->cls_list = base ? (int*)(o->tab + S) : nullptr;
-    }
+    o->tab = (KmSlide*)take((size_t)S * (sizeof(KmSlide) + 4));
+    o->cls_list = base ? (int*)(o->tab + S) : nullptr;
     o->bytes = sq_align_up(off, 256);
 }
 
-void km_bufs(int S, int n, int D, int k, char* base, KmBufs* o, KmLgBufs* lg = nullptr) {
-    km_bufs_rows(S, (size_t)S * n, (size_t)S * n * n, D, k, base, o, lg, false);
-}
-
-// The Lloyd loop, the final E-step and the cluster means, shared by sq_kmeans_fit, sq_kmeans_fit_large and
-// sq_kmeans_fit_ragged: expects the centred data, the tolerance state, the seeded centres in b.centers and
-// labels_old = -1.  geo says where each slide's rows lie; n sizes the grids (the uniform row count, or the largest slide's:
-// blocks beyond their own slide's rows return at once).  lg == nullptr: member lists by km_members_kernel (n <= 4096,
-// any S); otherwise by the three-launch counting sort (any n, S == 1, uniform).
-template <class Geo>
+// The Lloyd loop, the final E-step and the cluster means: expects the slide table in b.tab, the centred data, the
+// tolerance state, the seeded centres in b.centers and labels_old = -1.  n, the largest slide's row count, sizes the
+// grids: blocks beyond their own slide's rows return at once.  lg == nullptr: member lists by km_members_kernel
+// (n <= 4096, any S); otherwise by the three-launch counting sort (any n, S == 1).
 int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter, int32_t* labels, float* cluster_features,
-                       int32_t* n_iter, const KmBufs& b, const KmLgBufs* lg, Geo geo, hipStream_t st) {
+                       int32_t* n_iter, const KmBufs& b, const KmLgBufs* lg, hipStream_t st) {
+    const KmSlide* tab = b.tab;
     auto members = [&](int force) -> int {
         if (!lg) {
-            hipLaunchKernelGGL(km_members_kernel<Geo>, dim3(S), dim3(KM_THREADS), 0, st, labels, b.members, b.offsets, b.st, geo, k, force);
+            hipLaunchKernelGGL(km_members_kernel, dim3(S), dim3(KM_THREADS), 0, st, labels, b.members, b.offsets, b.st, tab, k, force);
             SQ_LAUNCH_CHECK();
             return SQ_OK;
         }
@@ -1174,12 +1195,12 @@ int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter,
     const int ksl = D >= 32 * KM_DOT_SLICES ? KM_DOT_SLICES : 1;
     auto e_step = [&](int force) -> int {
         // dots[slice][centre][point] = centres . points (fp64), K sliced so that the launch fills the chip
-        hipLaunchKernelGGL(km_dgemm_nt_kernel<Geo>, dim3((n + 63) / 64, (k + 63) / 64, S * ksl), dim3(256), 0, st, cur, b.Xc, b.dots, k, n, D,
-                           (long long)k * D, (long long)n * D, (long long)k * n, ksl, 0, geo);
+        hipLaunchKernelGGL(km_dgemm_nt_kernel, dim3((n + 63) / 64, (k + 63) / 64, S * ksl), dim3(256), 0, st, cur, b.Xc, b.dots, k, n, D,
+                           (long long)k * D, ksl, 0, tab);
         SQ_LAUNCH_CHECK();
         hipLaunchKernelGGL(km_center_norms_kernel, dim3(k, S), dim3(64), 0, st, cur, b.shift_part + (size_t)S * k, b.st, D, k, force);
         SQ_LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_assign_kernel<Geo>, dim3((n + 63) / 64, S), dim3(1024), 0, st, b.dots, b.shift_part + (size_t)S * k, labels, b.st, geo, D, k, force, ksl);
+        hipLaunchKernelGGL(km_assign_kernel, dim3((n + 63) / 64, S), dim3(1024), 0, st, b.dots, b.shift_part + (size_t)S * k, labels, b.st, tab, D, k, force, ksl);
         SQ_LAUNCH_CHECK();
         return members(force);
     };
@@ -1189,14 +1210,14 @@ int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter,
         const int burst = it == 0 ? 2 : 4;      // iterations between host checks of the done flags
         for (int q = 0; q < burst && it < max_iter; ++q, ++it) {
             if (int e = e_step(0)) return e;
-            hipLaunchKernelGGL(km_sums_kernel<Geo>, dim3(k, S), dim3(256), 0, st, b.Xc, b.members, b.offsets, b.sums, b.st, geo, D, k);
+            hipLaunchKernelGGL(km_sums_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.members, b.offsets, b.sums, b.st, tab, D, k);
             SQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(km_relocate_kernel<Geo>, dim3(S), dim3(KM_THREADS), 0, st, b.Xc, cur, labels, b.offsets, b.sums,
-                               b.weights, b.dist, b.st, geo, D, k);
+            hipLaunchKernelGGL(km_relocate_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.Xc, cur, labels, b.offsets, b.sums,
+                               b.weights, b.dist, b.st, tab, D, k);
             SQ_LAUNCH_CHECK();
             hipLaunchKernelGGL(km_update_centers_kernel, dim3(k, S), dim3(256), 0, st, cur, nxt, b.sums, b.weights, b.shift_part, b.st, D, k);
             SQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(km_finish_iter_kernel<Geo>, dim3(S), dim3(KM_THREADS), 0, st, b.shift_part, labels, b.labels_old, b.st, geo, k, max_iter);
+            hipLaunchKernelGGL(km_finish_iter_kernel, dim3(S), dim3(KM_THREADS), 0, st, b.shift_part, labels, b.labels_old, b.st, tab, k, max_iter);
             SQ_LAUNCH_CHECK();
             float* t = cur; cur = nxt; nxt = t;
         }
@@ -1216,12 +1237,12 @@ int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter,
         // strict slides keep labels (== labels_old after the last update); non-strict get a fresh E-step
         if (int e = e_step(1)) return e;
         // restore labels of strict slides from labels_old and rebuild their member lists
-        hipLaunchKernelGGL(km_restore_strict_kernel<Geo>, dim3((n + 255) / 256, S), dim3(256), 0, st, labels, (const int*)b.labels_old, (const KmState*)b.st, geo);
+        hipLaunchKernelGGL(km_restore_strict_kernel, dim3((n + 255) / 256, S), dim3(256), 0, st, labels, (const int*)b.labels_old, (const KmState*)b.st, tab);
         SQ_LAUNCH_CHECK();
         if (int e = members(1)) return e;
     }
     if (cluster_features) {
-        hipLaunchKernelGGL(km_cluster_means_kernel<Geo>, dim3(k, S), dim3(256), 0, st, X, b.members, b.offsets, cluster_features, geo, D, k);
+        hipLaunchKernelGGL(km_cluster_means_kernel, dim3(k, S), dim3(256), 0, st, X, b.members, b.offsets, cluster_features, tab, D, k);
         SQ_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(km_report_kernel, dim3((S + 63) / 64), dim3(64), 0, st, b.st, S, n_iter);
@@ -1229,92 +1250,56 @@ int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter,
     return SQ_OK;
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------
+// 6. the driver behind the three entries
+// ------------------------------------------------------------------------------------------
+constexpr int KM_GRAM_MAX_N = 4096;              // the seeding kernel holds a slide's points in one workgroup's registers
+constexpr int KM_RAGGED_MAX_SLIDES = 4096;
 
-extern "C" size_t sq_kmeans_workspace_bytes(int n_slides, int n_samples, int dim, int n_clusters) {
-    if (n_slides < 1 || n_samples < 1 || dim < 1 || n_clusters < 1) return 0;
-    KmBufs b;
-    km_bufs(n_slides, n_samples, dim, n_clusters, nullptr, &b);
-    return b.bytes;
+// What an entry refuses, in one order for all three: the sizes before the device pointers, so a caller can ask with
+// NULL data why a shape is refused.  who: the entry's prefix; s_max: its bound on the slides (0: none); n_hi: on the
+// rows of a slide.  shape_only: stop behind what the workspace size depends on.
+int km_check(const char* who, const KmCounts& c, int s_max, int n_hi, int D, int k, bool shape_only, int trials, bool pointers) {
+    if (s_max) SQ_REQUIRE(c.S >= 1 && c.S <= s_max, "%s: n_slides=%d, must be in 1..%d", who, c.S, s_max);
+    else SQ_REQUIRE(c.S >= 1, "%s: n_slides=%d, must be at least 1", who, c.S);
+    SQ_REQUIRE(c.ns && (shape_only || c.firsts), "%s: null pointer (n_samples / first_centers)", who);
+    SQ_REQUIRE(k >= 1 && k <= KM_MAX_K, "%s: n_clusters=%d, must be in 1..%d", who, k, KM_MAX_K);
+    const int distinct = c.stride ? c.S : 1;
+    for (int s = 0; s < distinct; ++s)
+        SQ_REQUIRE(c.n(s) >= k && c.n(s) <= n_hi, "%s: slide %d has n_samples=%d, must be in n_clusters=%d..%d%s", who, s, c.n(s), k, n_hi,
+                   n_hi == KM_GRAM_MAX_N ? " (larger slides: sq_kmeans_fit_large)" : "");
+    SQ_REQUIRE(D >= 4 && D % 4 == 0, "%s: dim=%d must be a multiple of 4", who, D);
+    if (shape_only) return SQ_OK;
+    SQ_REQUIRE(trials >= 1 && trials <= KM_MAX_TRIALS, "%s: n_local_trials=%d, must be in 1..%d", who, trials, KM_MAX_TRIALS);
+    for (int s = 0; s < distinct; ++s)
+        SQ_REQUIRE(c.first(s) >= 0 && c.first(s) < c.n(s), "%s: slide %d has first_center=%d outside 0..%d", who, s, c.first(s), c.n(s) - 1);
+    SQ_REQUIRE(pointers, "%s: null pointer", who);
+    return SQ_OK;
 }
 
-extern "C" int sq_kmeans_fit(const float* X, int S, int n, int D, int k, int first_center, const double* uniforms,
-                             int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
-                             int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes,
-                             sq_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    SQ_REQUIRE(X && labels && uniforms && workspace, "kmeans: null pointer");
-    SQ_REQUIRE(S >= 1 && n >= k && k >= 1 && k <= KM_MAX_K, "kmeans: need n_samples >= n_clusters and 1 <= n_clusters <= %d (n=%d k=%d)", KM_MAX_K, n, k);
-    SQ_REQUIRE(n <= 4096, "kmeans: n_samples=%d > 4096 per slide (max_patch_number default is 4000)", n);
-    SQ_REQUIRE(D % 4 == 0, "kmeans: dim=%d must be a multiple of 4", D);
-    SQ_REQUIRE(n_local_trials >= 1 && n_local_trials <= KM_MAX_TRIALS, "kmeans: n_local_trials=%d", n_local_trials);
-    SQ_REQUIRE(first_center >= 0 && first_center < n, "kmeans: first_center=%d", first_center);
-    KmBufs b;
-    km_bufs(S, n, D, k, (char*)workspace, &b);
-    if (b.bytes > workspace_bytes) {
-        sq_set_error("kmeans: workspace %zu < required %zu", workspace_bytes, b.bytes);
-        return SQ_ERR_WORKSPACE;
+// The seeding from one fp64 Gram matrix per slide: every slide's seeds in b.seeds.
+int km_seed_gram(const KmBufs& b, const KmExtents& e, int S, int D, int k, const double* uniforms, int trials, hipStream_t st) {
+    const int n = e.n_max;
+    hipLaunchKernelGGL(km_dgemm_nt_kernel, dim3((n + 63) / 64, (n + 63) / 64, S), dim3(256), 0, st, b.Xc, b.Xc, b.G, n, n, D, 0LL, 1, 1, b.tab);
+    SQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_dist_f32_kernel, dim3(n, S), dim3(256), 0, st, b.G, b.dist32, b.tab);
+    SQ_LAUNCH_CHECK();
+    // one launch per class present: a slide's reduction layout depends on its own row count alone
+    const int* list = b.cls_list;
+    for (int q = 0; q < KM_SEED_CLASSES; list += e.cls_n[q++]) {
+        if (!e.cls_n[q]) continue;
+        const KmSeedLayout& lay = KM_SEED_LAYOUTS[q];
+        hipLaunchKernelGGL(lay.pts == 2 ? km_seed_kernel<2> : km_seed_kernel<4>, dim3(e.cls_n[q]), dim3(lay.threads), 0, st, b.dist32, uniforms,
+                           b.tab, list, k, trials, b.seeds);
+        SQ_LAUNCH_CHECK();
     }
-    const KmUniform geo{n};
-    hipLaunchKernelGGL(km_center_kernel<KmUniform>, dim3((D + KC_COLS - 1) / KC_COLS, S), dim3(256), 0, st, X, b.Xc, b.colvar, geo, D);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_tol_kernel, dim3(S), dim3(256), 0, st, b.colvar, b.st, D, tol);
-    SQ_LAUNCH_CHECK();
-    // Gram matrix of the centred data (fp64)
-    hipLaunchKernelGGL(km_dgemm_nt_kernel<KmUniform>, dim3((n + 63) / 64, (n + 63) / 64, S), dim3(256), 0, st, b.Xc, b.Xc, b.G, n, n, D,
-                       (long long)n * D, (long long)n * D, (long long)n * n, 1, 1, geo);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_dist_f32_kernel<KmUniform>, dim3(n, S), dim3(256), 0, st, b.G, b.dist32, geo);
-    SQ_LAUNCH_CHECK();
-    if (n <= KM_THREADS)       // 4 waves x 4 points per thread: cheaper barriers and wave exchanges than 16 waves x 1
-        hipLaunchKernelGGL(km_seed_kernel<4>, dim3(S), dim3(256), 0, st, b.dist32, uniforms, first_center, n, k, n_local_trials, b.seeds);
-    else if (n <= KM_THREADS)
-        hipLaunchKernelGGL(km_seed_kernel<1>, dim3(S), dim3(KM_THREADS), 0, st, b.dist32, uniforms, first_center, n, k, n_local_trials, b.seeds);
-    else if (n <= 2 * KM_THREADS)
-        hipLaunchKernelGGL(km_seed_kernel<2>, dim3(S), dim3(KM_THREADS), 0, st, b.dist32, uniforms, first_center, n, k, n_local_trials, b.seeds);
-    else
-        hipLaunchKernelGGL(km_seed_kernel<4>, dim3(S), dim3(KM_THREADS), 0, st, b.dist32, uniforms, first_center, n, k, n_local_trials, b.seeds);
-    SQ_LAUNCH_CHECK();
-    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)S * k * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(km_gather_centers_kernel<KmUniform>, dim3(k, S), dim3(256), 0, st, b.Xc, b.seeds, b.centers, geo, D, k);
-    SQ_LAUNCH_CHECK();
-    SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, (size_t)S * n * 4, st));          // labels_old = -1
-
-    return km_lloyd_and_means(X, S, n, D, k, max_iter, labels, cluster_features, n_iter, b, nullptr, geo, st);
+    return SQ_OK;
 }
 
-extern "C" size_t sq_kmeans_large_workspace_bytes(int n_samples, int dim, int n_clusters) {
-    if (n_samples < 1 || n_samples > KM_LG_MAX_N || dim < 1 || n_clusters < 1) return 0;
-    KmBufs b;
-    KmLgBufs lg;
-    km_bufs(1, n_samples, dim, n_clusters, nullptr, &b, &lg);
-    return b.bytes;
-}
-
-extern "C" int sq_kmeans_fit_large(const float* X, int n, int D, int k, int first_center, const double* uniforms,
-                                   int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
-                                   int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes,
-                                   sq_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    SQ_REQUIRE(n <= KM_LG_MAX_N, "kmeans (large): n_samples=%d > %d per slide", n, KM_LG_MAX_N);
-    SQ_REQUIRE(X && labels && uniforms && workspace, "kmeans (large): null pointer");
-    SQ_REQUIRE(n >= k && k >= 1 && k <= KM_MAX_K, "kmeans (large): need n_samples >= n_clusters and 1 <= n_clusters <= %d (n=%d k=%d)", KM_MAX_K, n, k);
-    SQ_REQUIRE(D >= 4 && D % 4 == 0, "kmeans (large): dim=%d must be a multiple of 4", D);
-    SQ_REQUIRE(n_local_trials >= 1 && n_local_trials <= KM_MAX_TRIALS, "kmeans (large): n_local_trials=%d", n_local_trials);
-    SQ_REQUIRE(first_center >= 0 && first_center < n, "kmeans (large): first_center=%d", first_center);
-    KmBufs b;
-    KmLgBufs lg;
-    km_bufs(1, n, D, k, (char*)workspace, &b, &lg);
-    if (b.bytes > workspace_bytes) {
-        sq_set_error("kmeans (large): workspace %zu < required %zu", workspace_bytes, b.bytes);
-        return SQ_ERR_WORKSPACE;
-    }
+// The seeding of one slide of any size (section 5): its seeds in b.seeds.
+int km_seed_large(const KmBufs& b, const KmLgBufs& lg, int n, int D, int k, int first_center, const double* uniforms, int trials,
+                  hipStream_t st) {
     const int nchunks = (n + KM_LG_CHUNK - 1) / KM_LG_CHUNK, ntiles = (n + KM_LG_TILE - 1) / KM_LG_TILE;
-    const KmUniform geo{n};
-    hipLaunchKernelGGL(km_center_kernel<KmUniform>, dim3((D + KC_COLS - 1) / KC_COLS, 1), dim3(256), 0, st, X, b.Xc, b.colvar, geo, D);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_tol_kernel, dim3(1), dim3(256), 0, st, b.colvar, b.st, D, tol);
-    SQ_LAUNCH_CHECK();
     hipLaunchKernelGGL(km_lg_rows_kernel<0>, dim3(ntiles), dim3(256), 0, st, (const float*)b.Xc, lg.norms, (const int*)nullptr, (int*)nullptr,
                        (const float*)nullptr, (float*)nullptr, (double*)nullptr, n, D, 0, nchunks, 0, 0);
     SQ_LAUNCH_CHECK();
@@ -1327,141 +1312,107 @@ extern "C" int sq_kmeans_fit_large(const float* X, int n, int D, int k, int firs
     SQ_LAUNCH_CHECK();
     for (int c = 1; c < k; ++c) {       // k - 1 dependent steps of three launches; the candidates never leave the device
         hipLaunchKernelGGL(km_lg_pick_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, (const float*)lg.closest, (const double*)lg.chunk_sum,
-                           (const float*)lg.pot, uniforms + (size_t)(c - 1) * n_local_trials, lg.cnt, n, n_local_trials);
+                           (const float*)lg.pot, uniforms + (size_t)(c - 1) * trials, lg.cnt, n, trials);
         SQ_LAUNCH_CHECK();
         hipLaunchKernelGGL(km_lg_rows_kernel<1>, dim3(ntiles), dim3(256), 0, st, (const float*)b.Xc, lg.norms, (const int*)lg.cnt, lg.cand,
-                           (const float*)lg.closest, lg.distc, lg.part, n, D, n_local_trials, nchunks, 0, 0);
+                           (const float*)lg.closest, lg.distc, lg.part, n, D, trials, nchunks, 0, 0);
         SQ_LAUNCH_CHECK();
         hipLaunchKernelGGL(km_lg_choose_kernel, dim3(nchunks), dim3(KM_LG_CHUNK), 0, st, (const double*)lg.part, (const float*)lg.distc,
-                           (const int*)lg.cand, lg.closest, lg.chunk_sum, lg.pot, b.seeds + c, n, n_local_trials, ntiles, 0);
+                           (const int*)lg.cand, lg.closest, lg.chunk_sum, lg.pot, b.seeds + c, n, trials, ntiles, 0);
         SQ_LAUNCH_CHECK();
     }
-    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)k * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(km_gather_centers_kernel<KmUniform>, dim3(k, 1), dim3(256), 0, st, b.Xc, b.seeds, b.centers, geo, D, k);
-    SQ_LAUNCH_CHECK();
-    SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, (size_t)n * 4, st));          // labels_old = -1
-    return km_lloyd_and_means(X, 1, n, D, k, max_iter, labels, cluster_features, n_iter, b, &lg, geo, st);
+    return SQ_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// 6. slides of different row counts in one call (each n_clusters <= n_s <= 4096: the Gram route)
-// ------------------------------------------------------------------------------------------
-namespace {
-
-constexpr int KM_RAGGED_MAX_SLIDES = 4096;
-constexpr int KM_SEED_CLASSES = 3;
-
-// The seeding layout sq_kmeans_fit gives a slide of n rows -- its dispatch, first match wins, is the definition:
-// 0: km_seed_kernel<4> on 256 threads (n <= 1024), 1: <2> on 1024 (n <= 2048), 2: <4> on 1024 (n <= 4096).
-int km_seed_class(int n) { return n <= KM_THREADS ? 0 : n <= 2 * KM_THREADS ? 1 : 2; }
-
-// Row and Gram offsets of the slides in list order; false for a list the entry refuses (the entry says why).
-bool km_ragged_extents(int S, const int32_t* n_samples, int k, size_t* rows, size_t* gram, int* n_max) {
-    if (S < 1 || S > KM_RAGGED_MAX_SLIDES || !n_samples || k < 1 || k > KM_MAX_K) return false;
-    *rows = 0; *gram = 0; *n_max = 0;
-    for (int s = 0; s < S; ++s) {
-        const int n = n_samples[s];
-        if (n < k || n > 4096) return false;
-        *rows += (size_t)n;
-        *gram += sq_align_up((size_t)n * n, 4);
-        if (n > *n_max) *n_max = n;
+// One fit: check, table, centring and tolerance, seeding (large: section 5 on the one slide, otherwise from the Gram
+// matrices), then seeds -> centres and the Lloyd loop.
+int km_fit(const char* who, int s_max, int n_hi, bool large, const float* X, const KmCounts& c, int D, int k, const double* uniforms,
+           int trials, int max_iter, double tol, int32_t* labels, float* cluster_features, int32_t* seed_indices, int32_t* n_iter,
+           void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int e = km_check(who, c, s_max, n_hi, D, k, false, trials, X && labels && uniforms && workspace)) return e;
+    const int S = c.S;
+    const bool lists = c.stride != 0;          // otherwise S equal slides: their table is filled on the device
+    // The host block of a table made from lists must outlive its copy: the Lloyd loop synchronises the stream at its
+    // first poll, every other way out waits here (`wait` is declared after `host`, so it runs first).
+    std::vector<char> host;
+    struct Wait {
+        hipStream_t st;
+        bool armed;
+        ~Wait() { if (armed) (void)hipStreamSynchronize(st); }
+    } wait{st, false};
+    const KmExtents e = km_walk(c, lists ? &host : nullptr);
+    KmBufs b;
+    KmLgBufs lg;
+    km_carve(S, e, D, k, (char*)workspace, &b, large ? &lg : nullptr);
+    SQ_REQUIRE_WORKSPACE(who, workspace_bytes, b.bytes);
+    if (lists) {
+        wait.armed = true;
+        SQ_HIP_CHECK(hipMemcpyAsync(b.tab, host.data(), host.size(), hipMemcpyHostToDevice, st));
+    } else {
+        hipLaunchKernelGGL(km_equal_table_kernel, dim3(1), dim3(256), 0, st, b.tab, b.cls_list, S, c.n(0), c.first(0), km_gram_elems(c.n(0)));
+        SQ_LAUNCH_CHECK();
     }
-    return true;
+    hipLaunchKernelGGL(km_center_kernel, dim3((D + KC_COLS - 1) / KC_COLS, S), dim3(256), 0, st, X, b.Xc, b.colvar, b.tab, D);
+    SQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_tol_kernel, dim3(S), dim3(256), 0, st, b.colvar, b.st, D, tol);
+    SQ_LAUNCH_CHECK();
+    if (int rc = large ? km_seed_large(b, lg, e.n_max, D, k, c.first(0), uniforms, trials, st) : km_seed_gram(b, e, S, D, k, uniforms, trials, st))
+        return rc;
+    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)S * k * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(km_gather_centers_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.seeds, b.centers, b.tab, D, k);
+    SQ_LAUNCH_CHECK();
+    SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, e.rows * 4, st));          // labels_old = -1
+    const int rc = km_lloyd_and_means(X, S, e.n_max, D, k, max_iter, labels, cluster_features, n_iter, b, large ? &lg : nullptr, st);
+    wait.armed = lists && (rc != SQ_OK || max_iter < 1);          // no poll ran
+    return rc;
+}
+
+size_t km_workspace(const KmCounts& c, int D, int k, bool large) {
+    KmBufs b;
+    KmLgBufs lg;
+    km_carve(c.S, km_walk(c, nullptr), D, k, nullptr, &b, large ? &lg : nullptr);
+    return b.bytes;
 }
 
 }  // namespace
 
+extern "C" size_t sq_kmeans_workspace_bytes(int n_slides, int n_samples, int dim, int n_clusters) {
+    if (n_slides < 1 || n_samples < 1 || dim < 1 || n_clusters < 1) return 0;
+    return km_workspace(KmCounts{n_slides, &n_samples, nullptr, 0}, dim, n_clusters, false);
+}
+
+extern "C" size_t sq_kmeans_large_workspace_bytes(int n_samples, int dim, int n_clusters) {
+    if (n_samples < 1 || n_samples > KM_LG_MAX_N || dim < 1 || n_clusters < 1) return 0;
+    return km_workspace(KmCounts{1, &n_samples, nullptr, 0}, dim, n_clusters, true);
+}
+
 extern "C" size_t sq_kmeans_ragged_workspace_bytes(int n_slides, const int32_t* n_samples, int dim, int n_clusters) {
-    size_t rows, gram;
-    int n_max;
-    if (dim < 4 || dim % 4 != 0 || !km_ragged_extents(n_slides, n_samples, n_clusters, &rows, &gram, &n_max)) return 0;
-    KmBufs b;
-    km_bufs_rows(n_slides, rows, gram, dim, n_clusters, nullptr, &b, nullptr, true);
-    return b.bytes;
+    const KmCounts c{n_slides, n_samples, nullptr, 1};
+    if (km_check("kmeans (ragged)", c, KM_RAGGED_MAX_SLIDES, KM_GRAM_MAX_N, dim, n_clusters, true, 0, false) != SQ_OK) return 0;
+    return km_workspace(c, dim, n_clusters, false);
+}
+
+extern "C" int sq_kmeans_fit(const float* X, int S, int n, int D, int k, int first_center, const double* uniforms,
+                             int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
+                             int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes,
+                             sq_stream_t stream) {
+    return km_fit("kmeans", 0, KM_GRAM_MAX_N, false, X, KmCounts{S, &n, &first_center, 0}, D, k, uniforms, n_local_trials, max_iter, tol,
+                  labels, cluster_features, seed_indices, n_iter, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int sq_kmeans_fit_large(const float* X, int n, int D, int k, int first_center, const double* uniforms,
+                                   int n_local_trials, int max_iter, double tol, int32_t* labels, float* cluster_features,
+                                   int32_t* seed_indices, int32_t* n_iter, void* workspace, size_t workspace_bytes,
+                                   sq_stream_t stream) {
+    return km_fit("kmeans (large)", 0, KM_LG_MAX_N, true, X, KmCounts{1, &n, &first_center, 0}, D, k, uniforms, n_local_trials, max_iter, tol,
+                  labels, cluster_features, seed_indices, n_iter, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int sq_kmeans_fit_ragged(const float* X, int S, const int32_t* n_samples, int D, int k, const int32_t* first_centers,
                                     const double* uniforms, int n_local_trials, int max_iter, double tol, int32_t* labels,
                                     float* cluster_features, int32_t* seed_indices, int32_t* n_iter, void* workspace,
-                                    size_t workspace_bytes, sq_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    SQ_REQUIRE(S >= 1 && S <= KM_RAGGED_MAX_SLIDES, "kmeans (ragged): n_slides=%d, must be in 1..%d", S, KM_RAGGED_MAX_SLIDES);
-    SQ_REQUIRE(n_samples && first_centers, "kmeans (ragged): null pointer (n_samples / first_centers)");
-    SQ_REQUIRE(k >= 1 && k <= KM_MAX_K, "kmeans (ragged): n_clusters=%d, must be in 1..%d", k, KM_MAX_K);
-    for (int s = 0; s < S; ++s)
-        SQ_REQUIRE(n_samples[s] >= k && n_samples[s] <= 4096,
-                   "kmeans (ragged): slide %d has n_samples=%d, must be in n_clusters=%d..4096 (larger slides: sq_kmeans_fit_large)", s,
-                   n_samples[s], k);
-    SQ_REQUIRE(D >= 4 && D % 4 == 0, "kmeans (ragged): dim=%d must be a multiple of 4", D);
-    SQ_REQUIRE(n_local_trials >= 1 && n_local_trials <= KM_MAX_TRIALS, "kmeans (ragged): n_local_trials=%d, must be in 1..%d", n_local_trials,
-               KM_MAX_TRIALS);
-    for (int s = 0; s < S; ++s)
-        SQ_REQUIRE(first_centers[s] >= 0 && first_centers[s] < n_samples[s], "kmeans (ragged): slide %d has first_center=%d outside 0..%d", s,
-                   first_centers[s], n_samples[s] - 1);
-    SQ_REQUIRE(X && labels && uniforms && workspace, "kmeans (ragged): null pointer");
-    size_t rows, gram;
-    int n_max;
-    km_ragged_extents(S, n_samples, k, &rows, &gram, &n_max);
-    KmBufs b;
-    km_bufs_rows(S, rows, gram, D, k, (char*)workspace, &b, nullptr, true);
-    SQ_REQUIRE_WORKSPACE("kmeans (ragged)", workspace_bytes, b.bytes);
-
-    // the descriptor table and, behind it, the slide indices grouped by seeding class: one block, one copy.  `host` must
-    // outlive the copy: the Lloyd loop synchronises the stream at its first poll, every other way out waits explicitly.
-    std::vector<char> host((size_t)S * (sizeof(KmSlide) + 4));
-    struct Wait {          // declared after `host`: an early return waits for the copy before `host` goes
-        hipStream_t st;
-        bool armed;
-        ~Wait() { if (armed) (void)hipStreamSynchronize(st); }
-    } wait{st, true};
-    KmSlide* tab = (KmSlide*)host.data();
-    int* list = (int*)(tab + S);
-    int cls_n[KM_SEED_CLASSES] = {0, 0, 0}, cls_lo[KM_SEED_CLASSES];
-    size_t ro = 0, go = 0;
-    for (int s = 0; s < S; ++s) {
-        tab[s] = KmSlide{n_samples[s], first_centers[s], (long long)ro, (long long)go};
-        ro += (size_t)n_samples[s];
-        go += sq_align_up((size_t)n_samples[s] * n_samples[s], 4);
-        ++cls_n[km_seed_class(n_samples[s])];
-    }
-    for (int c = 0, at = 0; c < KM_SEED_CLASSES; ++c) { cls_lo[c] = at; at += cls_n[c]; }
-    {
-        int fill[KM_SEED_CLASSES] = {cls_lo[0], cls_lo[1], cls_lo[2]};
-        for (int s = 0; s < S; ++s) list[fill[km_seed_class(n_samples[s])]++] = s;
-    }
-    SQ_HIP_CHECK(hipMemcpyAsync(b.tab, host.data(), host.size(), hipMemcpyHostToDevice, st));
-
-    const KmRagged geo{b.tab};
-    hipLaunchKernelGGL(km_center_kernel<KmRagged>, dim3((D + KC_COLS - 1) / KC_COLS, S), dim3(256), 0, st, X, b.Xc, b.colvar, geo, D);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_tol_kernel, dim3(S), dim3(256), 0, st, b.colvar, b.st, D, tol);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_dgemm_nt_kernel<KmRagged>, dim3((n_max + 63) / 64, (n_max + 63) / 64, S), dim3(256), 0, st, b.Xc, b.Xc, b.G, n_max,
-                       n_max, D, 0LL, 0LL, 0LL, 1, 1, geo);
-    SQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(km_dist_f32_kernel<KmRagged>, dim3(n_max, S), dim3(256), 0, st, b.G, b.dist32, geo);
-    SQ_LAUNCH_CHECK();
-    // one seeding launch per class present: every slide keeps the reduction layout of its own sq_kmeans_fit call
-    if (cls_n[0]) {
-        hipLaunchKernelGGL(km_seed_ragged_kernel<4>, dim3(cls_n[0]), dim3(256), 0, st, b.dist32, uniforms, b.tab, b.cls_list + cls_lo[0], k,
-                           n_local_trials, b.seeds);
-        SQ_LAUNCH_CHECK();
-    }
-    if (cls_n[1]) {
-        hipLaunchKernelGGL(km_seed_ragged_kernel<2>, dim3(cls_n[1]), dim3(KM_THREADS), 0, st, b.dist32, uniforms, b.tab, b.cls_list + cls_lo[1],
-                           k, n_local_trials, b.seeds);
-        SQ_LAUNCH_CHECK();
-    }
-    if (cls_n[2]) {
-        hipLaunchKernelGGL(km_seed_ragged_kernel<4>, dim3(cls_n[2]), dim3(KM_THREADS), 0, st, b.dist32, uniforms, b.tab, b.cls_list + cls_lo[2],
-                           k, n_local_trials, b.seeds);
-        SQ_LAUNCH_CHECK();
-    }
-    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)S * k * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(km_gather_centers_kernel<KmRagged>, dim3(k, S), dim3(256), 0, st, b.Xc, b.seeds, b.centers, geo, D, k);
-    SQ_LAUNCH_CHECK();
-    SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, rows * 4, st));          // labels_old = -1
-    const int rc = km_lloyd_and_means(X, S, n_max, D, k, max_iter, labels, cluster_features, n_iter, b, nullptr, geo, st);
-    wait.armed = rc != SQ_OK || max_iter < 1;          // no poll ran
-    return rc;
+                                    size_t workspace_bytes, sq_stream_t stream) {
+    return km_fit("kmeans (ragged)", KM_RAGGED_MAX_SLIDES, KM_GRAM_MAX_N, false, X, KmCounts{S, n_samples, first_centers, 1}, D, k, uniforms,
+                  n_local_trials, max_iter, tol, labels, cluster_features, seed_indices, n_iter, workspace, workspace_bytes,
+                  (hipStream_t)stream);
 }

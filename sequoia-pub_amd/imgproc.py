@@ -48,7 +48,7 @@ _plan_cache = {}
 
 def _device_plan(h_in, w_in, h_out, w_out, flt, dev):
     """The tables depend only on the shapes and the filter: the double arithmetic and the (synchronous, pageable) upload are
-    paid once per shape, as kmeans._device_draws does for the seeding draws."""
+    paid once per shape, as kmeans._uniforms does for the seeding draws."""
     key = (int(h_in), int(w_in), int(h_out), int(w_out), int(flt), str(dev))
     hit = _plan_cache.get(key)
     if hit is None:

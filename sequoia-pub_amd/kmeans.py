@@ -28,22 +28,71 @@ def seeding_draws(n_samples, n_clusters, random_state=0):
 
 GRAM_MAX_ROWS = 4096          # sq_kmeans_fit seeds from one n x n Gram matrix per slide and stops here
 LARGE_MAX_ROWS = 65536        # SQ_KMEANS_LARGE_MAX_SAMPLES, the bound of sq_kmeans_fit_large
+RAGGED_MAX_SLIDES = 4096      # slides per sq_kmeans_fit_ragged call
 
-_draws_cache = {}
+_uniforms_cache = {}          # (k, seed, device) -> (device table, trials)
+_first_cache = {}             # (n, k, seed) -> first centre
 
 
-def _device_draws(n_samples, n_clusters, random_state, dev):
-    """The draw sequence depends only on (n, k, seed): the reference clusters every slide with the same
-    ``random_state`` (kmean_features.py:96), so the host RNG walk and the (synchronous, pageable) upload are paid once
-    per shape instead of once per slide -- 60-80 us of a 1.6 ms call."""
-    key = (int(n_samples), int(n_clusters), int(random_state), str(dev))
-    hit = _draws_cache.get(key)
+def _uniforms(n_clusters, random_state, dev):
+    """The uniforms of seeding_draws on the device.  They do not depend on the patch count, and the reference clusters
+    every slide with the same ``random_state`` (kmean_features.py:96): the host RNG walk and the (synchronous, pageable)
+    upload are paid once instead of once per slide -- 60-80 us of a 1.6 ms call."""
+    key = (int(n_clusters), int(random_state), str(dev))
+    hit = _uniforms_cache.get(key)
     if hit is None:
-        first, u = seeding_draws(n_samples, n_clusters, random_state)
-        if len(_draws_cache) >= 64:
-            _draws_cache.clear()
-        hit = _draws_cache[key] = (first, torch.from_numpy(u).to(dev), u.shape[1])      # blocking copy: visible to every stream
+        u = seeding_draws(n_clusters, n_clusters, random_state)[1]
+        if len(_uniforms_cache) >= 64:
+            _uniforms_cache.clear()
+        hit = _uniforms_cache[key] = (torch.from_numpy(u).to(dev), u.shape[1])      # blocking copy: visible to every stream
     return hit
+
+
+def _first_center(n_samples, n_clusters, random_state):
+    """The first centre of a slide of n_samples patches, the only draw of seeding_draws that depends on the patch count."""
+    key = (int(n_samples), int(n_clusters), int(random_state))
+    hit = _first_cache.get(key)
+    if hit is None:
+        if len(_first_cache) >= 8192:
+            _first_cache.clear()
+        hit = _first_cache[key] = seeding_draws(n_samples, n_clusters, random_state)[0]
+    return hit
+
+
+def _fit(route, X, counts, n_clusters, random_state, max_iter, tol, want_means):
+    """One checked call of a C entry on X f32 [rows, D] (rows of the slides back to back): allocates the outputs and the
+    workspace.  route "batch": counts = [S, n], S slides of n rows through sq_kmeans_fit; "large": counts = [n], one slide
+    through sq_kmeans_fit_large; "ragged": counts = the slides' row counts, through sq_kmeans_fit_ragged.
+    Returns labels i32 [rows], cluster_features f32 [S, k, D] (None without want_means), indices i32 [S, k], n_iter i32 [S]."""
+    L = _lib.lib()
+    D, k, dev = int(X.shape[1]), int(n_clusters), X.device
+    if route == "batch":
+        S, n = counts
+        shape, need = (S, n), L.sq_kmeans_workspace_bytes(S, n, D, k)
+    elif route == "large":
+        S, n = 1, counts[0]
+        shape, need = (n,), L.sq_kmeans_large_workspace_bytes(n, D, k)
+        if need == 0:          # a size the entry refuses: let it say why (it names its bound) before anything is allocated
+            _lib.check(L.sq_kmeans_fit_large(None, n, D, k, 0, None, 1, max_iter, float(tol), None, None, None, None, None, 0, None))
+            raise _lib.SequoiaHipError(f"kmeans (large): unsupported size n={n} dim={D} k={k}")
+    else:
+        S, n = len(counts), counts[0]
+        ns = np.ascontiguousarray(counts, dtype=np.int32)
+        firsts = np.array([_first_center(c, k, random_state) for c in counts], dtype=np.int32)
+        shape, need = (S, ns.ctypes.data), int(L.sq_kmeans_ragged_workspace_bytes(S, ns.ctypes.data, D, k))
+    X = X.to(torch.float32).contiguous()
+    u_dev, trials = _uniforms(k, random_state, dev)
+    first = firsts.ctypes.data if route == "ragged" else _first_center(n, k, random_state)
+    labels = torch.empty(X.shape[0], dtype=torch.int32, device=dev)
+    means = torch.empty(S, k, D, dtype=torch.float32, device=dev) if want_means else None
+    seeds = torch.empty(S, k, dtype=torch.int32, device=dev)
+    n_iter = torch.empty(S, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    entry = dict(batch=L.sq_kmeans_fit, large=L.sq_kmeans_fit_large, ragged=L.sq_kmeans_fit_ragged)[route]
+    with torch.cuda.device(dev):
+        _lib.check(entry(_lib.ptr(X), *shape, D, k, first, _lib.ptr(u_dev), trials, max_iter, float(tol), _lib.ptr(labels), _lib.ptr(means),
+                         _lib.ptr(seeds), _lib.ptr(n_iter), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+    return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
 
 
 def kmeans_fit_batch(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_means=True):
@@ -54,45 +103,10 @@ def kmeans_fit_batch(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, 
         X = X.unsqueeze(0)
     if not X.is_cuda:
         raise _lib.SequoiaHipError("kmeans_fit_batch needs a CUDA tensor (no CPU fallback)")
-    X = X.to(torch.float32).contiguous()
     S, n, D = X.shape
-    dev = X.device
-    first, u_dev, trials = _device_draws(n, n_clusters, random_state, dev)
-    labels = torch.empty(S, n, dtype=torch.int32, device=dev)
-    means = torch.empty(S, n_clusters, D, dtype=torch.float32, device=dev) if want_means else None
-    seeds = torch.empty(S, n_clusters, dtype=torch.int32, device=dev)
-    n_iter = torch.empty(S, dtype=torch.int32, device=dev)
-    need = _lib.lib().sq_kmeans_workspace_bytes(S, n, D, n_clusters)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().sq_kmeans_fit(_lib.ptr(X), S, n, D, n_clusters, first, _lib.ptr(u_dev), trials, max_iter,
-                                            float(tol), _lib.ptr(labels), _lib.ptr(means), _lib.ptr(seeds), _lib.ptr(n_iter),
-                                            _lib.ptr(ws), need, _lib.stream_ptr(dev)))
-    return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
-
-
-def _fit_large(X, n_clusters, random_state, max_iter, tol, want_means):
-    """One slide [n, D] through sq_kmeans_fit_large (any n_clusters <= n <= LARGE_MAX_ROWS).  The size is checked before
-    anything is allocated or copied."""
-    n, D = X.shape
-    dev = X.device
-    L = _lib.lib()
-    need = L.sq_kmeans_large_workspace_bytes(n, D, n_clusters)
-    if need == 0:          # a size the entry refuses: let it say why (it names its bound) before anything is allocated
-        _lib.check(L.sq_kmeans_fit_large(None, n, D, n_clusters, 0, None, 1, max_iter, float(tol), None, None, None, None, None, 0, None))
-        raise _lib.SequoiaHipError(f"kmeans (large): unsupported size n={n} dim={D} k={n_clusters}")
-    X = X.to(torch.float32).contiguous()
-    first, u_dev, trials = _device_draws(n, n_clusters, random_state, dev)
-    labels = torch.empty(1, n, dtype=torch.int32, device=dev)
-    means = torch.empty(1, n_clusters, D, dtype=torch.float32, device=dev) if want_means else None
-    seeds = torch.empty(1, n_clusters, dtype=torch.int32, device=dev)
-    n_iter = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.sq_kmeans_fit_large(_lib.ptr(X), n, D, n_clusters, first, _lib.ptr(u_dev), trials, max_iter, float(tol),
-                                         _lib.ptr(labels), _lib.ptr(means), _lib.ptr(seeds), _lib.ptr(n_iter), _lib.ptr(ws), need,
-                                         _lib.stream_ptr(dev)))
-    return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
+    r = _fit("batch", X.reshape(S * n, D), [S, n], n_clusters, random_state, max_iter, tol, want_means)
+    r["labels"] = r["labels"].view(S, n)
+    return r
 
 
 def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_means=True, *, route=None):
@@ -101,8 +115,9 @@ def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_m
 
     The kernels are chosen from the row count alone: n <= GRAM_MAX_ROWS runs kmeans_fit_batch (seeding from the slide's
     Gram matrix), larger slides run sq_kmeans_fit_large (per-step candidate distances, chunked member sort; the same
-    Lloyd kernels).  ``route`` is a TEST HOOK, keyword-only: "large" sends a small slide through the large-slide entry so
-    that the tests can compare the two routes where both exist; "gram" forces the other; leave it None otherwise."""
+    Lloyd kernels; the size is checked before anything is allocated or copied).  ``route`` is a TEST HOOK, keyword-only:
+    "large" sends a small slide through the large-slide entry so that the tests can compare the two routes where both
+    exist; "gram" forces the other; leave it None otherwise."""
     _lib.require_gpu()
     if X.dim() == 3 and X.shape[0] == 1:
         X = X[0]
@@ -115,24 +130,9 @@ def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, want_m
     large = X.shape[0] > GRAM_MAX_ROWS if route is None else route == "large"
     if not large:
         return kmeans_fit_batch(X.unsqueeze(0), n_clusters, random_state, max_iter, tol, want_means)
-    return _fit_large(X, n_clusters, random_state, max_iter, tol, want_means)
-
-
-RAGGED_MAX_SLIDES = 4096      # slides per sq_kmeans_fit_ragged call
-
-_first_cache = {}
-
-
-def _first_center(n_samples, n_clusters, random_state):
-    """The first centre of a slide of n_samples patches: the only draw of seeding_draws that depends on the patch count
-    (the uniforms behind it are the same table for every n), cached per n on the host."""
-    key = (int(n_samples), int(n_clusters), int(random_state))
-    hit = _first_cache.get(key)
-    if hit is None:
-        if len(_first_cache) >= 8192:
-            _first_cache.clear()
-        hit = _first_cache[key] = seeding_draws(n_samples, n_clusters, random_state)[0]
-    return hit
+    r = _fit("large", X, [int(X.shape[0])], n_clusters, random_state, max_iter, tol, want_means)
+    r["labels"] = r["labels"].view(1, -1)
+    return r
 
 
 def _ragged_bytes(counts, D, k):
@@ -204,31 +204,11 @@ def kmeans_fit_ragged(slides, n_clusters=100, random_state=0, max_iter=300, tol=
     S, D, k, dev = len(counts), int(X.shape[1]), int(n_clusters), X.device
     plan = ragged_plan(counts, D, k, max_workspace_bytes)
     rows = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    labels = torch.empty(int(rows[-1]), dtype=torch.int32, device=dev)
-    means = torch.empty(S, k, D, dtype=torch.float32, device=dev) if want_means else None
-    seeds = torch.empty(S, k, dtype=torch.int32, device=dev)
-    n_iter = torch.empty(S, dtype=torch.int32, device=dev)
-    _, u_dev, trials = _device_draws(counts[0], k, random_state, dev)      # one table: the uniforms do not depend on n
-    L = _lib.lib()
-    for lo, hi, route in plan:
-        r0, r1 = int(rows[lo]), int(rows[hi])
-        if route == "large":
-            r = _fit_large(X[r0:r1], k, random_state, max_iter, tol, want_means)
-            labels[r0:r1] = r["labels"][0]
-            seeds[lo] = r["indices"][0]
-            n_iter[lo] = r["n_iter"][0]
-            if want_means:
-                means[lo] = r["cluster_features"][0]
-            continue
-        ns = np.ascontiguousarray(counts[lo:hi], dtype=np.int32)
-        firsts = np.array([_first_center(n, k, random_state) for n in ns], dtype=np.int32)
-        need = int(L.sq_kmeans_ragged_workspace_bytes(hi - lo, ns.ctypes.data, D, k))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.sq_kmeans_fit_ragged(_lib.ptr(X[r0:r1]), hi - lo, ns.ctypes.data, D, k, firsts.ctypes.data, _lib.ptr(u_dev), trials,
-                                              max_iter, float(tol), _lib.ptr(labels[r0:r1]), _lib.ptr(means[lo:hi]) if want_means else None,
-                                              _lib.ptr(seeds[lo:hi]), _lib.ptr(n_iter[lo:hi]), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
-    return dict(labels=[labels[int(rows[i]):int(rows[i + 1])] for i in range(S)], cluster_features=means, indices=seeds, n_iter=n_iter)
+    parts = [_fit("large" if route == "large" else "ragged", X[int(rows[lo]):int(rows[hi])], counts[lo:hi], k, random_state, max_iter, tol,
+                  want_means) for lo, hi, route in plan]
+    r = parts[0] if len(parts) == 1 else {key: torch.cat([p[key] for p in parts]) if parts[0][key] is not None else None for key in parts[0]}
+    r["labels"] = [r["labels"][int(rows[i]):int(rows[i + 1])] for i in range(S)]
+    return r
 
 
 class KMeans:

@@ -34,6 +34,12 @@ def same(a, b, equal_nan=False):
             and np.array_equal(a[3], b[3], equal_nan=equal_nan))
 
 
+def oracle(X):
+    """The CPU oracle's fit of one slide, in the form of alone()."""
+    o = ko.kmeans_fit(X)
+    return (o["labels"], o["indices"], o["n_iter"], ko.cluster_means(X, o["labels"]))
+
+
 def ragged(Xs, **kw):
     return kmeans_fit_ragged([torch.from_numpy(x).cuda() for x in Xs], 100, **kw)
 
@@ -57,9 +63,8 @@ def test_seeding_classes_and_tile_edges_in_one_call(slides64):
     assert r["labels"][0].dtype == torch.int32 and [int(l.numel()) for l in r["labels"]] == COUNTS_64
     for i in range(8):
         assert same(slide_of(r, i), ref[i]), (i, COUNTS_64[i])
-    for i in (0, 1, 4):                                      # 100, 257 and 1025 patches against the oracle
-        o = ko.kmeans_fit(Xs[i])
-        assert same(slide_of(r, i), (o["labels"], o["indices"], o["n_iter"], ko.cluster_means(Xs[i], o["labels"]))), COUNTS_64[i]
+    for i in range(8):                                       # every slide against the oracle: both sides of both class borders
+        assert same(slide_of(r, i), oracle(Xs[i])), COUNTS_64[i]
 
 
 def test_sliced_product_d512(gold):
@@ -70,6 +75,7 @@ def test_sliced_product_d512(gold):
     assert np.array_equal(r["labels"][0].cpu().numpy(), gold["gmm_8_512_n257::labels"])
     for i, x in enumerate(Xs):
         assert same(slide_of(r, i), alone(x)), i
+    assert same(slide_of(r, 3), oracle(Xs[3]))               # the planes behind three other slides' against the oracle
 
 
 def test_golden_anchors_d1024(gold):
@@ -97,6 +103,9 @@ def test_position_and_company(slides64):
     assert np.array_equal(torch.stack(e["labels"]).cpu().numpy(), b["labels"].cpu().numpy())
     for key in ("indices", "n_iter", "cluster_features"):
         assert np.array_equal(e[key].cpu().numpy(), b[key].cpu().numpy()), key
+    for i in (0, 7):                                         # the uniform batch itself against the oracle
+        assert same((b["labels"][i].cpu().numpy(), b["indices"][i].cpu().numpy(), int(b["n_iter"][i]),
+                     b["cluster_features"][i].cpu().numpy()), oracle(Es[i])), i
     # the (X_cat, counts) form of the input
     pair = kmeans_fit_ragged((torch.from_numpy(np.concatenate(Xs[:3])).cuda(), COUNTS_64[:3]), 100)
     for i in range(3):
@@ -139,6 +148,7 @@ def test_budget_split_and_large_slide(slides64):
     assert [g[2] for g in ragged_plan([600, 4100, 257], 64, 100, 4 << 30)] == ["gram", "large", "gram"]
     m = ragged([Xs[2], big, Xs[1]])
     assert same(slide_of(m, 1), alone(big))
+    assert same(slide_of(m, 1), oracle(big))                 # the large route, anchored outside the code under test
     assert same(slide_of(m, 0), ref[2]) and same(slide_of(m, 2), ref[1])
 
 
