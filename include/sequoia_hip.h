@@ -24,6 +24,12 @@ extern "C" {
 typedef void* sq_stream_t; /* hipStream_t */
 typedef void* sq_event_t;  /* hipEvent_t */
 
+#define SQ_OK 0
+#define SQ_ERR_ARG -1         /* an argument is outside what the entry admits; nothing was launched */
+#define SQ_ERR_HIP -2         /* a HIP runtime call failed */
+#define SQ_ERR_WORKSPACE -3   /* the workspace is smaller than *_workspace_bytes says */
+#define SQ_ERR_UNSUPPORTED -4 /* well-formed arguments the entry cannot serve (sq_resize_u8, sq_emd_status_check) */
+
 #define SQ_DTYPE_F32 0  /* exact fp32 MFMA (v_mfma_f32_32x32x2_f32): parity mode */
 #define SQ_DTYPE_BF16 1 /* bf16 MFMA, fp32 accumulate: perf mode              */
 #define SQ_DTYPE_BF16X3 2 /* split bf16 (sq_resnet50_extract only): every fp32 value as hi + lo bf16 planes, a.b = a_hi.b_hi + a_hi.b_lo +
@@ -792,6 +798,19 @@ int sq_emd_solve(const double* grids, int cells, const int32_t* dims, int P, int
                  double* value, int32_t* status, int32_t* counts, int32_t* cell_a, double* w_a, int32_t* cell_b, double* w_b,
                  double* u, double* v, int32_t* arc_i, int32_t* arc_j, double* arc_f, void* workspace, size_t workspace_bytes,
                  sq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Test and probe hooks (not a stable interface): the switches and bare kernel launches the tests and tools/ use.
+ *   sq_dbg_set       : experiment knobs of the GEMM engines (csrc/gemm.hip lists the keys).
+ *   sq_dbg_chain_x3  : one launch of the split-mode expand / reduce chain of the 56 x 56 stage (csrc/chain_x3.hip).
+ *   sq_dbg_chain_x3w : one launch of the same chain for the 28 x 28 and 14 x 14 stages (csrc/chain_x3w.hip).
+ * ---------------------------------------------------------------------------------------------------------- */
+int sq_dbg_set(int key, int value);
+int sq_dbg_chain_x3(int f16, int n2, int ds, int tail, long long P, int W, void* act, void* wts, void* fp, void* frag, void* stream);
+int sq_dbg_chain_x3w(int f16, int c, int n2, long long P, const void* t2_hi, const void* t2_lo, const void* res_hi, const void* res_lo,
+                     void* y_hi, void* y_lo, void* t1n_hi, void* t1n_lo, const void* w3_hi, const void* w3_lo,
+                     const void* w1n_hi, const void* w1n_lo, const float* b3, const float* cs3, const float* b1n, const float* cs1n,
+                     int w_tiled, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,5 +87,3 @@ int sq_launch_gemm_x3(const GemmArgs& a, hipStream_t stream);
 //   a.K = number of rows contracted.  Same epilogue / split-K fields as sq_launch_gemm.
 int sq_launch_gemm_tn(const GemmArgs& a, int dtype, hipStream_t stream);
 int sq_launch_splitk_reduce(const GemmArgs& a, hipStream_t stream);
-// experiment knobs (not part of the product ABI): key 0 = forced tile (WTM*10+WTN, 0 = auto), key 1 = dbg flags
-extern "C" int sq_dbg_set(int key, int value);

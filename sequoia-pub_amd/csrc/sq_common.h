@@ -3,12 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
-
-#define SQ_OK 0
-#define SQ_ERR_ARG -1
-#define SQ_ERR_HIP -2
-#define SQ_ERR_WORKSPACE -3
-#define SQ_ERR_UNSUPPORTED -4
+#include "../../include/sequoia_hip.h"      // SQ_OK / SQ_ERR_*: every entry returns them to its caller
 
 #define SQ_F32 0
 #define SQ_BF16 1

@@ -16,24 +16,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import CONSTANTS as _C
 from ._tables import call as _call, columns as _columns, table as _table
 
-MAX_CELLS = 4096                  # SQ_EMD_MAX_CELLS: cells of positive weight per map
-MAX_DIM = 16384                   # SQ_EMD_MAX_DIM
-MAX_GRID_CELLS = 1 << 24          # SQ_EMD_MAX_GRID_CELLS
-MAX_PROBLEMS = 1 << 16            # SQ_EMD_MAX_PROBLEMS
-MAX_ARCS = 16384                  # SQ_EMD_MAX_ARCS
-DEFAULT_AUGMENTATIONS = 256       # SQ_EMD_DEFAULT_AUGMENTATIONS: the default cap on augmentations, x (n + m)
-
-_vp, _sz, _i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-_lib.register_signature("sq_emd_column_chunk", _i32, [])
-_lib.register_signature("sq_emd_status_text", ctypes.c_char_p, [_i32])
-_lib.register_signature("sq_emd_status_check", _i32, [_vp, _i32])
-_lib.register_signature("sq_emd_fill_workspace_bytes", _sz, [_i32, _i32])
-_lib.register_signature("sq_emd_fill", _i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
-                                              _vp, _sz, _vp])
-_lib.register_signature("sq_emd_workspace_bytes", _sz, [_i32, _i32, _i32])
-_lib.register_signature("sq_emd_solve", _i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32] + [_vp] * 12 + [_vp, _sz, _vp])
+MAX_CELLS = _C["SQ_EMD_MAX_CELLS"]                          # cells of positive weight per map
+MAX_DIM = _C["SQ_EMD_MAX_DIM"]
+MAX_GRID_CELLS = _C["SQ_EMD_MAX_GRID_CELLS"]
+MAX_PROBLEMS = _C["SQ_EMD_MAX_PROBLEMS"]
+MAX_ARCS = _C["SQ_EMD_MAX_ARCS"]
+DEFAULT_AUGMENTATIONS = _C["SQ_EMD_DEFAULT_AUGMENTATIONS"]  # the default cap on augmentations, x (n + m)
 
 
 def column_chunk():

@@ -10,31 +10,21 @@ result equals the reference's own call bit for bit (NaN signs and payloads aside
 is no CPU fallback.  The EMD itself -- the grid fill, the normalisation and the transportation problem the reference hands
 to cv2.EMD -- is emd.py (csrc/emd.hip); ``align_ground_truth(..., emd=True)`` adds its two columns.  The figures stay out
 (DESIGN.md section 7)."""
-import ctypes
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._abi import CONSTANTS as _C
 from ._tables import call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table, vector as _vector
 from .mapstats import MAX_ROWS, percentile_of_score
 
-MAX_SPOTS = 1 << 20               # SQ_GT_MAX_SPOTS
-MAX_K = 8                         # SQ_GT_MAX_K
-MAX_RADIUS = 3                    # SQ_GT_MAX_RADIUS
-MAX_GRID_CELLS = 1 << 24          # SQ_GT_MAX_GRID_CELLS
-MAX_UNIQUE_COLS = 1 << 16         # SQ_GT_MAX_UNIQUE_COLS
-
-_vp, _sz, _i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-_lib.register_signature("sq_gt_spot_chunk", _i32, [])
-_lib.register_signature("sq_gt_unique_chunk_rows", _i32, [])
-_lib.register_signature("sq_gt_nearest_spots", _i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp])
-_lib.register_signature("sq_gt_spot_means", _i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp])
-_lib.register_signature("sq_gt_median_filter_workspace_bytes", _sz, [_i32, _i32, _i32])
-_lib.register_signature("sq_gt_median_filter", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp])
-_lib.register_signature("sq_gt_count_unique_workspace_bytes", _sz, [_i32, _i32])
-_lib.register_signature("sq_gt_count_unique", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp])
+MAX_SPOTS = _C["SQ_GT_MAX_SPOTS"]
+MAX_K = _C["SQ_GT_MAX_K"]
+MAX_RADIUS = _C["SQ_GT_MAX_RADIUS"]
+MAX_GRID_CELLS = _C["SQ_GT_MAX_GRID_CELLS"]
+MAX_UNIQUE_COLS = _C["SQ_GT_MAX_UNIQUE_COLS"]
 
 
 def spot_chunk():

@@ -11,17 +11,12 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
-SQ_RESIZE_BILINEAR = 0
-SQ_RESIZE_BICUBIC = 1
+SQ_RESIZE_BILINEAR = _abi.CONSTANTS["SQ_RESIZE_BILINEAR"]
+SQ_RESIZE_BICUBIC = _abi.CONSTANTS["SQ_RESIZE_BICUBIC"]
 FILTERS = {"bilinear": SQ_RESIZE_BILINEAR, "bicubic": SQ_RESIZE_BICUBIC, SQ_RESIZE_BILINEAR: SQ_RESIZE_BILINEAR,
            SQ_RESIZE_BICUBIC: SQ_RESIZE_BICUBIC}
-
-vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-_lib.register_signature("sq_resize_plan_bytes", sz, [i32, i32, i32, i32, i32])
-_lib.register_signature("sq_resize_plan_init", i32, [i32, i32, i32, i32, i32, vp, sz])
-_lib.register_signature("sq_resize_u8", i32, [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp])
 
 
 def resize_plan(h_in, w_in, h_out, w_out, resample="bilinear"):
@@ -32,7 +27,7 @@ def resize_plan(h_in, w_in, h_out, w_out, resample="bilinear"):
     if need == 0:
         raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
     plan = np.empty(need // 4, dtype=np.int32)
-    _lib.check(L.sq_resize_plan_init(h_in, w_in, h_out, w_out, flt, plan.ctypes.data_as(vp), need))
+    _lib.check(L.sq_resize_plan_init(h_in, w_in, h_out, w_out, flt, plan.ctypes.data_as(ctypes.c_void_p), need))
     return plan
 
 

@@ -11,7 +11,7 @@ per further centre), produced here with numpy's ``RandomState`` and handed to th
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 
 def seeding_draws(n_samples, n_clusters, random_state=0):
@@ -27,7 +27,7 @@ def seeding_draws(n_samples, n_clusters, random_state=0):
 
 
 GRAM_MAX_ROWS = 4096          # sq_kmeans_fit seeds from one n x n Gram matrix per slide and stops here
-LARGE_MAX_ROWS = 65536        # SQ_KMEANS_LARGE_MAX_SAMPLES, the bound of sq_kmeans_fit_large
+LARGE_MAX_ROWS = _abi.CONSTANTS["SQ_KMEANS_LARGE_MAX_SAMPLES"]       # the bound of sq_kmeans_fit_large
 RAGGED_MAX_SLIDES = 4096      # slides per sq_kmeans_fit_ragged call
 
 _uniforms_cache = {}          # (k, seed, device) -> (device table, trials)

@@ -7,28 +7,20 @@ the device.  The reference ranks every tile with one ``scipy.stats.percentileofs
 correlates the genes with ``DataFrame.corr()`` on one core; here both are one library call.  Tensors live on the device
 and there is no CPU fallback.  The alignment with the spatial-transcriptomics ground truth is gtalign.py; figures and the EMD stay out
 (DESIGN.md section 7)."""
-import ctypes
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._abi import CONSTANTS as _C
 from ._tables import call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table
 
-MAX_ROWS = 262144                 # SQ_MAP_MAX_ROWS
-MAX_CORR_COLS = 32768             # SQ_MAP_MAX_CORR_COLS
+MAX_ROWS = _C["SQ_MAP_MAX_ROWS"]
+MAX_CORR_COLS = _C["SQ_MAP_MAX_CORR_COLS"]
 LABELS = ("ac", "cc", "mes", "lin")
 # gbm_celltype_analysis.py:44-47,102 (the reference's names: 'purple' is the teal, 'green' the ochre)
 COLORS = OrderedDict([("ac", "#36CEBC"), ("cc", "#CE3649"), ("mes", "#3648CE"), ("lin", "#CEBC36")])
-
-_vp, _sz, _i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-_lib.register_signature("sq_map_rank_chunk_rows", _i32, [])
-_lib.register_signature("sq_map_percentile_workspace_bytes", _sz, [_i32, _i32, _i32])
-_lib.register_signature("sq_map_percentile", _i32, [_vp, _i32, _i32, _i32, _vp, _i32, ctypes.c_double, _vp, _vp, _vp, _sz, _vp])
-_lib.register_signature("sq_map_category_means", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp])
-_lib.register_signature("sq_map_gene_corr_workspace_bytes", _sz, [_i32, _i32])
-_lib.register_signature("sq_map_gene_corr", _i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp])
 
 
 def rank_chunk_rows():

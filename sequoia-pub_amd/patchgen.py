@@ -22,26 +22,18 @@ A slide is anything with OpenSlide's interface subset (``level_dimensions``, ``r
 ``properties``); ``ArraySlide`` provides it over numpy arrays so the whole flow runs without openslide."""
 import os
 
-import ctypes
-
 import numpy as np
 from scipy.ndimage import binary_dilation, binary_erosion
 
 from . import _lib, store
+from ._abi import CONSTANTS as _C
 
-FILTER_MIN_DIM, FILTER_MAX_DIM = 8, 512            # SQ_PATCH_FILTER_MIN_DIM, SQ_PATCH_FILTER_MAX_DIM
-SLIDE_MASK_MAX_DIM, SLIDE_MASK_MAX_PIXELS = 32768, 1 << 30      # SQ_SLIDE_MASK_MAX_DIM; h w <= 2^30
-SLIDE_MASK_MAX_ITERATIONS = 8                      # SQ_SLIDE_MASK_MAX_ITERATIONS
-SLIDE_MASK_TILE = (64, 256)                        # SQ_SLIDE_MASK_TILE_ROWS, SQ_SLIDE_MASK_TILE_COLS: the closing kernel's tile
-TILE_GRID_MAX_WINDOW, TILE_GRID_PACKED_MAX_WINDOW = 512, 64     # SQ_TILE_GRID_MAX_WINDOW, SQ_TILE_GRID_PACKED_MAX_WINDOW
-TILE_GRID_MAX_ITERATIONS = 8                       # SQ_TILE_GRID_MAX_ITERATIONS
-
-_vp, _sz, _i32, _f64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
-_lib.register_signature("sq_patch_filter_workspace_bytes", _sz, [_i32, _i32, _i32])
-_lib.register_signature("sq_patch_filter", _i32, [_vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
-_lib.register_signature("sq_slide_mask_workspace_bytes", _sz, [_i32, _i32])
-_lib.register_signature("sq_slide_mask", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp])
-_lib.register_signature("sq_tile_grid_valid", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp])
+FILTER_MIN_DIM, FILTER_MAX_DIM = _C["SQ_PATCH_FILTER_MIN_DIM"], _C["SQ_PATCH_FILTER_MAX_DIM"]
+SLIDE_MASK_MAX_DIM, SLIDE_MASK_MAX_PIXELS = _C["SQ_SLIDE_MASK_MAX_DIM"], 1 << 30      # h w <= 2^30
+SLIDE_MASK_MAX_ITERATIONS = _C["SQ_SLIDE_MASK_MAX_ITERATIONS"]
+SLIDE_MASK_TILE = (_C["SQ_SLIDE_MASK_TILE_ROWS"], _C["SQ_SLIDE_MASK_TILE_COLS"])      # the closing kernel's tile
+TILE_GRID_MAX_WINDOW, TILE_GRID_PACKED_MAX_WINDOW = _C["SQ_TILE_GRID_MAX_WINDOW"], _C["SQ_TILE_GRID_PACKED_MAX_WINDOW"]
+TILE_GRID_MAX_ITERATIONS = _C["SQ_TILE_GRID_MAX_ITERATIONS"]
 
 
 # ---- scikit-image restatements ---------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _abi, _lib
 
 LAYERS = (3, 4, 6, 3)
 PLANES = (64, 128, 256, 512)
@@ -309,7 +309,7 @@ class ResNet50(nn.Module):
         raise NotImplementedError("only forward_extract is on the SEQUOIA path (fc is never used by the reference scripts)")
 
 
-HW_MIN, HW_MAX = 193, 416      # include/sequoia_hip.h SQ_RESNET50_HW_MIN / _MAX
+HW_MIN, HW_MAX = _abi.CONSTANTS["SQ_RESNET50_HW_MIN"], _abi.CONSTANTS["SQ_RESNET50_HW_MAX"]
 
 
 def _is_square32(H, W):

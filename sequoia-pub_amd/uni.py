@@ -15,31 +15,11 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _abi, _lib
 from ._flat import FlatParams, numel
 
-SQ_UNI_MAX_DEPTH = 32
-_LAYER_FIELDS = ["ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2"]
-
-
-class UniConfig(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("dim", "depth", "heads", "mlp_dim", "img_size")]
-
-
-class UniLayerOffsets(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int64) for n in _LAYER_FIELDS]
-
-
-class UniLayout(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int64) for n in ("patch_w", "patch_b", "cls", "pos", "norm_g", "norm_b", "total")] + \
-               [("layer", UniLayerOffsets * SQ_UNI_MAX_DEPTH)]
-
-
-vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-_lib.register_signature("sq_uni_layout_init", i32, [ctypes.POINTER(UniConfig), ctypes.POINTER(UniLayout)])
-_lib.register_signature("sq_uni_workspace_bytes", sz, [ctypes.POINTER(UniConfig), i32, i32])
-_lib.register_signature("sq_uni_forward", i32, [ctypes.POINTER(UniConfig), i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp])
-_lib.register_signature("sq_uni_forward_checked", i32, [ctypes.POINTER(UniConfig), i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp, vp])
+SQ_UNI_MAX_DEPTH = _abi.CONSTANTS["SQ_UNI_MAX_DEPTH"]
+UniConfig, UniLayerOffsets, UniLayout = (_abi.STRUCTS[n] for n in ("sq_uni_config", "sq_uni_layer_offsets", "sq_uni_layout"))
 
 
 def tensor_map(cfg, lay):

@@ -3,14 +3,17 @@ include/sequoia_hip.h declares; host-side layout logic; no compute calls."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
 
-from sequoia_pub_amd import _lib
+from sequoia_pub_amd import _abi, _lib
 from sequoia_pub_amd.vis import ViS, tensor_map, vis_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "sequoia_hip.h")
 
 
 def declared_symbols():
@@ -25,6 +28,63 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 6
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/sequoia_hip.h but not exported"
+
+
+def test_every_declared_function_is_bound_with_its_arity_and_return_kind():
+    """The binding is derived from the header (_abi.py); the counts here come from this test's own reading of it."""
+    lib = _lib.lib()
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    decls = re.findall(r"([\w \*]+?)\s*\b(sq_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src)
+    assert sorted(d[1] for d in decls) == declared_symbols() == sorted(_abi.FUNCTIONS)
+    assert {"sq_dbg_set", "sq_dbg_chain_x3", "sq_dbg_chain_x3w"} <= set(_abi.FUNCTIONS)
+    for ret, name, args in decls:
+        fn = getattr(lib, name)
+        kind = ctypes.c_char_p if "char" in ret else ctypes.c_size_t if "size_t" in ret else ctypes.c_int
+        assert ret.split()[-1].rstrip("*") in ("char", "size_t", "int") and fn.restype is kind, (name, ret)
+        assert len(fn.argtypes) == (0 if args.strip() == "void" else args.count(",") + 1), name
+
+
+@pytest.mark.parametrize("text", [
+    "int sq_f(sq_unknown_t x);",                                          # unknown parameter type
+    "int sq_f(int x)\nint sq_g(void);",                                   # malformed: no semicolon
+    "typedef struct sq_s { int16_t a; } sq_s;",                           # unknown field type
+    "typedef struct sq_s { int32_t a[SQ_NOT_DEFINED]; } sq_s;",           # extent that is no macro of the header
+    "#define SQ_LIMIT (1 << 4)\n",                                        # a limit that is not a plain integer
+    "void sq_f(int x);",                                                  # a return type no entry has
+])
+def test_parser_refuses_what_it_does_not_understand(text):
+    good = "#define SQ_N 2\ntypedef struct sq_s { int32_t a, b[SQ_N]; } sq_s;\nint sq_g(const sq_s* s, size_t n);\n"
+    fns, structs, consts = _abi.parse(good)
+    assert consts == {"SQ_N": 2} and ctypes.sizeof(structs["sq_s"]) == 12
+    assert fns == {"sq_g": (ctypes.c_int, [ctypes.POINTER(structs["sq_s"]), ctypes.c_size_t])}
+    with pytest.raises(_abi.AbiError):
+        _abi.parse(good + text)
+
+
+def test_structs_and_constants_equal_what_the_c_compiler_sees(tmp_path):
+    """sizeof / offsetof of every struct field and the value of every SQ_* macro, printed by a C program that includes
+    the header, against the ctypes structures and constants derived from it: the compiler reads the header itself."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    macros = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SQ_\w+)[ \t]+\S", src, flags=re.M)
+    assert sorted(re.findall(r"\}\s*(sq_\w+)\s*;", src)) == sorted(_abi.STRUCTS) and len(_abi.STRUCTS) == 11
+    assert sorted(macros) == sorted(_abi.CONSTANTS) and len(macros) >= 40
+    prog = ["#include <stdio.h>", f'#include "{HEADER}"', "int main(void) {"]
+    want = {}
+    for cname, cls in _abi.STRUCTS.items():
+        prog.append(f'printf("{cname} %zu 0\\n", sizeof({cname}));')
+        want[cname] = (ctypes.sizeof(cls), 0)
+        for field, _ in cls._fields_:
+            prog.append(f'printf("{cname}.{field} %zu %zu\\n", sizeof((({cname}*)0)->{field}), offsetof({cname}, {field}));')
+            want[f"{cname}.{field}"] = (getattr(cls, field).size, getattr(cls, field).offset)
+    for m in macros:
+        prog.append(f'printf("{m} %lld 0\\n", (long long)({m}));')
+        want[m] = (_abi.CONSTANTS[m], 0)
+    (tmp_path / "abi.c").write_text("\n".join(prog + ["return 0; }", ""]))
+    cc = shutil.which("cc") or shutil.which("clang") or "/opt/rocm/llvm/bin/clang"
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "abi"), str(tmp_path / "abi.c")], check=True)
+    out = subprocess.run([str(tmp_path / "abi")], check=True, capture_output=True, text=True).stdout
+    got = {k: (int(a), int(b)) for k, a, b in (line.split() for line in out.splitlines())}
+    assert got == want
 
 
 def test_layout_is_aligned_and_dense():

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import emd_cases as ec
-from sequoia_pub_amd import _lib, emd
+from sequoia_pub_amd import _abi, _lib, emd
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sequoia_hip.h")
 
@@ -119,9 +119,9 @@ def test_every_emd_symbol_of_the_header_has_a_registered_signature():
     assert len(symbols) >= 7 and {"sq_emd_fill", "sq_emd_solve", "sq_emd_workspace_bytes", "sq_emd_column_chunk"} <= set(symbols)
     L = _lib.lib()
     for s in symbols:
-        assert s in _lib._OPTIONAL, s
+        assert s in _abi.FUNCTIONS, s
         assert hasattr(L, s), s
-        assert getattr(L, s).argtypes == _lib._OPTIONAL[s][1], s
+        assert getattr(L, s).restype == _abi.FUNCTIONS[s][0] and getattr(L, s).argtypes == _abi.FUNCTIONS[s][1], s
     limits = dict(re.findall(r"#define (SQ_EMD_MAX_\w+) (\d+)", text))
     assert int(limits["SQ_EMD_MAX_CELLS"]) == emd.MAX_CELLS == ec.MAX_CELLS >= 4096 and int(limits["SQ_EMD_MAX_DIM"]) == emd.MAX_DIM
     assert int(limits["SQ_EMD_MAX_GRID_CELLS"]) == emd.MAX_GRID_CELLS and int(limits["SQ_EMD_MAX_PROBLEMS"]) == emd.MAX_PROBLEMS

@@ -224,7 +224,6 @@ def test_eight_phase_256x256x64_variant(M, N, K, act, out, sched, bn):
     next tile's operands requested before the current tile's results are stored): the cases with more than 256 tiles."""
     _lib.require_gpu()
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randn(M, K, generator=g).cuda().bfloat16()
     W = (torch.randn(N, K, generator=g) / K ** 0.5).cuda().bfloat16()
@@ -264,7 +263,6 @@ def test_ring_variant_matches_default_tile(M, N, K):
     128 x 128 kernel: identical bits, including a ragged last M tile, with bias + bf16 residual + ReLU."""
     _lib.require_gpu()
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     g = torch.Generator().manual_seed(M + K)
     A = torch.randn(M, K, generator=g).to(torch.bfloat16).cuda()
     W = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16).cuda()

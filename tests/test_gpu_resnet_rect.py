@@ -190,7 +190,6 @@ def test_x3_halo_staged_3x3_at_256x265(golden_dir, mode):
     _lib.require_gpu()
     z = np.load(os.path.join(golden_dir, "resnet50_rect.npz"))
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     m, sd = _model(mode)
     p = torch.from_numpy(z["vis_u8"]).cuda()
     outs = {}

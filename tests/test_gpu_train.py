@@ -268,7 +268,6 @@ def test_batch384_bf16_step_on_the_eight_phase_gemm_vs_oracle():
     import ctypes
     _lib.require_gpu()
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     cfg = dict(num_outputs=512, input_dim=1024, depth=2, nheads=16, dimensions_f=64, dimensions_s=64, dimensions_c=64)
     sd = vis_oracle.perturb_norm_params(vis_oracle.init_vis_state_dict(**cfg, seed=17), seed=6)
     B = 384                     # 600 tiles: the GELU' epilogue is taken from two full rounds of tiles on

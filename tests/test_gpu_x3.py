@@ -91,7 +91,6 @@ def block_shape(request):
     """Both block shapes of gemm_x3.hip on every problem: the 8-wave 256-row ping-pong kernel and the 4-wave 128-row,
     two-blocks-per-CU kernel (the launcher picks by K; sq_dbg_set key 7 forces one)."""
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.sq_dbg_set(7, {"auto": -1, "rows256": 0, "rows128": 1 << 30}[request.param])
     yield request.param
     lib.sq_dbg_set(7, -1)
@@ -234,7 +233,6 @@ def test_conv_x3_halo_staged_3x3(Cin, Cout, H, n, halo, fmt):
     inside a 256-pixel tile, a ragged last tile -- and the implicit-GEMM form (sq_dbg_set key 8 = 0) on the same problem."""
     _lib.require_gpu()
     lib = _lib.lib()
-    lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
     g = torch.Generator().manual_seed(Cin + Cout + H + n)
     x = torch.randn(n, H, H, Cin, generator=g)
     w = torch.randn(Cout, 3, 3, Cin, generator=g) * (1.0 / np.sqrt(9 * Cin))
@@ -273,8 +271,6 @@ def test_chain_x3w_is_bit_identical_to_the_two_launches(C, N2, P, fmt):
     y and t1' must be equal bit for bit -- ragged last tiles, per-channel power-of-two weight scales, both plane formats."""
     _lib.require_gpu()
     lib = _lib.lib()
-    vp = ctypes.c_void_p
-    lib.sq_dbg_chain_x3w.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [vp] * 16 + [ctypes.c_int, vp]
     g = torch.Generator().manual_seed(C * 13 + N2 + P + fmt)
     N1 = 4 * C
     t2 = torch.relu(torch.randn(P, C, generator=g)) * torch.rand(P, 1, generator=g) * 2

@@ -9,8 +9,6 @@ import sequoia_pub_amd  # noqa
 from sequoia_pub_amd import _lib
 
 lib = _lib.lib()
-lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
-lib.sq_dbg_chain_x3.argtypes = [ctypes.c_int] * 4 + [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 5
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 500
 P = n * 56 * 56
 dev = "cuda:0"

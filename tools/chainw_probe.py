@@ -11,9 +11,6 @@ import sequoia_pub_amd  # noqa
 from sequoia_pub_amd import _lib
 
 lib = _lib.lib()
-vp = ctypes.c_void_p
-lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
-lib.sq_dbg_chain_x3w.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong] + [vp] * 16 + [ctypes.c_int, vp]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 dbgs = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, 1, 2, 3, 4, 8, 12, 15]
 dev = "cuda:0"

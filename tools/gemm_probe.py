@@ -8,7 +8,6 @@ import sequoia_pub_amd
 from sequoia_pub_amd import _lib
 
 lib = _lib.lib()
-lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
 WS = torch.empty(128 << 20, dtype=torch.uint8, device='cuda')        # split-K scratch (the launcher ignores it for forced special kernels)
 
 

@@ -4,7 +4,7 @@ import ctypes, sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sequoia_pub_amd
 from sequoia_pub_amd import _lib
-lib = _lib.lib(); lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
+lib = _lib.lib()
 M, N, K = 6400, 1024, 1024
 NB = 8
 A = [torch.randn(M, K, device="cuda").bfloat16() for _ in range(NB)]

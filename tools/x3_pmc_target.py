@@ -5,7 +5,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sequoia_pub_amd  # noqa
 from sequoia_pub_amd import _lib
 lib = _lib.lib()
-lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
 g = torch.Generator(device="cuda").manual_seed(1)
 n, H, Cin, N = 500, 14, 256, 256
 M, K = n * H * H, 9 * Cin

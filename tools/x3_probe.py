@@ -7,7 +7,6 @@ import sequoia_pub_amd  # noqa
 from sequoia_pub_amd import _lib
 
 lib = _lib.lib()
-lib.sq_dbg_set.argtypes = [ctypes.c_int, ctypes.c_int]
 
 
 def time_fn(fn, iters=20):
