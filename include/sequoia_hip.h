@@ -804,6 +804,11 @@ int sq_emd_solve(const double* grids, int cells, const int32_t* dims, int P, int
  *   sq_dbg_set       : experiment knobs of the GEMM engines (csrc/gemm.hip lists the keys).
  *   sq_dbg_chain_x3  : one launch of the split-mode expand / reduce chain of the 56 x 56 stage (csrc/chain_x3.hip).
  *   sq_dbg_chain_x3w : one launch of the same chain for the 28 x 28 and 14 x 14 stages (csrc/chain_x3w.hip).
+ *   sq_dbg_uni_attn  : the attention core of one UNI block, softmax(q k^T / 8) v per (image, head), through the launch the
+ *                      forward pass uses (csrc/uni.hip).  qkv [n_images * n_tokens, 3 * heads * 64] -> o [n_images * n_tokens,
+ *                      heads * 64], row-major, in `dtype`: SQ_DTYPE_F32 or SQ_DTYPE_BF16; SQ_DTYPE_F16X3: the fp16 hi plane
+ *                      followed by the lo plane, n_images * n_tokens * 3 * heads * 64 elements apart in qkv and
+ *                      n_images * n_tokens * heads * 64 in o.  1 <= n_tokens <= 256; 16-byte aligned pointers.
  * ---------------------------------------------------------------------------------------------------------- */
 int sq_dbg_set(int key, int value);
 int sq_dbg_chain_x3(int f16, int n2, int ds, int tail, long long P, int W, void* act, void* wts, void* fp, void* frag, void* stream);
@@ -811,6 +816,7 @@ int sq_dbg_chain_x3w(int f16, int c, int n2, long long P, const void* t2_hi, con
                      void* y_hi, void* y_lo, void* t1n_hi, void* t1n_lo, const void* w3_hi, const void* w3_lo,
                      const void* w1n_hi, const void* w1n_lo, const float* b3, const float* cs3, const float* b1n, const float* cs1n,
                      int w_tiled, void* stream);
+int sq_dbg_uni_attn(int dtype, const void* qkv, void* o, int n_images, int n_tokens, int heads, void* stream);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,14 @@ def init_state_dict(dim=1024, depth=24, heads=16, mlp_dim=4096, img_size=224, se
     return sd
 
 
+def attention(q, k, v):
+    """timm's ``Attention`` core: softmax(q k^T * hd^-0.5) v for q, k, v [B, heads, N, hd].  A function of its own so that a
+    test can put a deliberately wrong core in its place (tests/test_uni_cases_host.py) and see whether its bounds notice."""
+    hd = q.shape[-1]
+    attn = ((q * hd ** -0.5) @ k.transpose(-2, -1)).softmax(dim=-1)
+    return attn @ v
+
+
 def forward(sd, x, heads):
     """x: f32 [B, 3, S, S] normalised -> f32 [B, D] (the normalised class token)."""
     B = x.shape[0]
@@ -86,8 +94,7 @@ def forward(sd, x, heads):
         qkv = F.linear(y, sd[p + "attn.qkv.weight"], sd[p + "attn.qkv.bias"])
         N = qkv.shape[1]
         q, k, v = qkv.reshape(B, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
-        attn = ((q * hd ** -0.5) @ k.transpose(-2, -1)).softmax(dim=-1)
-        o = (attn @ v).transpose(1, 2).reshape(B, N, D)
+        o = attention(q, k, v).transpose(1, 2).reshape(B, N, D)
         o = F.linear(o, sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"])
         t = t + sd[p + "ls1.gamma"] * o
         y = F.layer_norm(t, (D,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], LN_EPS)

@@ -241,31 +241,38 @@ __global__ void uni_nonfinite_kernel(const float* __restrict__ x, uint32_t total
         if (!(fabsf(x[i]) <= 3.0e38f)) atomicOr(flag, 1u);
 }
 
-// softmax(q k^T * scale) v for one (image, head): q / k / v rows of this head staged in LDS as fp32,
-// wave w owns query rows w, w+4, ...; lane = key (4 per lane) for the scores, lane = channel for P V
+// softmax(q k^T * scale) v for one (image, head): k / v rows of this head staged in LDS as fp32,
+// wave w owns query rows w, w+4, ... (each staged in the wave's own 64 floats: with all T query rows resident as well, the
+// image of 226 tokens -- 240 px -- would need 174 KiB of the 160 KiB a workgroup can have); lane = key (4 per lane) for the
+// scores, lane = channel for P V
+constexpr size_t uni_attn_lds(int Ttok) { return ((size_t)Ttok * (DH + 1) + (size_t)Ttok * DH + 4 * ATT_MAXT + 4 * DH) * sizeof(float); }
+static_assert(uni_attn_lds(ATT_MAXT) <= 160 * 1024, "uni_attn_kernel: the K / V image of ATT_MAXT tokens must fit a workgroup's LDS");
+
 template <typename T>
 __global__ __launch_bounds__(256) void uni_attn_kernel(const T* __restrict__ qkv, T* __restrict__ o, int Ttok, int H, float scale) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* sq = sm;                          // [T][64]
-    float* sk = sq + Ttok * DH;              // [T][65]
+    float* sk = sm;                          // [T][65]
     float* sv = sk + Ttok * (DH + 1);        // [T][64]
     float* sp = sv + Ttok * DH;              // [4 waves][ATT_MAXT]
+    float* sq = sp + 4 * ATT_MAXT;           // [4 waves][64]: the query row a wave is working on
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int I = H * DH, ldq = 3 * I;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const T* base = qkv + (size_t)b * Ttok * ldq + h * DH;
     for (int i = tid; i < Ttok * DH; i += 256) {
         const int r = i >> 6, d = i & 63;
-        sq[r * DH + d] = ld(base + (size_t)r * ldq + d);
         sk[r * (DH + 1) + d] = ld(base + (size_t)r * ldq + I + d);
         sv[r * DH + d] = ld(base + (size_t)r * ldq + 2 * I + d);
     }
     __syncthreads();
     float* prow = sp + wv * ATT_MAXT;
+    float* qrow = sq + wv * DH;
     for (int i = wv; i < Ttok; i += 4) {
+        qrow[lane] = ld(base + (size_t)i * ldq + lane);
+        __builtin_amdgcn_wave_barrier();
         float s[4] = {0.f, 0.f, 0.f, 0.f};
         for (int d = 0; d < DH; ++d) {
-            const float q = sq[i * DH + d];
+            const float q = qrow[d];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = lane + 64 * u;
@@ -610,6 +617,37 @@ __global__ __launch_bounds__(ATT_X3_WAVES * 64, 1) void uni_attn_x3_kernel(const
     }
 }
 
+// The attention core of one block in every mode -- kernel choice, LDS size and the opt-in to more than 64 KiB of it -- for both
+// forward paths and sq_dbg_uni_attn.  qkv [n T, 3 H 64] -> o [n T, H 64] in `dtype` (SQ_F16X3: the hi plane followed by the lo
+// plane, n T 3 H 64 and n T H 64 elements apart); 1 <= T <= ATT_MAXT, the keys the K / V images of all three kernels hold.
+int uni_launch_attn(int dtype, const void* qkv, void* o, int n, int T, int H, hipStream_t s) {
+    SQ_REQUIRE(T >= 1 && T <= ATT_MAXT, "uni attention: %d tokens out of [1,%d]", T, ATT_MAXT);
+    constexpr size_t mfma_lds = 2 * ATT_MAXT * 128 + 4 * 4096;      // K and V images of ATT_MAXT rows, 4 waves' output staging
+    constexpr size_t x3_lds = 4 * ATT_MAXT * 128;                   // K and V, both planes: <= 128 KiB
+    static SqDevOnce attr;       // hipFuncSetAttribute is per device
+    if (attr.needed()) {
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)uni_attn_lds(ATT_MAXT)));
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lds));
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x3_lds));
+        attr.done();
+    }
+    const int Tp = (T + 31) / 32 * 32;
+    const size_t Mt = (size_t)n * T, I = (size_t)H * DH;
+    if (dtype == SQ_F32)
+        hipLaunchKernelGGL(uni_attn_kernel<float>, dim3(n * H), dim3(256), uni_attn_lds(T), s, (const float*)qkv, (float*)o, T, H, 0.125f);
+    else if (dtype == SQ_BF16)
+        hipLaunchKernelGGL(uni_attn_mfma_kernel, dim3(n * H), dim3(256), mfma_lds, s, (const bf16_t*)qkv, (bf16_t*)o, T, H, 0.125f);
+    else if (dtype == SQ_F16X3)
+        hipLaunchKernelGGL(uni_attn_x3_kernel, dim3(n * H), dim3(ATT_X3_WAVES * 64), (size_t)4 * Tp * 128, s, (const bf16_t*)qkv, Mt * 3 * I,
+                           (bf16_t*)o, Mt * I, T, H, 0.125f);
+    else {
+        sq_set_error("uni attention: dtype %d (f32, bf16 or f16x3)", dtype);
+        return SQ_ERR_ARG;
+    }
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
+}
+
 struct UniBufs {
     void* col; float* E; float* X; float* X1; void* Xn; void* QKV; void* O; void* Hid; float* cls; size_t bytes;
 };
@@ -726,21 +764,13 @@ int uni_forward_x3(const sq_uni_config* c, const float* params, const void* para
                        (const float4*)Pf(lay.pos), (float4*)w.X, n, T, D / 4);
     SQ_LAUNCH_CHECK();
 
-    const int Tp = (T + 31) / 32 * 32;
-    const size_t att_lds = (size_t)4 * Tp * 128;          // K and V, both planes: <= 128 KiB (T <= 256, check_cfg)
-    static SqDevOnce attr;       // hipFuncSetAttribute is per device
-    if (attr.needed()) {
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * ATT_MAXT * 128));
-        attr.done();
-    }
     float* X = w.X;
     float* X1 = w.X1;
     for (int l = 0; l < c->depth; ++l) {
         const sq_uni_layer_offsets& L = lay.layer[l];
         if (int e = ln(X, (size_t)D, L.ln1_g, L.ln1_b, (int)Mt)) return e;
         if (int e = gemm(Xn, plXn, D, plXn, L.qkv_w, L.qkv_b, (int)Mt, 3 * D, D, SQ_ACT_NONE, nullptr, 0, QKV, plQKV, 3 * D)) return e;
-        hipLaunchKernelGGL(uni_attn_x3_kernel, dim3(n * H), dim3(ATT_X3_WAVES * 64), att_lds, s, (const bf16_t*)QKV, plQKV, O, plO, T, H, 0.125f);
-        SQ_LAUNCH_CHECK();
+        if (int e = uni_launch_attn(SQ_F16X3, QKV, O, n, T, H, s)) return e;
         // the last block: projection, LayerNorm and MLP on the n class rows only (as in the fp32 / bf16 path)
         const bool cls_only = l == c->depth - 1;
         const int R = cls_only ? n : (int)Mt;
@@ -816,16 +846,6 @@ int uni_forward_f32_bf16(const sq_uni_config* c, int dtype, const float* params,
                        (const float4*)Pf(lay.pos), (float4*)w.X, n, T, D / 4);
     SQ_LAUNCH_CHECK();
 
-    const size_t att_lds = ((size_t)T * DH * 2 + (size_t)T * (DH + 1) + 4 * ATT_MAXT) * sizeof(float);
-    const size_t att_mfma_lds = 2 * 256 * 128 + 4 * 4096;
-    const bool valu_attn = (T + 31) / 32 * 32 > 256;   // the MFMA core's K / V images hold <= 256 keys
-    static SqDevOnce attr;       // hipFuncSetAttribute is per device
-    if (attr.needed()) {
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)att_mfma_lds));
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)uni_attn_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr.done();
-    }
     float* X = w.X;
     float* X1 = w.X1;
     for (int l = 0; l < c->depth; ++l) {
@@ -837,10 +857,7 @@ int uni_forward_f32_bf16(const sq_uni_config* c, int dtype, const float* params,
             g.C = w.QKV; g.out_dtype = dtype; g.ldc = 3 * D; g.M = Mt; g.N = 3 * D; g.K = D;
             if (int e = sq_launch_gemm(g, dtype, s)) return e;
         }
-        if (lp && !valu_attn) hipLaunchKernelGGL(uni_attn_mfma_kernel, dim3(n * H), dim3(256), att_mfma_lds, s, (const bf16_t*)w.QKV, (bf16_t*)w.O, T, H, 0.125f);
-        else if (lp) hipLaunchKernelGGL(uni_attn_kernel<bf16_t>, dim3(n * H), dim3(256), att_lds, s, (const bf16_t*)w.QKV, (bf16_t*)w.O, T, H, 0.125f);
-        else hipLaunchKernelGGL(uni_attn_kernel<float>, dim3(n * H), dim3(256), att_lds, s, (const float*)w.QKV, (float*)w.O, T, H, 0.125f);
-        SQ_LAUNCH_CHECK();
+        if (int e = uni_launch_attn(dtype, w.QKV, w.O, n, T, H, s)) return e;
         // The LAST block: only the class token of its output is read (forward_head with global_pool='token', num_classes=0:
         // compute_features_hdf5.py:125-129 takes feat_model(image) = norm(x)[:, 0]).  Keys and values need every token, everything
         // behind the attention core is per token: the projection, LayerNorm and the MLP run on the n class rows only (row stride
@@ -893,6 +910,17 @@ extern "C" int sq_uni_forward_checked(const sq_uni_config* c, int dtype, const f
         SQ_LAUNCH_CHECK();
     }
     return SQ_OK;
+}
+
+// test hook: the attention core alone, through the forward pass's own launch (include/sequoia_hip.h)
+extern "C" int sq_dbg_uni_attn(int dtype, const void* qkv, void* o, int n_images, int n_tokens, int heads, void* stream) {
+    SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16 || dtype == SQ_F16X3, "sq_dbg_uni_attn: dtype %d (f32, bf16 or f16x3)", dtype);
+    SQ_REQUIRE(qkv && o, "sq_dbg_uni_attn: null pointer");
+    SQ_REQUIRE((((uintptr_t)qkv | (uintptr_t)o) & 15) == 0, "sq_dbg_uni_attn: qkv and o must be 16-byte aligned");
+    SQ_REQUIRE(n_tokens >= 1 && n_tokens <= ATT_MAXT, "sq_dbg_uni_attn: n_tokens=%d out of [1,%d]", n_tokens, ATT_MAXT);
+    SQ_REQUIRE(n_images >= 1 && heads >= 1 && (long long)n_images * heads <= 65535, "sq_dbg_uni_attn: n_images=%d heads=%d", n_images, heads);
+    SQ_REQUIRE((size_t)n_images * n_tokens * 3 * heads * DH * sizeof(float) < (1ull << 31), "sq_dbg_uni_attn: %d images of %d tokens and %d heads exceed 2 GiB", n_images, n_tokens, heads);
+    return uni_launch_attn(dtype, qkv, o, n_images, n_tokens, heads, (hipStream_t)stream);
 }
 
 // params: fp32 flat buffer (sq_uni_layout) -- biases, LayerNorm and embeddings are read from it;

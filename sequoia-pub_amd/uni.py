@@ -98,11 +98,13 @@ class UniViT(nn.Module, FlatParams):
     no classifier head.  ``forward(x f32 [B, 3, S, S]) -> f32 [B, dim]``."""
 
     def __init__(self, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4.0, img_size=224, patch_size=16, init_values=1e-5,
-                 num_classes=0, compute_dtype="fp32", **_ignored):
+                 num_classes=0, compute_dtype="fp32", mlp_dim=None, **_ignored):
+        """mlp_dim: the hidden width itself where embed_dim * mlp_ratio does not say it exactly (192 * (200 / 192) is 199.99...)."""
         super().__init__()
         if patch_size != 16 or num_classes != 0 or embed_dim != num_heads * 64:
             raise ValueError("the HIP kernels cover patch_size=16, head dim 64, num_classes=0 (the reference's UNI configuration)")
-        self.cfg = UniConfig(int(embed_dim), int(depth), int(num_heads), int(embed_dim * mlp_ratio), int(img_size))
+        self.cfg = UniConfig(int(embed_dim), int(depth), int(num_heads), int(embed_dim * mlp_ratio) if mlp_dim is None else int(mlp_dim),
+                             int(img_size))
         self.layout = UniLayout()
         _lib.check(_lib.lib().sq_uni_layout_init(ctypes.byref(self.cfg), ctypes.byref(self.layout)))
         self._tmap = tensor_map(self.cfg, self.layout)
@@ -152,7 +154,7 @@ class UniViT(nn.Module, FlatParams):
         tw = self.__dict__.get("_twin")
         if tw is None:
             c = self.cfg
-            tw = UniViT(embed_dim=c.dim, depth=c.depth, num_heads=c.heads, mlp_ratio=c.mlp_dim / c.dim, img_size=c.img_size,
+            tw = UniViT(embed_dim=c.dim, depth=c.depth, num_heads=c.heads, mlp_dim=c.mlp_dim, img_size=c.img_size,
                         init_values=self._init_values, compute_dtype="fp32")
             self.__dict__["_twin"] = tw                  # not a registered submodule: state_dict() keeps timm's keys
             self.__dict__["_twin_key"] = None
