@@ -379,6 +379,10 @@ int sq_linear_x3(int fmt, const void* A_hi, const void* A_lo, int lda, const voi
 /* Weight gradient of a linear layer: dW[N_out, N_in] (f32, lddw) = dY[T, N_out]^T . X[T, N_in], contracting
  * over the T token rows, straight from the token-major tensors (the `loss.backward()` of the nn.Linear call
  * sites above, src/vit.py:178).  dY (lddy) and X (ldx) are `dtype`; N_in % 8 == 0; lddy >= round_up(N_out, 8).
+ * Columns [N_out, round_up(N_out, 8)) of dY must exist (the loader fetches whole 16-byte chunks) but may hold anything, NaN and
+ * infinities included: a dY column only ever reaches its own row of dW and its own element of dbias, and rows >= N_out are never
+ * stored (tests/test_gpu_gemm_contract.py pins this with NaN there).  Columns of dY from round_up(N_out, 8) on, columns of X from
+ * N_in on and rows from n_tokens on are not read; of dW only [N_out, N_in] is written, whatever lddw.
  * dbias (optional, [N_out] f32): the bias gradient sum_t dY[t, :], computed by the same launch.
  * workspace: optional fp32 scratch enabling deterministic split-K over the tokens. */
 int sq_linear_weight_grad(int dtype, const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, float* dbias,

@@ -1,5 +1,6 @@
 """HE2RNA comparator on the HIP engine (sequoia_pub_amd/he2rna.py) against the golden vectors of the reference's own
 class (tests/golden/he2rna.npz) and, at the size pretrain_gtex.py builds it, against the pinned oracle."""
+import functools
 import os
 import sys
 
@@ -79,6 +80,77 @@ def test_the_three_users_of_the_layer_stack_agree_bit_for_bit(layers):
         pred = m(x)
         assert pred.shape == (B, G) and bool(torch.isfinite(pred).all())
         assert torch.equal(pred, m.window_predictions(scores, mask, members))
+
+
+NARROW_KS = [1, 5, 20]
+NARROW_STACKS = {      # B = 3 slides of N = 20 tiles with C = 35 channels, G = 12 genes
+    "layers1": dict(layers=[1], D=32, seed=11),                   # the reference's default: a hidden width of ONE
+    "layers5x12": dict(layers=[5, 12], D=30, seed=12),            # no width and no input_dim a multiple of 8
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _narrow_stack(name):
+    """Seeded state dict, input and loss weights of one stack, and the float64 reference (oracle + autograd) of both forward
+    forms: dict(pred, grads {key: array}, gx) per form.  Tiles are masked (all channels <= 0) in the middle and at the end of a
+    slide, never at its start (no 0/0).  Computed once, shared by the cases, never modified."""
+    c = NARROW_STACKS[name]
+    B, C, N, G, D = 3, 35, 20, 12, c["D"]
+    g = torch.Generator().manual_seed(c["seed"])
+    dims = [D] + c["layers"] + [G]
+    sd = {}
+    for i in range(len(dims) - 1):
+        sd[f"conv{i}.weight"] = (torch.rand(dims[i + 1], dims[i], 1, generator=g) - 0.35) / dims[i] ** 0.5
+        sd[f"conv{i}.bias"] = torch.rand(dims[i + 1], generator=g) * 0.2 - 0.05
+    x = torch.randn(B, C, N, generator=g).clamp_min(-0.2)
+    x[0, :, 7] = 0
+    x[0, :, 19] = -0.1
+    x[1, :, 10:12] = 0
+    x[2, :, 17:] = 0
+    r = torch.randn(B, G, generator=g)
+    refs = {}
+    for form in ("fixed_k5", "eval_mean"):
+        leaf = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+        xl = x.double().requires_grad_(True)
+        pred = ho.forward_fixed_k(leaf, xl, 5, D) if form == "fixed_k5" else ho.forward_eval(leaf, xl, NARROW_KS, D)
+        (pred * r.double()).sum().backward()
+        refs[form] = dict(pred=pred.detach().numpy(), grads={k: v.grad.numpy() for k, v in leaf.items()}, gx=xl.grad.numpy())
+    hidden = torch.nn.functional.conv1d(x[:, C - D:].double(), sd["conv0.weight"].double(), sd["conv0.bias"].double())     # [B, width, N]
+    return sd, x, r, refs, (hidden > 0)
+
+
+@pytest.mark.parametrize("form", ["fixed_k5", "eval_mean"])
+@pytest.mark.parametrize("name", list(NARROW_STACKS))
+def test_gradients_of_narrow_and_unpadded_stacks_match_float64_autograd(name, form):
+    """The GEMM engine as HE2RNA uses it at its narrowest: layers=[1] (an N = 1 product written into rows of 8, a K = 8 product,
+    a weight gradient with n_out = 1) and layers=[5, 12] on input_dim 30 (every width zero-padded), through forward_fixed_k(x, 5)
+    and through the eval-mode mean over ks = [1, 5, 20] (sq_he2rna_topk_mean_bwd with more than one k).  Loss (pred * r).sum();
+    prediction, parameter gradients and the gradient w.r.t. x against autograd over oracle.he2rna_oracle in float64, at the bounds of
+    test_gradients_match_reference_golden."""
+    _lib.require_gpu()
+    c = NARROW_STACKS[name]
+    sd, x, r, refs, alive = _narrow_stack(name)
+    ref = refs[form]
+    # the reference itself exercises what the test is about: no gradient tensor vanishes, and every hidden unit of the first
+    # layer (THE unit, for layers=[1]) is alive on some tiles and dead on others
+    assert all(np.abs(v).max() > 0 for v in ref["grads"].values()) and np.abs(ref["gx"]).max() > 0 and np.isfinite(ref["pred"]).all()
+    assert bool(alive.any(dim=2).any(dim=0).all()) and bool((~alive).any())
+    assert bool((x[:, :, 0].max(dim=1)[0] > 0).all()) and bool((x.max(dim=1)[0] <= 0).any())
+    m = HE2RNA(input_dim=c["D"], output_dim=12, layers=c["layers"], ks=NARROW_KS, dropout=0.5, device="cuda:0")
+    m.load_state_dict(sd)
+    m.eval()
+    xg = x.cuda().requires_grad_(True)
+    pred = m.forward_fixed_k(xg, 5) if form == "fixed_k5" else m(xg)
+    (pred * r.cuda()).sum().backward()
+    err = float(np.abs(pred.detach().cpu().numpy() - ref["pred"]).max() / np.abs(ref["pred"]).max())
+    print(f"HE2RNA {name} {form}: prediction rel err {err:.2e}; " + ", ".join(
+        f"{k} {np.abs(p.grad.cpu().numpy() - ref['grads'][k]).max() / np.abs(ref['grads'][k]).max():.2e}" for k, p in m.named_parameters()))
+    assert err < 1e-4, err
+    for k, p in m.named_parameters():
+        g = ref["grads"][k]
+        assert p.grad.shape == g.shape
+        np.testing.assert_allclose(p.grad.cpu().numpy(), g, rtol=1e-4, atol=1e-4 * np.abs(g).max(), err_msg=k)
+    np.testing.assert_allclose(xg.grad.cpu().numpy(), ref["gx"], rtol=1e-4, atol=1e-4 * np.abs(ref["gx"]).max())
 
 
 def test_full_size_against_oracle_and_training_step():
