@@ -470,6 +470,59 @@ int sq_he2rna_window_topk_mean(const float* scores, int ld_scores, const float* 
                                sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * HE2RNA training step on the device (src/he2rna.py:108-127, the loop the k-fold experiment of :323-436 runs): fp32, one process.
+ * dims = host [n_layers + 1] = {input_dim, *layers, output_dim}, n_layers <= SQ_HE2RNA_MAX_LAYERS.  Every entry is asynchronous on
+ * `stream` and allocates, copies and synchronises nothing.
+ *   sq_he2rna_param_layout : offsets (in floats) of layer i's weight and bias in ONE flat fp32 buffer and the buffer's size.  A weight
+ *                         is [n_out, round_up(n_in, 8)] row-major; every tensor starts on a 16-byte boundary.  The padding columns and
+ *                         the gaps hold zero and stay zero under the optimiser: their gradient is exactly zero, so both Adam
+ *                         moments stay zero.  Gradient and moments use the same layout.  w_off / b_off / total may be NULL.
+ *   sq_he2rna_loss_head : sq_he2rna_topk_mean, sq_mse_loss_grad and sq_he2rna_topk_mean_bwd of a step with each (slide, gene)
+ *                         column ranked ONCE: pred f32 [B, G] (bit-identical to sq_he2rna_topk_mean), *loss_out = mean((pred -
+ *                         target)^2) (device scalar, fp64 sums in a fixed order), grad_scores f32 [B, N, ld_grad >= G] = the
+ *                         gradient sq_he2rna_topk_mean_bwd gives for grad_out = grad_scale * (pred - target), bit-identical; every
+ *                         element of [:, :, :G] is written, zeros included, columns >= G are untouched.  grad_scores may be NULL
+ *                         (forward only).  Bounds on N, k and n_ks as sq_he2rna_topk_mean.  The ranking and the gradient are one
+ *                         launch; a one-block launch behind it adds the blocks' partial sums of the loss.
+ *   sq_he2rna_dropout   : in place on act f32 [rows, ld], columns < width: an element is kept when u >= p and scaled by 1 / (1 - p).
+ *                         u in [0, 1) is word (column % 4) of Philox4x32-10 with key = seed on the counter (column / 4, row, layer,
+ *                         step): a pure function of (seed, step, layer, row, column), whatever the grid.  p = 0 launches nothing;
+ *                         p >= 1 is refused.  0 <= step < 2^32.
+ *   sq_he2rna_dropout_gate : grad[r, c] = act[r, c] > 0 ? grad[r, c] / (1 - p) : 0 for c < width, in place: ReLU and dropout backward
+ *                         from the saved post-dropout activation, no stored mask.  16-byte accesses when both tables allow them,
+ *                         a scalar tail for widths that are no multiple of 4.
+ *   sq_he2rna_train_forward : x f32 [B * N, C] token-major (the loader's layout); the tile mask is taken over all C channels, the
+ *                         model reads the last dims[0].  Layer stack from the flat buffer (sq_linear, bias and ReLU in the
+ *                         epilogue), dropout behind every hidden layer (layer = its index), then the loss head with
+ *                         grad_scale.  Saves the padded input, every layer's output and the gradient of the scores in the
+ *                         workspace: sq_he2rna_train_workspace_bytes gives its size and, in act_offsets (NULL or [n_layers + 1]),
+ *                         where the input (0) and layer i's output (i + 1) lie, in floats from its start, as [B * N,
+ *                         round_up(width, 8)] tables.
+ *   sq_he2rna_train_backward : the flat gradient of the loss sq_he2rna_train_forward left in the SAME workspace (same dims, B, N,
+ *                         p_drop, params): sq_linear_weight_grad with the bias sums, dX as NT products on transposed weight copies
+ *                         made here, sq_he2rna_dropout_gate between them.  The input gets no gradient.  Every element of every
+ *                         tensor of `grads` is written; the gaps between tensors are not.
+ * The optimiser of the step is sq_adamw_step with weight_decay = 0: torch.optim.Adam(lr, weight_decay=0.) term for term.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_HE2RNA_MAX_LAYERS 8
+int sq_he2rna_param_layout(const int32_t* dims, int n_layers, int64_t* w_off, int64_t* b_off, int64_t* total);
+size_t sq_he2rna_loss_head_workspace_bytes(int batch, int n_genes);
+int sq_he2rna_loss_head(const float* scores, int ld_scores, const float* mask, const int32_t* ks, int n_ks, float scale,
+                        const float* target, float grad_scale, float* pred, float* loss_out, float* grad_scores, int ld_grad,
+                        int batch, int n_tiles, int n_genes, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+int sq_he2rna_dropout(float* act, int ld, int rows, int width, float p, long long seed, long long step, int layer,
+                      sq_stream_t stream);
+int sq_he2rna_dropout_gate(float* grad, int ld_grad, const float* act, int ld_act, int rows, int width, float p,
+                           sq_stream_t stream);
+size_t sq_he2rna_train_workspace_bytes(const int32_t* dims, int n_layers, int batch, int n_tiles, int64_t* act_offsets);
+int sq_he2rna_train_forward(const float* x, int batch, int n_tiles, int n_channels, const int32_t* dims, int n_layers,
+                            const float* params, const int32_t* ks, int n_ks, float scale, float p_drop, long long seed,
+                            long long step, const float* target, float grad_scale, float* pred, float* loss_out, void* workspace,
+                            size_t workspace_bytes, sq_stream_t stream);
+int sq_he2rna_train_backward(int batch, int n_tiles, const int32_t* dims, int n_layers, const float* params, float p_drop,
+                             float* grads, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Pillow-exact resize of uint8 patches (the resize in front of the extractors: `transforms.Resize(224)` on a PIL image,
  * /root/reference/pre_processing/compute_features_hdf5.py:53-56,125-126 and spatial_vis/visualize.py:226-230, which is
  * Image.resize(..., BILINEAR); `patch.resize(patch_size)`, pre_processing/patch_gen_hdf5.py:117, Pillow's default BICUBIC).

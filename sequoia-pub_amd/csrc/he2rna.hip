@@ -13,16 +13,11 @@
 // Sums are accumulated in fp64 (the reference adds fp32 values in sorted order: equal within fp32 rounding).
 #include "../../include/sequoia_hip.h"
 #include "elementwise.h"
+#include "he2rna.h"
 
 namespace {
 
-constexpr int HE_MAX_N = 128, HE_MAX_KS = 16, HE_THREADS = 256;
-
-struct HeKs {
-    int k[HE_MAX_KS];
-    int n;
-    float scale;
-};
+constexpr int HE_THREADS = 256;
 
 __global__ __launch_bounds__(256) void he2rna_mask_kernel(const float* __restrict__ x, int rows, int C, float* __restrict__ mask) {
     // one wave per row: max over the C channels of a token-major row
@@ -154,17 +149,6 @@ __global__ __launch_bounds__(T) void he2rna_topk_kernel(const float* __restrict_
     }
 }
 
-int fill_ks(const int32_t* ks, int n_ks, float scale, int N, HeKs* o) {
-    SQ_REQUIRE(ks && n_ks >= 1 && n_ks <= HE_MAX_KS, "he2rna: %d values of k (1..%d)", n_ks, HE_MAX_KS);
-    for (int i = 0; i < n_ks; ++i) {
-        SQ_REQUIRE(ks[i] >= 1 && ks[i] <= N, "he2rna: k=%d out of range for %d tiles (torch.topk would raise)", ks[i], N);
-        o->k[i] = ks[i];
-    }
-    o->n = n_ks;
-    o->scale = scale;
-    return SQ_OK;
-}
-
 }  // namespace
 
 extern "C" int sq_he2rna_tile_mask(const float* x_tokens, int n_rows, int n_channels, float* mask, sq_stream_t stream_) {
@@ -179,7 +163,7 @@ extern "C" int sq_he2rna_topk_mean(const float* scores, int ld_scores, const flo
     SQ_REQUIRE(scores && mask && out && B >= 1 && G >= 1 && ld_scores >= G, "he2rna_topk_mean: bad arguments");
     SQ_REQUIRE(N >= 1 && N <= HE_MAX_N, "he2rna_topk_mean: %d tiles per slide (1..%d)", N, HE_MAX_N);
     HeKs k;
-    if (int e = fill_ks(ks, n_ks, scale, N, &k)) return e;
+    if (int e = he_fill_ks(ks, n_ks, scale, N, &k)) return e;
     const size_t lds = (size_t)N * HE_THREADS * sizeof(float);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
@@ -198,7 +182,7 @@ extern "C" int sq_he2rna_topk_mean_bwd(const float* scores, int ld_scores, const
     SQ_REQUIRE(scores && mask && grad_out && grad_scores && B >= 1 && G >= 1 && ld_scores >= G && ld_grad >= G, "he2rna_topk_mean_bwd: bad arguments");
     SQ_REQUIRE(N >= 1 && N <= HE_MAX_N, "he2rna_topk_mean_bwd: %d tiles per slide (1..%d)", N, HE_MAX_N);
     HeKs k;
-    if (int e = fill_ks(ks, n_ks, scale, N, &k)) return e;
+    if (int e = he_fill_ks(ks, n_ks, scale, N, &k)) return e;
     const size_t lds = (size_t)N * HE_THREADS * sizeof(float);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
@@ -218,7 +202,7 @@ extern "C" int sq_he2rna_window_topk_mean(const float* scores, int ld_scores, co
                "he2rna_window_topk_mean: bad arguments");
     SQ_REQUIRE(N >= 1 && N <= HE_MAX_N, "he2rna_window_topk_mean: %d tiles per window (1..%d)", N, HE_MAX_N);
     HeKs k;
-    if (int e = fill_ks(ks, n_ks, scale, N, &k)) return e;
+    if (int e = he_fill_ks(ks, n_ks, scale, N, &k)) return e;
     const size_t lds = (size_t)N * HE_WIN_THREADS * sizeof(float);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {

@@ -10,7 +10,12 @@ top-k over the tiles and the position-weighted mean of he2rna.py:93-99 -- for al
 launch -- are ``sq_he2rna_tile_mask`` / ``sq_he2rna_topk_mean``; the backward pass is ``sq_he2rna_topk_mean_bwd``,
 ``sq_linear`` on transposed weights and ``sq_linear_weight_grad``.  Dropout masks are drawn with torch's device RNG
 (no stream of the reference's CPU generator can be reproduced on another device anyway); everything else is C calls.
-There is no CPU fallback: tensors must live on the MI355X."""
+There is no CPU fallback: tensors must live on the MI355X.
+
+``fit(engine="fused")`` trains on ``He2rnaTrainStep`` instead: parameters, gradient and Adam moments in one flat padded
+buffer, a step = ``sq_he2rna_train_forward`` + ``sq_he2rna_train_backward`` + ``sq_adamw_step`` (csrc/he2rna_train.hip:
+counter-based dropout without stored masks, one loss-head launch that ranks every column once), the validation score
+from one ``sq_batch_metrics`` call.  ``fit``'s default engine, ``forward`` and the loops above are unchanged."""
 import os
 import time
 
@@ -245,6 +250,15 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
         eye = _ScoresFn.apply(x, self.p_drop if self.training else 0.0, self.input_dim, self._workspace(x.device), *self._params())
         return eye
 
+    def replace_head(self, n_genes):
+        """The ``--change_num_genes`` step of the k-fold experiment (he2rna.py:403-409): a fresh ``Conv1d(layers[-1], n_genes, 1)``
+        becomes the last layer, for fine-tuning a model that was trained on another gene list."""
+        last = getattr(self, "conv" + str(self.n_layers - 1))
+        head = nn.Conv1d(last.in_channels, int(n_genes), kernel_size=1, stride=1, bias=True).to(last.weight.device)
+        setattr(self, "conv" + str(self.n_layers - 1), head)
+        self.output_dim = int(n_genes)
+        return self
+
 
 class _ScoresFn(torch.autograd.Function):
     @staticmethod
@@ -258,6 +272,132 @@ class _ScoresFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         raise NotImplementedError("HE2RNA.conv is an inspection helper; train through forward / forward_fixed_k")
+
+
+# ---------------------------------------------------------------------------------------------
+# the training step as C calls on one flat parameter buffer (csrc/he2rna_train.hip)
+# ---------------------------------------------------------------------------------------------
+def param_layout(dims):
+    """sq_he2rna_param_layout for ``dims = [input_dim, *layers, output_dim]``: (weight offsets, bias offsets, total), in floats.
+    Layer i's weight is ``[dims[i + 1], round_up(dims[i], 8)]`` row-major; every tensor starts on a 16-byte boundary."""
+    d = np.asarray(dims, dtype=np.int32)
+    n = len(d) - 1
+    w, b, total = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64), np.zeros(1, dtype=np.int64)
+    _lib.check(_lib.lib().sq_he2rna_param_layout(d.ctypes.data, n, w.ctypes.data, b.ctypes.data, total.ctypes.data))
+    return [int(v) for v in w], [int(v) for v in b], int(total[0])
+
+
+class He2rnaTrainStep:
+    """One training step of he2rna.py:108-127 -- forward, MSE loss, backward, Adam -- as four C calls
+    (sq_he2rna_train_forward, sq_he2rna_train_backward, sq_adamw_step) on flat fp32 buffers: parameters, gradient and
+    the two Adam moments share the padded layout of ``param_layout``.  The arithmetic of the update is
+    ``torch.optim.Adam(lr, betas, eps, weight_decay=0.)``.
+
+    The module's ``conv{i}.weight`` / ``conv{i}.bias`` become VIEWS of the flat parameter buffer, so ``state_dict()``,
+    ``torch.save(model)``, ``evaluate`` and ``he2rna_predict`` see the current values at any time and ``load_state_dict``
+    writes through.  The model has to be on its device before the step is built and must not be moved afterwards.
+
+    Dropout needs no stored mask: unit (row, column) of hidden layer i is kept in step s when Philox4x32-10, keyed by
+    ``seed``, says so for (s, i, row, column); ``step_index`` is the s of the next step."""
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, seed=0):
+        _lib.require_gpu()
+        params = model._params()
+        dev = params[0].device
+        if dev.type != "cuda":
+            raise _lib.SequoiaHipError("He2rnaTrainStep needs the model on the GPU (no CPU fallback)")
+        self.model, self.device = model, dev
+        self.lr, self.betas, self.eps, self.seed = float(lr), (float(betas[0]), float(betas[1])), float(eps), int(seed)
+        self.dims = np.asarray([params[0].shape[1]] + [w.shape[0] for w in params[0::2]], dtype=np.int32)
+        self.n_layers = len(self.dims) - 1
+        self.w_off, self.b_off, self.total = param_layout(self.dims)
+        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (torch.zeros(self.total, dtype=torch.float32, device=dev) for _ in range(4))
+        for (_, view), p in zip(self._views(self.flat), params):
+            view.copy_(p.detach())
+            p.data = view
+        self.t = 0                     # Adam's step count
+        self.step_index = 0            # dropout stream position
+        self.pred = None               # raw predictions of the last step, f32 [B, G]
+        self._ws, self._shape, self._act_off = None, None, None
+
+    def _views(self, flat):
+        """(state_dict key, view of `flat`) per tensor, in ``model._params()`` order."""
+        for i in range(self.n_layers):
+            n_in, n_out = int(self.dims[i]), int(self.dims[i + 1])
+            ld = _up(n_in, 8)
+            yield f"conv{i}.weight", flat[self.w_off[i]:self.w_off[i] + n_out * ld].view(n_out, ld)[:, :n_in].unsqueeze(-1)
+            yield f"conv{i}.bias", flat[self.b_off[i]:self.b_off[i] + n_out]
+
+    def param_views(self):
+        return dict(self._views(self.flat))
+
+    def grad_views(self):
+        return dict(self._views(self.grad))
+
+    def padding_mask(self):
+        """bool [total]: True where the flat layout holds padding (weight columns >= n_in, gaps behind a bias)."""
+        pad = torch.ones(self.total, dtype=torch.bool, device=self.device)
+        for _, v in self._views(pad):
+            v.fill_(False)
+        return pad
+
+    def _workspace(self, B, N):
+        if self._shape != (B, N):
+            off = np.zeros(self.n_layers + 1, dtype=np.int64)
+            need = _lib.lib().sq_he2rna_train_workspace_bytes(self.dims.ctypes.data, self.n_layers, B, N, off.ctypes.data)
+            if need == 0:
+                raise _lib.SequoiaHipArgError(f"libsequoia_hip: {_lib.lib().sq_last_error().decode()}")
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._shape, self._act_off = (B, N), [int(o) for o in off]
+        return self._ws
+
+    def saved_activations(self):
+        """Copies of what the last step's forward pass saved: the hidden layers' outputs after ReLU and dropout, f32 [B * N, width]."""
+        B, N = self._shape
+        ws = self._ws.view(torch.float32)
+        out = []
+        for i in range(1, self.n_layers):
+            ld = _up(int(self.dims[i]), 8)
+            out.append(ws[self._act_off[i]:self._act_off[i] + B * N * ld].view(B * N, ld)[:, :int(self.dims[i])].clone())
+        return out
+
+    def forward_backward(self, x, y, k):
+        """Loss (device scalar) and flat gradient of one batch at top-k `k`, without the update.  x [B, N, C] as the loader
+        gives it (tiles x channels), y [B, G]."""
+        lib, dev, m = _lib.lib(), self.device, self.model
+        x = x.to(dev, torch.float32).contiguous()
+        y = torch.as_tensor(y).to(dev, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] < m.input_dim or tuple(y.shape) != (x.shape[0], int(self.dims[-1])):
+            raise ValueError(f"He2rnaTrainStep: x must be [batch, tiles, channels >= {m.input_dim}] and y [batch, {int(self.dims[-1])}], "
+                             f"got {tuple(x.shape)} and {tuple(y.shape)}")
+        B, N, C = x.shape
+        G = int(self.dims[-1])
+        ws = self._workspace(B, N)
+        ks = np.asarray([int(k)], dtype=np.int32)
+        self.pred = torch.empty(B, G, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            _lib.check(lib.sq_he2rna_train_forward(_lib.ptr(x), B, N, C, self.dims.ctypes.data, self.n_layers, _lib.ptr(self.flat), ks.ctypes.data, 1,
+                                                   1.0, m.p_drop, self.seed, self.step_index, _lib.ptr(y), 2.0 / (B * G), _lib.ptr(self.pred),
+                                                   _lib.ptr(loss), _lib.ptr(ws), ws.numel(), st))
+            _lib.check(lib.sq_he2rna_train_backward(B, N, self.dims.ctypes.data, self.n_layers, _lib.ptr(self.flat), m.p_drop, _lib.ptr(self.grad),
+                                                    _lib.ptr(ws), ws.numel(), st))
+        return loss
+
+    def step(self, x, y):
+        """One optimisation step; returns the batch's loss as a device tensor (no host read).  The k of the step is drawn with one
+        ``np.random.choice(model.ks)``, as ``HE2RNA.forward`` draws it in training mode."""
+        k = int(np.random.choice(self.model.ks))              # he2rna.py:85
+        loss = self.forward_backward(x, y, k)
+        self.t += 1
+        self.step_index += 1
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().sq_adamw_step(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), None,
+                                                self.total, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, self.t, 1.0,
+                                                _lib.stream_ptr(self.device)))
+        return loss
 
 
 # ---------------------------------------------------------------------------------------------
@@ -323,33 +463,84 @@ def he2rna_predict(model, dataloader):
     return np.concatenate(preds, 0), np.concatenate(labels, 0), np.concatenate(wsis, 0), np.concatenate(projs, 0)
 
 
-def fit(model, lr, train_loader, valid_loader, test_loader, params={}, fold=None, optimizer=None, path=None, verbose=True):
+def training_epoch_fused(trainer, dataloader):
+    """training_epoch on He2rnaTrainStep: the per-batch losses stay on the device, their mean (he2rna.py:125) is read once."""
+    trainer.model.train()
+    losses = [trainer.step(x, y) for x, y, _, _ in dataloader]
+    return float(torch.stack(losses).mean())
+
+
+def device_validation_score(pred, labels):
+    """``compute_correlations(labels, ReLU(pred))`` for raw predictions and labels f32 [n, G] on the device, as a device
+    scalar: one sq_batch_metrics call over the whole set (fp64 Pearson r per gene, genes with a constant label skipped, NaN r
+    dropped, NaN when no gene is left)."""
+    lib, dev = _lib.lib(), pred.device
+    n, G = pred.shape
+    p = torch.relu(pred.detach().to(torch.float32)).contiguous()
+    y = labels.to(dev, torch.float32).contiguous()
+    out3 = torch.empty(3, dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.sq_train_scratch_bytes(G), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sq_batch_metrics(_lib.ptr(p), _lib.ptr(y), n, G, _lib.ptr(out3), _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    return out3[1]
+
+
+def evaluate_device(model, dataloader):
+    """``evaluate`` with predictions and labels kept on the device: the loss on the raw predictions per batch, the score from
+    device_validation_score over the whole validation set; two host reads per pass."""
+    model.eval()
+    loss_fn = nn.MSELoss()
+    losses, preds, labels = [], [], []
+    with torch.no_grad():
+        for x, y, _, _ in _batches(model, dataloader):
+            y = torch.as_tensor(y).float().to(model.device)
+            pred = model(x)
+            losses.append(loss_fn(pred, y))
+            preds.append(pred)
+            labels.append(y)
+    score = device_validation_score(torch.cat(preds), torch.cat(labels))
+    return float(torch.stack(losses).mean()), float(score)
+
+
+def fit(model, lr, train_loader, valid_loader, test_loader, params={}, fold=None, optimizer=None, path=None, verbose=True,
+        engine="autograd", seed=0):
     """he2rna.py:217-318: Adam(lr) unless an optimizer is given, up to ``max_epochs`` (200) epochs; with a validation
     loader the model with the best mean correlation is kept (``model[_fold].pt``) and training stops after ``patience``
     (100) epochs without improvement; returns the test predictions when a test loader is given, else the model.
-    (The reference's wandb calls inside the validation branch reference an undefined ``args``; they are not mirrored.)"""
+    (The reference's wandb calls inside the validation branch reference an undefined ``args``; they are not mirrored.)
+    ``engine="fused"``: the steps run on He2rnaTrainStep (Adam(lr) only: an ``optimizer`` is refused; ``seed`` keys its
+    dropout) and the validation pass on evaluate_device; saving, patience and reloading follow the same rules."""
+    if engine not in ("autograd", "fused"):
+        raise ValueError(f"fit: engine must be 'autograd' or 'fused', got {engine!r}")
+    if engine == "fused" and optimizer is not None:
+        raise ValueError("fit: engine='fused' runs its own Adam(lr); it cannot take an optimizer")
     if path is not None and not os.path.exists(path):
         os.mkdir(path)
     cfg = {"max_epochs": 200, "patience": 100}
     cfg.update(params)
-    if optimizer is None:
-        optimizer = torch.optim.Adam(list(model.parameters()), lr=lr, weight_decay=0.0)
+    if engine == "fused":
+        trainer = He2rnaTrainStep(model, lr, seed=seed)
+        run_epoch, run_eval = (lambda loader: training_epoch_fused(trainer, loader)), evaluate_device
+    else:
+        if optimizer is None:
+            optimizer = torch.optim.Adam(list(model.parameters()), lr=lr, weight_decay=0.0)
+        run_epoch, run_eval = (lambda loader: training_epoch(model, loader, optimizer)), evaluate
     name = "model" if fold is None else "model_" + str(fold)
     best = 0
     if valid_loader is not None:
-        _, best = evaluate(model, valid_loader)
+        _, best = run_eval(model, valid_loader)
         if np.isnan(best):
             best = 0
     since_best, t0 = 0, time.time()
     try:
         for e in range(cfg["max_epochs"]):
             since_best += 1
-            train_loss = training_epoch(model, train_loader, optimizer)
+            train_loss = run_epoch(train_loader)
             if verbose:
                 print("Epoch {}/{} - {:.2f}s".format(e + 1, cfg["max_epochs"], time.time() - t0))
             t0 = time.time()
             if valid_loader is not None:
-                valid_loss, score = evaluate(model, valid_loader)
+                valid_loss, score = run_eval(model, valid_loader)
                 if verbose:
                     print("loss: {:.4f}, val loss: {:.4f}".format(train_loss, valid_loss))
                     print("correlations: {:.3f}".format(score))
