@@ -866,7 +866,24 @@ int sq_emd_solve(const double* grids, int cells, const int32_t* dims, int P, int
  *                      heads * 64], row-major, in `dtype`: SQ_DTYPE_F32 or SQ_DTYPE_BF16; SQ_DTYPE_F16X3: the fp16 hi plane
  *                      followed by the lo plane, n_images * n_tokens * 3 * heads * 64 elements apart in qkv and
  *                      n_images * n_tokens * heads * 64 in o.  1 <= n_tokens <= 256; 16-byte aligned pointers.
+ *   sq_dbg_resnet50_taps : sq_resnet50_extract_hw (same arguments, same admitted shapes, same forward and routes) that also
+ *                      copies intermediate tensors out as fp32 NHWC: fp32 as is, bf16 widened, split modes hi + lo added in fp32.
+ *                      Tap order (SQ_RESNET50_TAPS - 1 = 33 tensors, one after another in `taps`):
+ *                        0            the stem's output behind the max-pool, [n, ceil(H/4), ceil(W/4), 64];
+ *                        1 + 2k       t1 of bottleneck k (k = 0..15 over layers 1-4 of 3, 4, 6, 3 blocks): the reduce 1x1's output
+ *                                     as that block's 3x3 reads it, [n, h, w, planes] on the block's INPUT map (h x w: ceil(H/4) x
+ *                                     ceil(W/4) in layer 1; the first block of layers 2-4 still has the previous layer's map),
+ *                                     planes = 64, 128, 256, 512 per layer -- whichever launch produced it (its own GEMM, the stem
+ *                                     launch, or the previous block's fused tail / chain);
+ *                        2 + 2k       y of bottleneck k, the block's output, [n, oh, ow, 4 * planes] (oh x ow: ceil of half the
+ *                                     input map in the first block of layers 2-4, else the input map).
+ *                      tap_offsets: host array of SQ_RESNET50_TAPS int64: element i = first float of tap i, element 33 = the total.
+ *                      taps == NULL: only tap_offsets is filled (to size the buffer), nothing is launched and the other pointers
+ *                      may be NULL.  A taps_floats below the total, or a shape sq_resnet50_extract_hw refuses, is an error
+ *                      before anything is launched.  t2 and the downsample tensor are not tapped: on the fused routes they
+ *                      never leave the CU.
  * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_RESNET50_TAPS 34
 int sq_dbg_set(int key, int value);
 int sq_dbg_chain_x3(int f16, int n2, int ds, int tail, long long P, int W, void* act, void* wts, void* fp, void* frag, void* stream);
 int sq_dbg_chain_x3w(int f16, int c, int n2, long long P, const void* t2_hi, const void* t2_lo, const void* res_hi, const void* res_lo,
@@ -874,6 +891,10 @@ int sq_dbg_chain_x3w(int f16, int c, int n2, long long P, const void* t2_hi, con
                      const void* w1n_hi, const void* w1n_lo, const float* b3, const float* cs3, const float* b1n, const float* cs1n,
                      int w_tiled, void* stream);
 int sq_dbg_uni_attn(int dtype, const void* qkv, void* o, int n_images, int n_tokens, int heads, void* stream);
+int sq_dbg_resnet50_taps(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
+                         const float* patches_f32_nchw, int n_patches, int height, int width, float* features,
+                         void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream,
+                         float* taps, size_t taps_floats, int64_t* tap_offsets);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,36 @@ __global__ void avgpool7_x3_kernel(const bf16_t* __restrict__ in, long long plan
     if (nonfinite && !(fabsf(acc) <= 3.0e38f)) atomicOr(nonfinite, 1u);
 }
 
+// sq_dbg_resnet50_taps: one activation -> fp32 (MODE 0: fp32 copied, 1: bf16 widened, 2 / 3: bf16 / fp16 hi + lo planes added in
+// fp32); thread = 8 consecutive elements (every activation's channel count is a multiple of 64)
+template <int MODE>
+__global__ __launch_bounds__(256) void tap_copy_kernel(const void* __restrict__ src, long long plane, float* __restrict__ dst, size_t groups) {
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
+        float v[8];
+        if constexpr (MODE == 0) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)src + g * 8), c = *reinterpret_cast<const f32x4*>((const float*)src + g * 8 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = c[e]; }
+        } else if constexpr (MODE == 1) {
+            const u32x4 t = *reinterpret_cast<const u32x4*>((const bf16_t*)src + g * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(t[e] << 16); v[2 * e + 1] = __uint_as_float(t[e] & 0xffff0000u); }
+        } else {
+            const uint16_t* h = (const uint16_t*)src + g * 8;
+            const u32x4 hi = *reinterpret_cast<const u32x4*>(h), lo = *reinterpret_cast<const u32x4*>(h + plane);
+            const uint16_t* hs = reinterpret_cast<const uint16_t*>(&hi);
+            const uint16_t* ls = reinterpret_cast<const uint16_t*>(&lo);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = X3Fmt<MODE == 3>::one(hs[e]) + X3Fmt<MODE == 3>::one(ls[e]);
+        }
+        *reinterpret_cast<f32x4*>(dst + g * 8) = f32x4{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(dst + g * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    }
+}
+
+// where sq_dbg_resnet50_taps copies to; nullptr in rn_extract: the forward as every public entry runs it
+struct RnTaps { float* out; const int64_t* off; };
+
 struct ConvSpec { int cin, cout, k, stride, pad; };
 
 void build_specs(ConvSpec* specs) {
@@ -225,6 +255,22 @@ void rn_bufs(int dtype, int n, int H, int W, char* base, RnBufs* o) {
     for (int i = 0; i < 5; ++i) o->act[i] = take(act);
     o->frag = (dtype == SQ_BF16X3 || dtype == SQ_F16X3) ? take(sq_chain_x3_frag_bytes()) : nullptr;     // chain_x3.hip's fragment-ordered weights
     o->bytes = sq_align_up(off, 256);
+}
+
+// first float of each tap of sq_dbg_resnet50_taps (include/sequoia_hip.h has the order), off[33] = the total
+void rn_tap_offsets(int n, int H0, int W0, int64_t* off) {
+    int H = ((H0 + 1) / 2 + 1) / 2, W = ((W0 + 1) / 2 + 1) / 2;
+    int64_t o = 0;
+    int i = 0;
+    off[i++] = o; o += (int64_t)n * H * W * 64;
+    const int planes[4] = {64, 128, 256, 512}, blocks[4] = {3, 4, 6, 3};
+    for (int li = 0; li < 4; ++li)
+        for (int b = 0; b < blocks[li]; ++b) {
+            off[i++] = o; o += (int64_t)n * H * W * planes[li];             // t1 on the block's input map
+            if (b == 0 && li > 0) { H = (H + 1) / 2; W = (W + 1) / 2; }
+            off[i++] = o; o += (int64_t)n * H * W * planes[li] * 4;         // y
+        }
+    off[i] = o;
 }
 
 }  // namespace
@@ -268,7 +314,8 @@ extern "C" size_t sq_resnet50_workspace_bytes_hw(int dtype, int n_patches, int h
 }
 
 static int rn_extract(bool hw_rule, int dtype, const void* weights, const float* bias, const uint8_t* patches_u8, const float* patches_f32_nchw, int n,
-                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st);
+                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st,
+                      const RnTaps* taps = nullptr);
 
 extern "C" int sq_resnet50_extract(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
                                    const float* patches_f32_nchw, int n, int S, float* features, void* workspace,
@@ -291,9 +338,27 @@ extern "C" int sq_resnet50_extract_hw(int dtype, const void* weights, const floa
                       nonfinite_flag, (hipStream_t)stream_);
 }
 
+extern "C" int sq_dbg_resnet50_taps(int dtype, const void* weights, const float* bias, const uint8_t* patches_u8,
+                                    const float* patches_f32_nchw, int n, int height, int width, float* features, void* workspace,
+                                    size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream_, float* taps, size_t taps_floats,
+                                    int64_t* tap_offsets) {
+    SQ_REQUIRE(tap_offsets != nullptr, "resnet50_taps: null tap_offsets");
+    SQ_REQUIRE(n >= 1 && rn_hw_admitted(height, width), "resnet50_taps: n=%d, patch %d x %d; height and width must each lie in [%d, %d]",
+               n, height, width, SQ_RESNET50_HW_MIN, SQ_RESNET50_HW_MAX);
+    rn_tap_offsets(n, height, width, tap_offsets);
+    if (!taps) return SQ_OK;
+    SQ_REQUIRE(taps_floats >= (size_t)tap_offsets[SQ_RESNET50_TAPS - 1], "resnet50_taps: taps buffer of %zu floats < required %lld",
+               taps_floats, (long long)tap_offsets[SQ_RESNET50_TAPS - 1]);
+    SQ_REQUIRE(((uintptr_t)taps & 15) == 0, "resnet50_taps: taps must be 16-byte aligned");
+    const RnTaps t{taps, tap_offsets};
+    return rn_extract(true, dtype, weights, bias, patches_u8, patches_f32_nchw, n, height, width, features, workspace, workspace_bytes,
+                      nonfinite_flag, (hipStream_t)stream_, &t);
+}
+
 // the forward pass itself for an H0 x W0 input.  hw_rule: admit what sq_resnet50_extract_hw admits (else: the square entries' rule)
 static int rn_extract(bool hw_rule, int dtype, const void* weights, const float* bias, const uint8_t* patches_u8, const float* patches_f32_nchw, int n,
-                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st) {
+                      int H0, int W0, float* features, void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, hipStream_t st,
+                      const RnTaps* taps) {
     SQ_REQUIRE(dtype == SQ_F32 || dtype == SQ_BF16 || dtype == SQ_BF16X3 || dtype == SQ_F16X3, "resnet50: dtype %d", dtype);
     SQ_REQUIRE(weights && bias && features && workspace, "resnet50: null pointer");
     SQ_REQUIRE((patches_u8 != nullptr) != (patches_f32_nchw != nullptr), "resnet50: give exactly one of patches_u8 / patches_f32_nchw");
@@ -360,6 +425,19 @@ static int rn_extract(bool hw_rule, int dtype, const void* weights, const float*
         return sq_launch_gemm(g, dtype, st);
     };
 #define RUN(expr) do { if (int _e = (expr)) return _e; } while (0)
+    // sq_dbg_resnet50_taps only (taps == nullptr: no launch): tap `idx` <- the activation at src, sized by the offset table
+    auto tap = [&](int idx, const void* src) -> int {
+        if (!taps) return SQ_OK;
+        const size_t groups = (size_t)(taps->off[idx + 1] - taps->off[idx]) / 8;
+        float* dst = taps->out + taps->off[idx];
+        size_t nb = (groups + 255) / 256; if (nb > 65535) nb = 65535;
+        if (f16) hipLaunchKernelGGL(tap_copy_kernel<3>, dim3((int)nb), dim3(256), 0, st, src, act_plane, dst, groups);
+        else if (x3) hipLaunchKernelGGL(tap_copy_kernel<2>, dim3((int)nb), dim3(256), 0, st, src, act_plane, dst, groups);
+        else if (lp) hipLaunchKernelGGL(tap_copy_kernel<1>, dim3((int)nb), dim3(256), 0, st, src, act_plane, dst, groups);
+        else hipLaunchKernelGGL(tap_copy_kernel<0>, dim3((int)nb), dim3(256), 0, st, src, act_plane, dst, groups);
+        SQ_LAUNCH_CHECK();
+        return SQ_OK;
+    };
 
     int H = (OH1 + 1) / 2, Wd = (OW1 + 1) / 2;    // after the max-pool (3x3, stride 2, pad 1): ceil of half per axis
     bool stem_t1 = false;
@@ -407,8 +485,9 @@ static int rn_extract(bool hw_rule, int dtype, const void* weights, const float*
     const bool fuse_chain256 = fuse_chain;
     int xi = 1, ci = 1, t1i = stem_t1 ? 2 : -1;
     const int blocks[4] = {3, 4, 6, 3};
+    int blk = 0;                                  // bottleneck index 0..15: taps 2 blk (its x), 1 + 2 blk (its t1)
     for (int li = 0; li < 4; ++li)
-        for (int bk = 0; bk < blocks[li]; ++bk) {
+        for (int bk = 0; bk < blocks[li]; ++bk, ++blk) {
             int free_[4], nf = 0;
             for (int i = 0; i < 5; ++i) if (i != xi && i != t1i) free_[nf++] = i;
             void* x = b.act[xi];
@@ -418,7 +497,9 @@ static int rn_extract(bool hw_rule, int dtype, const void* weights, const float*
             const bool has_ds = bk == 0;
             // 3x3 stride 2 pad 1 and the 1x1 stride 2 downsample both give floor((s - 1) / 2) + 1 = ceil(s / 2)
             const int OH = (H - 1) / c2.stride + 1, OW = (Wd - 1) / c2.stride + 1;
+            RUN(tap(2 * blk, x));                 // the stem's output (blk 0) or the previous block's y, live here
             if (t1i < 0) RUN(conv(c1, x, H, Wd, t1, H, Wd, nullptr, SQ_ACT_RELU));
+            RUN(tap(2 * blk + 1, t1));            // from this GEMM, the stem launch or the previous block's tail / chain
             const int cnext = ci + (has_ds ? 4 : 3);
             if (fuse56 && li == 0) {
                 void* y = b.act[free_[1]]; void* t1n = b.act[free_[2]];
@@ -528,6 +609,7 @@ static int rn_extract(bool hw_rule, int dtype, const void* weights, const float*
             t1i = -1;
             H = OH; Wd = OW;
         }
+    RUN(tap(2 * blk, b.act[xi]));                 // the last block's y
     {
         const int total = n * 2048;
         if (f16) hipLaunchKernelGGL(avgpool7_x3_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, (const bf16_t*)b.act[xi], act_plane, features, n, H, Wd, 2048, nonfinite_flag);
