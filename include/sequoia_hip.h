@@ -857,6 +857,72 @@ int sq_emd_solve(const double* grids, int cells, const int32_t* dims, int P, int
                  sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Spot normalisation: the first lines of spatial_vis/get_emd.py (get_emd.py:148-155) -- sc.pp.normalize_total,
+ * sc.pp.log1p and sc.pp.scale of the raw spot matrix, then adata[:, gene].X -- restated in f64 (scanpy works in the
+ * matrix's own dtype, usually float32: NO digit-for-digit claim against it is made).  X is [n_spots, n_genes] in CSR:
+ * indptr int64 [n_spots + 1] and indices int32 [nnz] on the device, data [nnz] f32 (data_kind = SQ_SN_DATA_F32), f64
+ * (SQ_SN_DATA_F64) or int32 (SQ_SN_DATA_I32), widened to f64 first; a row's indices strictly increasing, values
+ * non-negative and finite.  Every argument is checked before the first launch; the calls are asynchronous on `stream`
+ * and never synchronise; no floating-point atomics, every sum in a fixed order that depends only on the shapes: two
+ * calls give the same bytes.  1 <= n_spots <= SQ_GT_MAX_SPOTS, 1 <= n_genes <= SQ_SN_MAX_GENES, 0 <= nnz <= SQ_SN_MAX_NNZ.
+ * A row whose indptr pair is not 0 <= start <= end <= nnz is read nowhere by any entry.
+ *
+ *   sq_spot_counts      : c_i = sum_j X_ij (get_emd.py:148-155, normalize_total's counts per cell): counts f64 [n_spots].
+ *                         One wave per row, the lanes stride the row's entries with an f64 partial each, the 64 partials
+ *                         are combined by a fixed xor butterfly (rows hold 0..n_genes entries).  With integer counts
+ *                         and row totals below 2^53 every order is exact: c equals numpy's sum bit for bit; for
+ *                         fractional data it is within the any-order bound.  status, one int32 on the device, is set
+ *                         to 0 first and then gets SQ_SN_BAD_ORDER (a row's indices not strictly increasing),
+ *                         SQ_SN_BAD_INDEX (an index outside [0, n_genes)), SQ_SN_BAD_VALUE (a negative or non-finite
+ *                         value) and SQ_SN_BAD_INDPTR (a row's start and end not 0 <= start <= end <= nnz) or-ed in
+ *                         (an integer atomic); with a non-zero status no result is to be used.
+ *   sq_spot_target      : get_emd.py:148-155, normalize_total's target: after [1] f64 = np.median(c[c > 0]) -- the middle
+ *                         value, or (a + b) / 2.0 of the two middle ones -- and n_positive [1] int32 = #(c > 0); no
+ *                         positive spot: after = NaN.  Exact for any spot count: the counts are sorted in chunks of
+ *                         sq_map_rank_chunk_rows() by the percentile's kernel (csrc/colsort.hip), then the k-th smallest
+ *                         is selected by bisection on the f64 bit pattern, counting keys <= x with the upper-bound search
+ *                         of csrc/colsort.h over the chunks.  One workgroup.
+ *   sq_spot_log_columns : get_emd.py:148-155, normalize_total's division, log1p and adata[:, gene]: L f64 [n_spots, C],
+ *                         L[i][c] = log1p(X[i][g] / s_i), g = cols[c] (any order, repeats allowed; NULL: all genes,
+ *                         C = n_genes), s_i = (c_i + (c_i == 0)) / after -- scanpy's two divisions in scanpy's
+ *                         order; counts and after are device pointers (the outputs of the two entries above).  An
+ *                         absent entry gives exactly 0.0.  With a column list: a binary search in the row's sorted
+ *                         indices, one thread per (row, column), consecutive threads on consecutive columns; with NULL:
+ *                         L is zero-filled and every row scatters its entries (one wave per row).  The two paths give
+ *                         the same bytes for the same columns.  log1p is the device library's f64 log1p: L lies
+ *                         within 1 ulp of the extended-precision truth rounded to f64 (measured on an MI355X over the
+ *                         tests' inputs, largest distance 1.00 ulp: profiles/spot_norm_rate.txt; the tests allow 2).
+ *                         n_spots C <= SQ_SN_MAX_CELLS.
+ *   sq_spot_scale       : get_emd.py:148-155, sc.pp.scale (zero-centred, max_value=None): per column of L f64 [n, ld],
+ *                         mean[c] = sum_i L_ic / n, sd[c] = sqrt(sum_i (L_ic - mean)^2 / (n - 1)) (two-pass), an sd of 0
+ *                         becomes 1; write_z = 1: L_ic = (L_ic - mean) / sd in place (a third pass).  Sums run over
+ *                         all n rows, zeros included.  2 <= n <= SQ_GT_MAX_SPOTS, 1 <= C <= ld.  16 consecutive columns
+ *                         per workgroup (coalesced row reads), 16 row lanes per column that each add every 16th row in
+ *                         row order, and an LDS tree in fixed order.  A column that is constant and non-zero gets a
+ *                         rounding-noise sd and z (as in scanpy); an all-zero column gives z = 0 exactly.
+ *   sq_spot_target_workspace_bytes returns 0 exactly for the refused n_spots (the invariant under "Map statistics").
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_SN_MAX_GENES 1048576
+#define SQ_SN_MAX_NNZ 2147483647
+#define SQ_SN_MAX_CELLS 1073741824     /* n_spots x C of one L table (8 GiB of f64) */
+#define SQ_SN_DATA_F32 0
+#define SQ_SN_DATA_F64 1
+#define SQ_SN_DATA_I32 2
+#define SQ_SN_BAD_ORDER 1
+#define SQ_SN_BAD_INDEX 2
+#define SQ_SN_BAD_VALUE 4
+#define SQ_SN_BAD_INDPTR 8
+int sq_spot_counts(const void* data, int data_kind, const int32_t* indices, const int64_t* indptr, int n_spots, int n_genes,
+                   long long nnz, double* counts, int32_t* status, sq_stream_t stream);
+size_t sq_spot_target_workspace_bytes(int n_spots);
+int sq_spot_target(const double* counts, int n_spots, double* after, int32_t* n_positive, void* workspace,
+                   size_t workspace_bytes, sq_stream_t stream);
+int sq_spot_log_columns(const void* data, int data_kind, const int32_t* indices, const int64_t* indptr, int n_spots,
+                        int n_genes, long long nnz, const double* counts, const double* after, const int32_t* cols, int C,
+                        double* L, sq_stream_t stream);
+int sq_spot_scale(double* L, int n, int ld, int C, double* mean, double* sd, int write_z, sq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Test and probe hooks (not a stable interface): the switches and bare kernel launches the tests and tools/ use.
  *   sq_dbg_set       : experiment knobs of the GEMM engines (csrc/gemm.hip lists the keys).
  *   sq_dbg_chain_x3  : one launch of the split-mode expand / reduce chain of the 56 x 56 stage (csrc/chain_x3.hip).

@@ -1,4 +1,4 @@
-"""What the wrappers of the slide analytics (mapstats.py, gtalign.py) share: a device table, column list or vector turned
+"""What the wrappers of the slide analytics (mapstats.py, gtalign.py, spotnorm.py) share: a device table, column list or vector turned
 into the arguments of the C ABI, and the one way a call is made and a shape is refused."""
 from collections import OrderedDict
 

@@ -6,9 +6,14 @@ percentiles of both and of the prediction within the slide, and the number of di
     python -m sequoia_pub_amd.cli.get_emd --slide_nr 242 --pred_folder gbm_celltypes --save_folder gbm_celltypes \\
         --gene_names EGFR,PDGFRA --ground_truth spots_242.csv
 
+    python -m sequoia_pub_amd.cli.get_emd --slide_nr 242 --pred_folder gbm_celltypes --save_folder gbm_celltypes \\
+        --gene_names EGFR,PDGFRA --h5ad auto
+
 Keeps the reference's four flags (with its path conventions as defaults) and adds --pred_csv and --out as explicit paths
-and --ground_truth: a CSV with the columns ``x``, ``y`` and one ALREADY NORMALISED column per gene (the reference reads an
-.h5ad and normalises it with scanpy: normalize_total, log1p, scale -- that stays with the caller).  Writes
+and the ground truth, exactly one of: --h5ad, the slide's raw anndata file, read and normalised on the device as the
+reference does with scanpy (:148-155: normalize_total, log1p, scale -- spotnorm.py, once for all genes where the reference
+redoes it per gene; f64, not scanpy's float32 digits), ``auto`` being the reference's path for --slide_nr; or
+--ground_truth, a CSV with the columns ``x``, ``y`` and one ALREADY NORMALISED column per gene.  Writes
 ``<out>/metrics.csv`` (gene, nr_gt_vals, nr_gt_vals_filt) and ``<out>/aligned.csv``, the per-tile frame of
 ``gtalign.align_ground_truth``.  With --emd, metrics.csv is the reference's file: gene, emd, nr_gt_vals, emd_filt,
 nr_gt_vals_filt -- the earth mover's distance between the predicted and the measured map, raw and as median-filtered
@@ -22,8 +27,9 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .. import gtalign
+from .. import gtalign, spotnorm
 
+H5AD_AUTO = os.path.join(".", "data", "Spatial_Heiland", "data", "AnnDataObject", "raw", "{nr}_T.h5ad")      # get_emd.py:148
 COORDS = ["xcoord", "ycoord", "xcoord_tf", "ycoord_tf"]
 NUM_TILES = 4             # get_emd.py:124: ground-truth spots per predicted tile
 
@@ -36,11 +42,26 @@ def build_parser():
     ap.add_argument("--gene_names", type=str, required=True, help="names of genes (separated by comma) or path to npy array containing gene names")
     ap.add_argument("--pred_csv", default=None, help="the slide's stride-1.csv (default: from --slide_nr and --pred_folder, as the reference)")
     ap.add_argument("--out", default=None, help="output folder (default: from --slide_nr and --save_folder, as the reference)")
-    ap.add_argument("--ground_truth", required=True, help="CSV with the columns x, y and one already-normalised column per gene")
+    ap.add_argument("--ground_truth", default=None, help="CSV with the columns x, y and one already-normalised column per gene")
+    ap.add_argument("--h5ad", default=None, help="the slide's raw .h5ad, normalised on the device (normalize_total, log1p, scale); "
+                                                 "'auto': the reference's path for --slide_nr")
     ap.add_argument("--emd", action="store_true", help="also compute emd and emd_filt per gene and append the slide's line to slide_info.txt")
     ap.add_argument("--max_augmentations", type=int, default=None, help="with --emd: the cap on augmenting paths of one problem (default: 256 per cell of the two maps)")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def parse_args(argv=None):
+    """The parsed arguments with exactly one of --ground_truth and --h5ad, and ``--h5ad auto`` resolved."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if (args.ground_truth is None) == (args.h5ad is None):
+        ap.error("exactly one of --ground_truth (a CSV of normalised spots) and --h5ad (the raw anndata file) must be given")
+    if args.h5ad == "auto":
+        if args.slide_nr is None:
+            ap.error("--h5ad auto needs --slide_nr")
+        args.h5ad = H5AD_AUTO.format(nr=args.slide_nr)
+    return args
 
 
 def resolve_paths(args):
@@ -75,22 +96,26 @@ def write_slide_info(args, pred_csv, out, tiles, first_gene):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     pred_csv, out = resolve_paths(args)
     genes = gene_list(args.gene_names)
     pred = pd.read_csv(pred_csv)
-    truth = pd.read_csv(args.ground_truth)
+    truth = None if args.ground_truth is None else pd.read_csv(args.ground_truth)
     for frame, path, need in ((pred, pred_csv, COORDS + genes), (truth, args.ground_truth, ["x", "y"] + genes)):
-        missing = [c for c in need if c not in frame.columns]
+        missing = [] if frame is None else [c for c in need if c not in frame.columns]
         if missing:
             raise SystemExit(f"{path} lacks the columns {missing[:8]}")
     names = [c for c in pred.columns if c not in COORDS and pd.api.types.is_numeric_dtype(pred[c])]
     device = torch.device(args.device)
     dev = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a, dtype=dtype)).to(device)      # noqa: E731
+    if truth is None:
+        spot_x, spot_y, spot_expr = spotnorm.spots_from_h5ad(args.h5ad, genes, device)
+    else:
+        spot_x, spot_y, spot_expr = dev(truth["x"].values, np.float64), dev(truth["y"].values, np.float64), dev(truth[genes].values, np.float64)
     tiles, metrics = gtalign.align_ground_truth(
         dev(pred[names].values, np.float32), names, dev(pred["xcoord"].values, np.float64), dev(pred["ycoord"].values, np.float64),
         dev(pred["xcoord_tf"].values, np.float64), dev(pred["ycoord_tf"].values, np.float64),
-        dev(truth["x"].values, np.float64), dev(truth["y"].values, np.float64), dev(truth[genes].values, np.float64), genes, num_tiles=NUM_TILES,
+        spot_x, spot_y, spot_expr, genes, num_tiles=NUM_TILES,
         emd=args.emd, max_augmentations=args.max_augmentations)
     os.makedirs(out, exist_ok=True)
     if args.emd:
