@@ -196,20 +196,35 @@ int sq_vit_backward(const sq_vit_config* cfg, int dtype, const float* params, co
 /* ------------------------------------------------------------------------------
  * Training-step pieces of src/vit.py:117-243 `train`
  * ---------------------------------------------------------------------------- */
+/* Scratch contract: a device buffer of sq_train_scratch_bytes(num_outputs) bytes, 8-byte aligned, serves sq_mse_loss_grad for
+ * any n and sq_batch_metrics for that num_outputs (any batch); neither writes a byte beyond it.  Contents on entry are
+ * ignored, contents on return unspecified; calls sharing one scratch must be ordered on one stream.
+ * Alignment of the data pointers of the three entries below: natural (4 bytes for float, 2 for the bf16 shadow) -- the
+ * kernels are element-wise, so any element range of a flat buffer may be passed. */
 size_t sq_train_scratch_bytes(int num_outputs);
 /* nn.MSELoss() (vit.py:129,166): *loss_out = mean((pred-target)^2) over n elements (device scalar);
- * grad[i] = grad_scale * (pred[i]-target[i])  (grad_scale = 2/n for the plain loss; grad may be NULL). */
+ * grad[i] = grad_scale * (pred[i]-target[i])  (grad_scale = 2/n for the plain loss; grad may be NULL: the loss is the
+ * same bits).  The difference is taken in fp32, its squares are summed in fp64 in a fixed order and rounded to float once.
+ * n == 0 or a null pred / target / loss_out / scratch: SQ_ERR_ARG, nothing launched. */
 int sq_mse_loss_grad(const float* pred, const float* target, size_t n, float grad_scale, float* grad, float* loss_out,
                      void* scratch, sq_stream_t stream);
 /* torch.optim.AdamW(lr, amsgrad=False, weight_decay) (src/main.py:180-183) on a flat fp32 buffer;
  * step is the 1-based step count; grads are multiplied by grad_scale first (1/world for an
- * all-reduced sum); params_lp (bf16 shadow) is refreshed in the same pass when not NULL. */
+ * all-reduced sum); params_lp (bf16 shadow) is refreshed in the same pass when not NULL: round-to-nearest-even of the
+ * parameters this call wrote; with NULL params / exp_avg / exp_avg_sq come out the same bits.  Every element is updated
+ * on its own, so one call over [0, n) equals calls over any partition of it into slices, bit for bit (SQ_ADAMW_BUCKETS).
+ * Hyperparameter precision: the ABI passes float.  1 - beta and beta^step are formed from those floats (torch forms them
+ * from the Python doubles), so with beta2 = 0.999 the second moment sits about 1.3e-5 relative below torch's; the effect on
+ * a parameter is below one fp32 rounding of the update (tests/train_prim_cases.py measures both).
+ * n == 0, step < 1 or a null params / grads / exp_avg / exp_avg_sq: SQ_ERR_ARG, nothing launched. */
 int sq_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* params_lp, size_t n,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                   sq_stream_t stream);
 /* Per-batch metrics the reference computes on the host every batch (vit.py:167-168):
  * out3[0] = sklearn mean_absolute_error, out3[1] = compute_correlations (src/he2rna.py:140-149:
- * mean per-gene Pearson r over genes with a non-constant target, NaN r dropped), out3[2] = #genes used. */
+ * mean per-gene Pearson r over genes with a non-constant target, NaN r dropped), out3[2] = #genes used.
+ * With no gene used (batch == 1 in particular) out3[1] is NaN, as np.mean([]), and out3[2] is 0; out3[0] is still the MAE.
+ * scratch: sq_train_scratch_bytes(num_outputs) bytes.  batch < 1, num_outputs < 1 or a null pointer: SQ_ERR_ARG. */
 int sq_batch_metrics(const float* pred, const float* target, int batch, int num_outputs, float* out3, void* scratch,
                      sq_stream_t stream);
 
@@ -344,12 +359,19 @@ int sq_resnet50_extract_hw(int dtype, const void* weights, const float* bias, co
                            const float* patches_f32_nchw, int n_patches, int height, int width, float* features,
                            void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream);
 
-/* dst_bf16[i] = bf16(src[i]) -- refresh of the bf16 parameter shadow after an optimizer step */
+/* dst_bf16[i] = bf16(src[i]) -- refresh of the bf16 parameter shadow after an optimizer step.  Round to nearest, ties to even
+ * (torch's .to(torch.bfloat16) bit for bit: subnormals kept, finite values beyond the bf16 range become +-inf); a NaN stays a
+ * NaN, its payload and sign unspecified.
+ * Alignment: both casts take any naturally aligned pointers (src 4 bytes, dst 2 bytes here; the reverse below), so any element
+ * range of a flat buffer may be passed.  16-byte accesses are used when src is 16-byte and dst 8-byte aligned (below: both
+ * 16-byte aligned), an element-wise kernel otherwise; the results are the same bits.
+ * n == 0: nothing is launched, SQ_OK (the pointers must still be non-null).  src and dst must not overlap. */
 int sq_cast_f32_to_bf16(const float* src, void* dst_bf16, size_t n, sq_stream_t stream);
 /* dst[i] = fp32(src_bf16[i]) -- with the call above the pack / unpack of the bf16 gradient exchange (BASELINE config 4: "RCCL grad
  * all-reduce over xGMI, bf16"; the reference trains on one device, src/main.py:78, so there is no counterpart to cite): a gradient
  * bucket is cast to bf16, summed over the ranks in bf16 (half the ring traffic of the fp32 form), cast back into the fp32 flat
- * gradient that AdamW reads (train.py FusedTrainStep) */
+ * gradient that AdamW reads (train.py FusedTrainStep).  Exact: the bits of dst[i] are src_bf16[i] << 16, NaNs included.
+ * Alignment and n == 0 as for sq_cast_f32_to_bf16. */
 int sq_cast_bf16_to_f32(const void* src_bf16, float* dst, size_t n, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------

@@ -307,6 +307,12 @@ __global__ void f32_to_bf16_kernel(const float4* __restrict__ src, uint2* __rest
     if (gid < (size_t)tail) tail_dst[gid] = f32_to_bf16(tail_src[gid]);
 }
 
+// any naturally aligned pair of pointers (a bucket slice that does not start on a 16 / 8-byte boundary)
+__global__ void f32_to_bf16_scalar_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        dst[i] = f32_to_bf16(src[i]);
+}
+
 __global__ void bf16_to_f32_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         dst[i] = bf16_to_f32(src[i]);
@@ -515,6 +521,13 @@ int sq_k_gather_ln64_gelu(const float* f_tile, const float* f_pos, const int32_t
 }
 
 int sq_k_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t s) {
+    if (n == 0) return SQ_OK;
+    // the vector kernel loads float4 and stores uint2: src 16-byte, dst 8-byte aligned; otherwise element by element
+    if (((uintptr_t)src & 15) != 0 || ((uintptr_t)dst & 7) != 0) {
+        hipLaunchKernelGGL(f32_to_bf16_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, src, dst, n);
+        SQ_LAUNCH_CHECK();
+        return SQ_OK;
+    }
     const size_t n4 = n / 4;
     const int tail = (int)(n - n4 * 4);
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n4 ? n4 : 1, 256)), dim3(256), 0, s, (const float4*)src, (uint2*)dst,
