@@ -255,6 +255,10 @@ int sq_window_vote(const float* win_pred, int n_windows, int num_outputs, const 
  * Outputs (device): labels i32 [S, n]; cluster_features f32 [S, k, dim] (may be NULL);
  * seed_indices i32 [S, k] (may be NULL); n_iter i32 [S] (may be NULL).
  * Synchronises the stream between Lloyd bursts (the stop decision is read on the host).
+ * max_iter is any int and tol any double.  max_iter <= 0 runs no Lloyd iteration: n_iter = 0, the centres stay the seeded
+ * rows and labels are the one E-step against them (what scikit-learn's loop does when it is not entered); cluster_features
+ * follow those labels.  tol is relative (scikit-learn's tol): the loop stops once the squared centre shift of an iteration
+ * is <= tol * mean(var(X, axis=0)); tol = 0 leaves the label rule and max_iter.
  * The three entries below share one driver and one set of kernels: a call's slides lie back to back and a slide table
  * in the workspace says where each starts.  They differ in how that table is filled -- n_slides equal slides, one slide
  * of up to 65536 patches, or slides of different patch counts -- and in their bounds.  Common to all: n_clusters <= 256,
@@ -970,6 +974,13 @@ int sq_spot_scale(double* L, int n, int ld, int C, double* mean, double* sd, int
  *                      may be NULL.  A taps_floats below the total, or a shape sq_resnet50_extract_hw refuses, is an error
  *                      before anything is launched.  t2 and the downsample tensor are not tapped: on the fused routes they
  *                      never leave the CU.
+ *   sq_dbg_kmeans_lloyd : sq_kmeans_fit (same bounds, same centring and tolerance, same Lloyd loop, final E-step and cluster
+ *                      means) without the k-means++ seeding and the centre gather: the loop starts from init_centers f32
+ *                      [n_slides, n_clusters, dim] in CENTRED coordinates (X minus its fp32 column mean), so the tests can put
+ *                      centres where no data lies and reach the empty-cluster relocation.  final_centers f32 [n_slides,
+ *                      n_clusters, dim] (may be NULL) receives the centres of the last update, centred as well (max_iter = 0:
+ *                      init_centers).  large_lists != 0 builds the member lists with the counting sort of sq_kmeans_fit_large
+ *                      (n_slides must be 1) on the same slide.  Workspace: sq_kmeans_workspace_bytes.  Writes no seed indices.
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_RESNET50_TAPS 34
 int sq_dbg_set(int key, int value);
@@ -983,6 +994,9 @@ int sq_dbg_resnet50_taps(int dtype, const void* weights, const float* bias, cons
                          const float* patches_f32_nchw, int n_patches, int height, int width, float* features,
                          void* workspace, size_t workspace_bytes, uint32_t* nonfinite_flag, sq_stream_t stream,
                          float* taps, size_t taps_floats, int64_t* tap_offsets);
+int sq_dbg_kmeans_lloyd(const float* X, int n_slides, int n_samples, int dim, int n_clusters, const float* init_centers,
+                        int large_lists, int max_iter, double tol, int32_t* labels, float* cluster_features, float* final_centers,
+                        int32_t* n_iter, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
 #ifdef __cplusplus
 }

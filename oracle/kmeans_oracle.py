@@ -37,6 +37,15 @@ restatement fixes a deterministic definition that lies inside that variability:
 Labels differ from sklearn's only when one of those roundings crosses a
 comparison (measured rate in DESIGN.md).  The HIP kernels implement exactly the
 definitions above, so HIP == oracle is expected bit-for-bit on labels.
+
+Trace: ``kmeans_plusplus``, ``lloyd`` and ``kmeans_fit`` take an optional dict and
+fill it without changing any result.  ``trace["seeding"]``: per step the candidates,
+their potentials (the fp32 values, the fp64 sums behind them, and whether each sum is
+exact in any order), the chosen trial, ``u * pot`` and the cumulative sums just below
+and at each candidate.  ``trace["lloyd"]``: per iteration each point's smallest and second
+smallest ``|c|^2 - 2 x.c``, ``shift``, the cluster weights, the empty clusters, the
+distances relocation sorted and the relocated points; one more record (``final``) for
+the closing E-step.  ``trace["strict"]``, ``trace["tol"]``: the stop rule's inputs.
 """
 import numpy as np
 
@@ -83,8 +92,19 @@ def _pot(d32):
     return np.float32(np.sum(d32.astype(np.float64)))
 
 
-def kmeans_plusplus(Xc, n_clusters, first_id, u):
-    """_kmeans.py:174-272 on centred fp32 data; returns indices[k] into Xc."""
+def _sum_is_exact(d32):
+    """Trace only: True when the fp64 sum of the non-negative fp32 values d32 is exact in ANY order of summation -- every
+    term is a multiple of q = 2^(smallest exponent - 24) and the total stays below 2^53 q, so no partial sum ever rounds."""
+    nz = d32[d32 > 0].astype(np.float64)
+    if len(nz) == 0:
+        return True
+    q = 2.0 ** (int(np.frexp(nz)[1].min()) - 24)
+    return bool(np.sum(nz) / q < 2.0 ** 53)
+
+
+def kmeans_plusplus(Xc, n_clusters, first_id, u, trace=None):
+    """_kmeans.py:174-272 on centred fp32 data; returns indices[k] into Xc.
+    trace: a dict; gets trace["seeding"] = one record per step (see the module's "Trace" note); results are unchanged."""
     n = Xc.shape[0]
     X64 = Xc.astype(np.float64)
     norms64 = np.einsum("ij,ij->i", X64, X64)
@@ -101,23 +121,36 @@ def kmeans_plusplus(Xc, n_clusters, first_id, u):
         np.minimum(closest, dc, out=dc)
         pots = np.array([_pot(row) for row in dc], dtype=np.float32)
         best = int(np.argmin(pots))
+        if trace is not None:
+            if c == 1:
+                trace["first_potential_sum"] = float(np.sum(closest.astype(np.float64)))
+                trace["first_potential_exact"] = _sum_is_exact(closest)
+            trace.setdefault("seeding", []).append(dict(
+                step=c, candidates=cand.copy(), potentials=pots.copy(), chosen=best, pot=float(pot), rand_vals=rand_vals.copy(),
+                potential_sums=np.array([np.sum(row.astype(np.float64)) for row in dc]),      # the fp64 sums behind `potentials`
+                potential_exact=np.array([_sum_is_exact(row) for row in dc]),
+                cum_below=np.where(cand > 0, cum[np.maximum(cand - 1, 0)], 0.0), cum_at=cum[cand].copy()))
         pot = pots[best]
         closest = dc[best]
         indices[c] = cand[best]
     return indices
 
 
-def _assign(X64, centers32):
+def _assign(X64, centers32, rec=None):
     """_k_means_lloyd.pyx:196-214: argmin_j (|c_j|^2 - 2 x.c_j), strict '<' so
-    the first minimum wins."""
+    the first minimum wins.  rec: a dict that gets every point's smallest and second smallest value."""
     C64 = centers32.astype(np.float64)
     cn = np.einsum("ij,ij->i", C64, C64)
     pd = cn[None, :] - 2.0 * (X64 @ C64.T)
+    if rec is not None:
+        two = np.partition(pd, 1, axis=1)[:, :2] if pd.shape[1] > 1 else np.concatenate([pd, np.full_like(pd, np.inf)], axis=1)
+        rec.update(best=two[:, 0].copy(), runner_up=two[:, 1].copy(), center_norms=cn)
     return np.argmin(pd, axis=1).astype(np.int32)
 
 
-def lloyd(Xc, centers_init, tol, max_iter=300):
-    """_kmeans.py:624-760 (_kmeans_single_lloyd) + lloyd_iter_chunked_dense."""
+def lloyd(Xc, centers_init, tol, max_iter=300, trace=None):
+    """_kmeans.py:624-760 (_kmeans_single_lloyd) + lloyd_iter_chunked_dense.
+    trace: a dict; gets trace["lloyd"] = one record per iteration and one for the final E-step; results are unchanged."""
     n, k = Xc.shape[0], centers_init.shape[0]
     X64 = Xc.astype(np.float64)
     centers = centers_init.astype(np.float32).copy()
@@ -126,7 +159,13 @@ def lloyd(Xc, centers_init, tol, max_iter=300):
     n_iter = 0
     for it in range(max_iter):
         n_iter = it + 1
-        labels = _assign(X64, centers)
+        rec = None
+        if trace is not None:
+            rec = dict(iteration=n_iter, final=False, empty=np.zeros(0, np.int64), relocated=np.zeros(0, np.int64))
+            trace.setdefault("lloyd", []).append(rec)
+        labels = _assign(X64, centers, rec)
+        if rec is not None:
+            rec["labels"] = labels.copy()
         sums = np.zeros((k, Xc.shape[1]), dtype=np.float64)
         np.add.at(sums, labels, X64)
         weight = np.bincount(labels, minlength=k).astype(np.float64)
@@ -134,8 +173,12 @@ def lloyd(Xc, centers_init, tol, max_iter=300):
         empty = np.where(weight == 0)[0]
         if len(empty) > 0:
             dist = ((Xc - centers[labels]) ** 2).sum(axis=1, dtype=np.float64)
+            if rec is not None:
+                rec.update(empty=empty.copy(), distances=dist.copy())
             if dist.max() > 0:
                 far = np.lexsort((np.arange(n), -dist))[:len(empty)]   # descending, ties by index
+                if rec is not None:
+                    rec["relocated"] = far.copy()
                 for new_id, far_idx in zip(empty, far):
                     old_id = labels[far_idx]
                     sums[old_id] -= X64[far_idx]
@@ -153,14 +196,22 @@ def lloyd(Xc, centers_init, tol, max_iter=300):
                 new[j] = new[amax]
         shift_tot = float(((new.astype(np.float64) - centers.astype(np.float64)) ** 2).sum())
         centers = new
+        if rec is not None:
+            rec.update(shift=shift_tot, weights=weight.copy(), heaviest=amax)
         if np.array_equal(labels, labels_old):
             strict = True
             break
         if shift_tot <= tol:
             break
         labels_old = labels
+    if trace is not None:
+        trace["strict"] = strict
     if not strict:
-        labels = _assign(X64, centers)
+        rec = None
+        if trace is not None:
+            rec = dict(iteration=n_iter, final=True)
+            trace.setdefault("lloyd", []).append(rec)
+        labels = _assign(X64, centers, rec)
     return labels, centers, n_iter
 
 
@@ -169,14 +220,16 @@ def tolerance(X, tol=1e-4):
     return float(np.mean(np.var(X.astype(np.float64), axis=0)) * tol)
 
 
-def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4):
-    """KMeans(n_clusters, random_state=0).fit(X) -> dict(labels, indices, n_iter, centers)."""
+def kmeans_fit(X, n_clusters=100, random_state=0, max_iter=300, tol=1e-4, trace=None):
+    """KMeans(n_clusters, random_state=0).fit(X) -> dict(labels, indices, n_iter, centers).  trace: see kmeans_plusplus / lloyd."""
     X = np.ascontiguousarray(X, dtype=np.float32)
     tol_ = tolerance(X, tol)
     first, u = seeding_draws(X.shape[0], n_clusters, random_state)
     Xc, mean = center_data(X)
-    idx = kmeans_plusplus(Xc, n_clusters, first, u)
-    labels, centers, n_iter = lloyd(Xc, Xc[idx], tol_, max_iter)
+    idx = kmeans_plusplus(Xc, n_clusters, first, u, trace)
+    labels, centers, n_iter = lloyd(Xc, Xc[idx], tol_, max_iter, trace)
+    if trace is not None:
+        trace["tol"] = tol_
     return dict(labels=labels, indices=idx, n_iter=n_iter, centers=centers + mean)
 
 

@@ -670,7 +670,9 @@ __global__ __launch_bounds__(KM_THREADS) void km_relocate_kernel(const float* __
             int bi = -1; double bd = -1.0;
             for (int j = 0; j < n; ++j)
                 if (dist[j] > bd) { bd = dist[j]; bi = j; }
-            far_idx = bd > 0.0 ? bi : -1;
+            // np.max(distances) == 0 is asked ONCE, of the farthest point of all: with fewer points off their centres than
+            // empty clusters the remaining clusters still take points at distance 0, lowest index first
+            far_idx = (e > 0 || bd > 0.0) ? bi : -1;
             if (bi >= 0) dist[bi] = -2.0;
         }
         __syncthreads();
@@ -1173,7 +1175,7 @@ void km_carve(int S, const KmExtents& e, int D, int k, char* base, KmBufs* o, Km
 // grids: blocks beyond their own slide's rows return at once.  lg == nullptr: member lists by km_members_kernel
 // (n <= 4096, any S); otherwise by the three-launch counting sort (any n, S == 1).
 int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter, int32_t* labels, float* cluster_features,
-                       int32_t* n_iter, const KmBufs& b, const KmLgBufs* lg, hipStream_t st) {
+                       int32_t* n_iter, float* final_centers, const KmBufs& b, const KmLgBufs* lg, hipStream_t st) {
     const KmSlide* tab = b.tab;
     auto members = [&](int force) -> int {
         if (!lg) {
@@ -1241,6 +1243,8 @@ int km_lloyd_and_means(const float* X, int S, int n, int D, int k, int max_iter,
         SQ_LAUNCH_CHECK();
         if (int e = members(1)) return e;
     }
+    // the centres of the last update, centred coordinates (slides that stopped earlier were copied through every update)
+    if (final_centers) SQ_HIP_CHECK(hipMemcpyAsync(final_centers, cur, (size_t)S * k * D * 4, hipMemcpyDeviceToDevice, st));
     if (cluster_features) {
         hipLaunchKernelGGL(km_cluster_means_kernel, dim3(k, S), dim3(256), 0, st, X, b.members, b.offsets, cluster_features, tab, D, k);
         SQ_LAUNCH_CHECK();
@@ -1324,12 +1328,22 @@ int km_seed_large(const KmBufs& b, const KmLgBufs& lg, int n, int D, int k, int 
     return SQ_OK;
 }
 
+// What sq_dbg_kmeans_lloyd puts in the place of the seeding: the centres the Lloyd loop starts from, where its last
+// centres go, and which member lists it builds.
+struct KmInject {
+    const float* init_centers;        // f32 [S, k, D], centred coordinates
+    float* final_centers;             // f32 [S, k, D] or nullptr
+    bool large_lists;                 // the counting sort of section 5 (one slide) in place of km_members_kernel
+};
+
 // One fit: check, table, centring and tolerance, seeding (large: section 5 on the one slide, otherwise from the Gram
-// matrices), then seeds -> centres and the Lloyd loop.
+// matrices), then seeds -> centres and the Lloyd loop.  inj != nullptr: no seeding and no gather, the centres are given.
 int km_fit(const char* who, int s_max, int n_hi, bool large, const float* X, const KmCounts& c, int D, int k, const double* uniforms,
            int trials, int max_iter, double tol, int32_t* labels, float* cluster_features, int32_t* seed_indices, int32_t* n_iter,
-           void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int e = km_check(who, c, s_max, n_hi, D, k, false, trials, X && labels && uniforms && workspace)) return e;
+           void* workspace, size_t workspace_bytes, hipStream_t st, const KmInject* inj = nullptr) {
+    if (int e = km_check(who, c, s_max, n_hi, D, k, false, trials, X && labels && (inj ? inj->init_centers != nullptr : uniforms != nullptr) && workspace))
+        return e;
+    if (inj && inj->large_lists) SQ_REQUIRE(c.S == 1, "%s: n_slides=%d, the large route's member lists take one slide", who, c.S);
     const int S = c.S;
     const bool lists = c.stride != 0;          // otherwise S equal slides: their table is filled on the device
     // The host block of a table made from lists must outlive its copy: the Lloyd loop synchronises the stream at its
@@ -1356,13 +1370,26 @@ int km_fit(const char* who, int s_max, int n_hi, bool large, const float* X, con
     SQ_LAUNCH_CHECK();
     hipLaunchKernelGGL(km_tol_kernel, dim3(S), dim3(256), 0, st, b.colvar, b.st, D, tol);
     SQ_LAUNCH_CHECK();
-    if (int rc = large ? km_seed_large(b, lg, e.n_max, D, k, c.first(0), uniforms, trials, st) : km_seed_gram(b, e, S, D, k, uniforms, trials, st))
-        return rc;
-    if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)S * k * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(km_gather_centers_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.seeds, b.centers, b.tab, D, k);
-    SQ_LAUNCH_CHECK();
+    const KmLgBufs* member_lists = large ? &lg : nullptr;
+    if (inj) {
+        SQ_HIP_CHECK(hipMemcpyAsync(b.centers, inj->init_centers, (size_t)S * k * D * 4, hipMemcpyDeviceToDevice, st));
+        if (inj->large_lists) {
+            // Only the per-chunk histograms of section 5 are needed, and the Gram matrix is not: they lie in its place.
+            // ((nchunks - 1) * 256 + k) ints against n^2 doubles: k <= n covers one chunk, n > 1024 any number of them.
+            lg = KmLgBufs{};
+            lg.hist = (int*)b.G;
+            member_lists = &lg;
+        }
+    } else {
+        if (int rc = large ? km_seed_large(b, lg, e.n_max, D, k, c.first(0), uniforms, trials, st) : km_seed_gram(b, e, S, D, k, uniforms, trials, st))
+            return rc;
+        if (seed_indices) SQ_HIP_CHECK(hipMemcpyAsync(seed_indices, b.seeds, (size_t)S * k * 4, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(km_gather_centers_kernel, dim3(k, S), dim3(256), 0, st, b.Xc, b.seeds, b.centers, b.tab, D, k);
+        SQ_LAUNCH_CHECK();
+    }
     SQ_HIP_CHECK(hipMemsetAsync(b.labels_old, 0xff, e.rows * 4, st));          // labels_old = -1
-    const int rc = km_lloyd_and_means(X, S, e.n_max, D, k, max_iter, labels, cluster_features, n_iter, b, large ? &lg : nullptr, st);
+    const int rc = km_lloyd_and_means(X, S, e.n_max, D, k, max_iter, labels, cluster_features, n_iter, inj ? inj->final_centers : nullptr, b,
+                                      member_lists, st);
     wait.armed = lists && (rc != SQ_OK || max_iter < 1);          // no poll ran
     return rc;
 }
@@ -1415,4 +1442,14 @@ extern "C" int sq_kmeans_fit_ragged(const float* X, int S, const int32_t* n_samp
     return km_fit("kmeans (ragged)", KM_RAGGED_MAX_SLIDES, KM_GRAM_MAX_N, false, X, KmCounts{S, n_samples, first_centers, 1}, D, k, uniforms,
                   n_local_trials, max_iter, tol, labels, cluster_features, seed_indices, n_iter, workspace, workspace_bytes,
                   (hipStream_t)stream);
+}
+
+// Test hook: sq_kmeans_fit with the seeding and the centre gather replaced by given centres (see the header).
+extern "C" int sq_dbg_kmeans_lloyd(const float* X, int S, int n, int D, int k, const float* init_centers, int large_lists, int max_iter,
+                                   double tol, int32_t* labels, float* cluster_features, float* final_centers, int32_t* n_iter,
+                                   void* workspace, size_t workspace_bytes, sq_stream_t stream) {
+    const int first_center = 0;
+    const KmInject inj{init_centers, final_centers, large_lists != 0};
+    return km_fit("kmeans (dbg lloyd)", 0, KM_GRAM_MAX_N, false, X, KmCounts{S, &n, &first_center, 0}, D, k, nullptr, 1, max_iter, tol, labels,
+                  cluster_features, nullptr, n_iter, workspace, workspace_bytes, (hipStream_t)stream, &inj);
 }

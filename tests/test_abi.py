@@ -36,7 +36,8 @@ def test_every_declared_function_is_bound_with_its_arity_and_return_kind():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     decls = re.findall(r"([\w \*]+?)\s*\b(sq_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src)
     assert sorted(d[1] for d in decls) == declared_symbols() == sorted(_abi.FUNCTIONS)
-    assert {"sq_dbg_set", "sq_dbg_chain_x3", "sq_dbg_chain_x3w", "sq_dbg_uni_attn", "sq_dbg_resnet50_taps"} <= set(_abi.FUNCTIONS)
+    assert {"sq_dbg_set", "sq_dbg_chain_x3", "sq_dbg_chain_x3w", "sq_dbg_uni_attn", "sq_dbg_resnet50_taps",
+            "sq_dbg_kmeans_lloyd"} <= set(_abi.FUNCTIONS)
     for ret, name, args in decls:
         fn = getattr(lib, name)
         kind = ctypes.c_char_p if "char" in ret else ctypes.c_size_t if "size_t" in ret else ctypes.c_int
