@@ -1,4 +1,4 @@
-"""HE2RNA -- the benchmark comparator of the reference (``/root/reference/src/he2rna.py:42-106``, built by
+"""HE2RNA -- the benchmark comparator of the reference (``src/he2rna.py:42-106``, built by
 ``src/pretrain_gtex.py:102-105`` as ``HE2RNA(input_dim, layers=[256, 256], ks=[1, 2, 5, 10, 20, 50, 100], output_dim)``)
 on the HIP engine: same constructor, ``state_dict`` keys (``conv{i}.weight [out, in, 1]``, ``conv{i}.bias``),
 ``forward`` / ``forward_fixed_k`` / ``conv`` semantics and HuggingFace mixin, plus the loops ``training_epoch``,
@@ -10,20 +10,22 @@ top-k over the tiles and the position-weighted mean of he2rna.py:93-99 -- for al
 launch -- are ``sq_he2rna_tile_mask`` / ``sq_he2rna_topk_mean``; the backward pass is ``sq_he2rna_topk_mean_bwd``,
 ``sq_linear`` on transposed weights and ``sq_linear_weight_grad``.  Dropout masks are drawn with torch's device RNG
 (no stream of the reference's CPU generator can be reproduced on another device anyway); everything else is C calls.
-There is no CPU fallback: tensors must live on the MI355X.
+There is no CPU fallback: tensors must live on the MI355X.  The parameters are one flat fp32 buffer (``_flat.FlatParams``) in
+the padded layout of ``sq_he2rna_param_layout``; every path here reads and writes it in place.
 
-``fit(engine="fused")`` trains on ``He2rnaTrainStep`` instead: parameters, gradient and Adam moments in one flat padded
-buffer, a step = ``sq_he2rna_train_forward`` + ``sq_he2rna_train_backward`` + ``sq_adamw_step`` (csrc/he2rna_train.hip:
+``fit(engine="fused")`` trains on ``He2rnaTrainStep`` instead: that buffer, a gradient and Adam moments in its layout, a step = ``sq_he2rna_train_forward`` + ``sq_he2rna_train_backward`` + ``sq_adamw_step`` (csrc/he2rna_train.hip:
 counter-based dropout without stored masks, one loss-head launch that ranks every column once), the validation score
 from one ``sq_batch_metrics`` call.  ``fit``'s default engine, ``forward`` and the loops above are unchanged."""
 import os
 import time
+from collections import OrderedDict
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
+from ._flat import FlatParams
 
 try:
     from huggingface_hub import PyTorchModelHubMixin
@@ -36,93 +38,90 @@ def _up(n, m):
     return (n + m - 1) // m * m
 
 
-def _layer_stack(xt, input_dim, params, ws, p_drop=0.0, dst=None):
-    """The stack of 1x1 convolutions (he2rna.py:101-106) on token-major rows xt f32 [M, C], of which the last `input_dim`
-    channels go in (:102): ``sq_linear`` per layer, bias and ReLU fused on all layers but the last, dropout behind every hidden
-    layer when p_drop > 0 (one torch.rand [M, ld] per hidden layer, in layer order).  Every activation / weight is zero-padded to
-    a multiple of 8 columns: the GEMM engine wants 16-byte rows, and the reference's default layers=[1] has a hidden width of
-    ONE.  `dst`: where the last layer writes (f32 [M, ld >= G] rows, e.g. a slice of a score table) instead of a new tensor.
-    Returns (acts -- the padded input and every layer's output --, padded weights, dropout masks or None per layer): what the
-    backward pass needs; acts[-1][:, :G] are the scores."""
-    lib = _lib.lib()
-    dev = xt.device
-    M, C = xt.shape
-    n_layers = len(params) // 2
-    with torch.cuda.device(dev):                       # the library keys per-device state on the current device
+def param_layout(dims):
+    """sq_he2rna_param_layout for ``dims = [input_dim, *layers, output_dim]``: (weight offsets, bias offsets, total), in floats.
+    Layer i's weight is ``[dims[i + 1], round_up(dims[i], 8)]`` row-major; every tensor starts on a 16-byte boundary."""
+    d, n = np.asarray(dims, dtype=np.int32), len(dims) - 1
+    w, b, total = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64), np.zeros(1, dtype=np.int64)
+    _lib.check(_lib.lib().sq_he2rna_param_layout(d.ctypes.data, n, w.ctypes.data, b.ctypes.data, total.ctypes.data))
+    return [int(v) for v in w], [int(v) for v in b], int(total[0])
+
+
+def _layer_stack(xt, m, p_drop=0.0, dst=None):
+    """The stack of 1x1 convolutions (he2rna.py:101-106) of model `m` on token-major rows xt f32 [M, C], of which the last
+    ``m.input_dim`` channels go in (:102): ``sq_linear`` per layer on the weight and bias slices of ``m.flat``, bias and ReLU fused on
+    all layers but the last, dropout behind every hidden layer when p_drop > 0 (one torch.rand [M, ld] per hidden layer, in layer
+    order).  Activations are zero-padded to a multiple of 8 columns, as the weight rows of ``flat`` are: the GEMM engine wants 16-byte
+    rows, and the reference's default layers=[1] has a hidden width of ONE.  `dst`: where the last layer writes (f32 [M, ld >= G]
+    rows, e.g. a slice of a score table) instead of a new tensor.  Returns (acts -- the padded input and every layer's output --,
+    dropout masks or None per layer): what the backward pass needs; acts[-1][:, :G] are the scores."""
+    lib, dev, flat = _lib.lib(), xt.device, m.flat.detach()
+    if not xt.is_cuda or flat.device != dev:
+        raise _lib.SequoiaHipError(f"HE2RNA: parameters on {flat.device}, input on {dev}: both must be on the same GPU (no CPU fallback)")
+    (M, C), ws = xt.shape, m._workspace(dev)
+    with torch.cuda.device(dev):                      # the library keys per-device state on the current device
         st = _lib.stream_ptr(dev)
-        a = torch.zeros(M, _up(input_dim, 8), dtype=torch.float32, device=dev)
-        a[:, :input_dim] = xt[:, C - input_dim:]
-        acts, wpads, drops = [a], [], []
-        for i in range(n_layers):
-            w, b = params[2 * i], params[2 * i + 1]
-            n_out, k_in = w.shape[0], w.shape[1]
-            wp = torch.zeros(n_out, acts[-1].shape[1], dtype=torch.float32, device=dev)
-            wp[:, :k_in] = w.detach().view(n_out, k_in)
-            last = i + 1 == n_layers
+        a = torch.zeros(M, _up(m.input_dim, 8), dtype=torch.float32, device=dev)
+        a[:, :m.input_dim] = xt[:, C - m.input_dim:]
+        acts, drops = [a], []
+        for i in range(m.n_layers):
+            n_out, k_pad = int(m.dims[i + 1]), acts[-1].shape[1]
+            last = i + 1 == m.n_layers
             out = dst if last and dst is not None else torch.zeros(M, _up(n_out, 8), dtype=torch.float32, device=dev)
-            bias = b.detach().float().contiguous()
-            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias),
-                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], M, n_out, wp.shape[1],
+            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(acts[-1]), k_pad, _lib.ptr(flat[m.w_off[i]:]), k_pad, _lib.ptr(flat[m.b_off[i]:]),
+                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], M, n_out, k_pad,
                                      _lib.ptr(ws), ws.numel(), st))
             dm = None
             if not last and p_drop > 0.0:
                 dm = (torch.rand(M, out.shape[1], device=dev) >= p_drop).to(torch.float32) / (1.0 - p_drop)
                 out.mul_(dm)
-            wpads.append(wp)
             drops.append(dm)
             acts.append(out)
-    return acts, wpads, drops
+    return acts, drops
 
 
 class _He2rnaFn(torch.autograd.Function):
-    """x [B, C, N] f32 -> [B, G]: forward_fixed_k for one k (scale 1) or the eval mean over ks (scale 1 / len(ks))."""
+    """x [B, C, N] f32 -> [B, G]: forward_fixed_k for one k (scale 1) or the eval mean over ks (scale 1 / len(ks)).  The gradient
+    w.r.t. the parameters is ONE tensor in the layout of ``flat``, zeroed on every backward (so its padding is exactly 0), into
+    whose slices sq_linear_weight_grad writes dW and db."""
 
     @staticmethod
-    def forward(ctx, x, ks, scale, p_drop, input_dim, ws, *params):
-        lib = _lib.lib()
-        dev = x.device
-        B, C, N = x.shape
+    def forward(ctx, flat, x, m, ks, scale, p_drop):
+        lib, dev, (B, C, N) = _lib.lib(), x.device, x.shape
         M = B * N
         xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(M, C)        # free when x came from 'b c f -> b f c'
-        G = params[-2].shape[0]
         ks_arr = np.asarray(ks, dtype=np.int32)
         mask = torch.empty(M, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
             _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(xt), M, C, _lib.ptr(mask), st))
-            acts, wpads, drops = _layer_stack(xt, input_dim, params, ws, p_drop)
-            pred = torch.empty(B, G, dtype=torch.float32, device=dev)
+            acts, drops = _layer_stack(xt, m, p_drop)
+            pred = torch.empty(B, m.output_dim, dtype=torch.float32, device=dev)
             _lib.check(lib.sq_he2rna_topk_mean(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), float(scale),
-                                               _lib.ptr(pred), B, N, G, st))
-        ctx.saved = (acts, wpads, drops, mask, ks_arr, float(scale), (B, C, N, input_dim), ws, [w.shape[1] for w in params[0::2]])
+                                               _lib.ptr(pred), B, N, m.output_dim, st))
+        ctx.save_for_backward(flat)                    # autograd refuses the backward pass if the buffer was written in between
+        ctx.saved = (acts, drops, mask, ks_arr, float(scale), (B, C, N), (m.dims, m.w_off, m.b_off), m._workspace(dev))
         return pred
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.lib()
-        acts, wpads, drops, mask, ks_arr, scale, (B, C, N, input_dim), ws, kins = ctx.saved
-        dev = gout.device
-        M = B * N
+        lib, dev, (flat,) = _lib.lib(), gout.device, ctx.saved_tensors
+        acts, drops, mask, ks_arr, scale, (B, C, N), (dims, w_off, b_off), ws = ctx.saved
+        M, input_dim, G = B * N, int(dims[0]), int(dims[-1])
+        gflat = torch.zeros_like(flat)
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
-            n_layers = len(wpads)
-            G = wpads[-1].shape[0]
             dy = torch.zeros_like(acts[-1])
             _lib.check(lib.sq_he2rna_topk_mean_bwd(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), scale,
                                                    _lib.ptr(gout.detach().float().contiguous()), _lib.ptr(dy), dy.shape[1], B, N, G, st))
-            grads = [None] * (2 * n_layers)
-            for i in range(n_layers - 1, -1, -1):
-                wp, a_in = wpads[i], acts[i]
-                n_out, k_pad = wp.shape
-                dw = torch.empty(n_out, k_pad, dtype=torch.float32, device=dev)
-                db = torch.empty(n_out, dtype=torch.float32, device=dev)
-                _lib.check(lib.sq_linear_weight_grad(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(a_in), k_pad, _lib.ptr(dw), k_pad, _lib.ptr(db),
-                                                     n_out, k_pad, M, _lib.ptr(ws), ws.numel(), st))
-                grads[2 * i] = dw[:, :kins[i]].unsqueeze(-1)
-                grads[2 * i + 1] = db
-                if i > 0 or ctx.needs_input_grad[0]:
+            for i in range(len(w_off) - 1, -1, -1):
+                a_in, n_out = acts[i], int(dims[i + 1])
+                k_pad = a_in.shape[1]
+                _lib.check(lib.sq_linear_weight_grad(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(a_in), k_pad, _lib.ptr(gflat[w_off[i]:]), k_pad,
+                                                     _lib.ptr(gflat[b_off[i]:]), n_out, k_pad, M, _lib.ptr(ws), ws.numel(), st))
+                if i > 0 or ctx.needs_input_grad[1]:
                     wt = torch.zeros(k_pad, dy.shape[1], dtype=torch.float32, device=dev)      # W^T, contraction over the padded outputs
-                    wt[:, :n_out] = wp.t()
+                    wt[:, :n_out] = flat[w_off[i]:w_off[i] + n_out * k_pad].view(n_out, k_pad).t()
                     dx = torch.empty(M, k_pad, dtype=torch.float32, device=dev)
                     _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(wt), wt.shape[1], None, None, 0, _lib.SQ_F32, 0,
                                              _lib.ptr(dx), _lib.SQ_F32, k_pad, M, k_pad, dy.shape[1], _lib.ptr(ws), ws.numel(), st))
@@ -132,40 +131,66 @@ class _He2rnaFn(torch.autograd.Function):
                             dx.mul_(drops[i - 1])
                     dy = dx
             gx = None
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[1]:
                 gx = torch.zeros(B, N, C, dtype=torch.float32, device=dev)
                 gx[:, :, C - input_dim:] = dy[:, :input_dim].view(B, N, input_dim)
                 gx = gx.transpose(1, 2)
-        return (gx, None, None, None, None, None) + tuple(grads)
+        return gflat, gx, None, None, None, None
 
 
-class HE2RNA(nn.Module, PyTorchModelHubMixin):
-    """he2rna.py:42-106.  ``nonlin`` other than ReLU is not supported on the device path (the reference never passes one)."""
+class _ScoresFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flat, x, m, p_drop):
+        B, C, N = x.shape
+        xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(B * N, C)
+        acts, _ = _layer_stack(xt, m, p_drop)
+        return acts[-1][:, :m.output_dim].reshape(B, N, m.output_dim).transpose(1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError("HE2RNA.conv is an inspection helper; train through forward / forward_fixed_k")
+
+
+class HE2RNA(nn.Module, FlatParams, PyTorchModelHubMixin):
+    """he2rna.py:42-106.  ``nonlin`` other than ReLU is not supported on the device path (the reference never passes one).
+
+    The parameters are ONE fp32 buffer ``flat`` in the layout of ``param_layout`` (zero-padded weight rows), which the layer stack, the
+    autograd function and He2rnaTrainStep read and write in place.  What differs from the reference class: ``parameters()`` yields
+    the single ``flat`` -- the reference's names and shapes are those of ``state_dict()`` (copies), ``named_reference_tensors()``
+    (views) and ``grad_views(flat.grad)`` --; there are no ``conv{i}`` attributes (a whole-module pickle that has them still loads);
+    more than SQ_HE2RNA_MAX_LAYERS (8) layers are refused at construction, with the library's message; and constructing one needs
+    the built library, also on the CPU (the layout is the library's)."""
 
     def __init__(self, input_dim, output_dim, layers=[1], nonlin=None, ks=[10], dropout=0.5, device="cpu", bias_init=None, **kwargs):
         super().__init__()
         if nonlin is not None and not isinstance(nonlin, nn.ReLU):
             raise NotImplementedError("HE2RNA on the HIP engine fuses ReLU into the layer launches; other activations are not implemented")
-        self.input_dim = input_dim
-        self.output_dim = output_dim
+        self.input_dim, self.output_dim = input_dim, output_dim
         dims = [input_dim] + list(layers) + [output_dim]
-        self.n_layers = len(dims) - 1
-        for i in range(self.n_layers):                      # parameter containers with the reference's names and shapes
-            setattr(self, "conv" + str(i), nn.Conv1d(dims[i], dims[i + 1], kernel_size=1, stride=1, bias=True))
+        # the reference's containers, drawn in its order (the same RNG stream, the same initial values), then packed and dropped
+        convs = [nn.Conv1d(dims[i], dims[i + 1], kernel_size=1, stride=1, bias=True) for i in range(len(dims) - 1)]
+        pairs = [(c.weight, c.bias) for c in convs]
         if bias_init is not None:
-            getattr(self, "conv" + str(self.n_layers - 1)).bias = bias_init
-        self.ks = np.array(ks)
-        self.p_drop = float(dropout)
-        self.device = device
+            pairs[-1] = (pairs[-1][0], torch.as_tensor(bias_init))
+        self._install_flat(self._pack(pairs))
+        self.ks, self.p_drop, self.device, self._ws = np.array(ks), float(dropout), device, None
         self.to(device)
-        self._ws = None
 
-    def _params(self):
-        out = []
+    def _pack(self, pairs):
+        """(weight [n_out, n_in, 1], bias [n_out]) per layer -> sets the layout of those widths and returns a buffer in it that holds
+        the tensors (padding zero), on the first weight's device."""
+        dims = [pairs[0][0].shape[1]] + [w.shape[0] for w, _ in pairs]
+        self.dims, self.n_layers = np.asarray(dims, dtype=np.int32), len(pairs)
+        self.w_off, self.b_off, total = param_layout(dims)
+        self._tmap, self._pitch = OrderedDict(), {}
         for i in range(self.n_layers):
-            c = getattr(self, "conv" + str(i))
-            out += [c.weight, c.bias]
-        return out
+            self._tmap[f"conv{i}.weight"] = (self.w_off[i], (dims[i + 1], dims[i], 1))
+            self._tmap[f"conv{i}.bias"] = (self.b_off[i], (dims[i + 1],))
+            self._pitch[f"conv{i}.weight"] = _up(dims[i], 8)
+        flat = torch.zeros(total, dtype=torch.float32, device=pairs[0][0].device)
+        for (_, view), t in zip(self._slices(flat), (t for pair in pairs for t in pair)):
+            view.copy_(t.detach().reshape(view.shape))
+        return flat
 
     def _workspace(self, dev):
         if self._ws is None or self._ws.device != dev:
@@ -174,9 +199,14 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
 
     def __getstate__(self):
         """``torch.save(model)`` (he2rna.py:261 pickles the whole module): the 64 MiB device workspace is scratch, not state."""
-        state = self.__dict__.copy()
-        state["_ws"] = None
-        return state
+        return dict(self.__dict__, _ws=None)
+
+    def __setstate__(self, state):
+        """A whole-module pickle written before the parameters moved into ``flat`` holds ``conv{i}`` submodules: they are packed."""
+        super().__setstate__(state)
+        if "flat" not in self._parameters:
+            convs = [self._modules.pop("conv" + str(i)) for i in range(self.n_layers)]
+            self._install_flat(self._pack([(c.weight, c.bias) for c in convs]))
 
     def _run(self, x, ks, scale, training):
         _lib.require_gpu()
@@ -184,8 +214,7 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
             raise _lib.SequoiaHipError("HE2RNA needs CUDA tensors (no CPU fallback)")
         if x.dim() != 3 or x.shape[1] < self.input_dim:
             raise ValueError(f"HE2RNA: x must be [batch, channels >= {self.input_dim}, tiles], got {tuple(x.shape)}")
-        return _He2rnaFn.apply(x, tuple(int(k) for k in ks), scale, self.p_drop if training else 0.0, self.input_dim,
-                               self._workspace(x.device), *self._params())
+        return _He2rnaFn.apply(self.flat, x, self, tuple(int(k) for k in ks), scale, self.p_drop if training else 0.0)
 
     def forward(self, x):
         if self.training:
@@ -208,31 +237,24 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
         _lib.require_gpu()
         if not cache.is_cuda or cache.dim() != 2 or cache.shape[1] < self.input_dim:
             raise ValueError(f"HE2RNA.tile_scores: expected a device cache [n_tiles, channels >= {self.input_dim}], got {tuple(cache.shape)}")
-        lib = _lib.lib()
-        dev = cache.device
-        st = _lib.stream_ptr(dev)
-        x = cache.to(torch.float32).contiguous()
+        dev, x = cache.device, cache.to(torch.float32).contiguous()
         n, C = x.shape
         mask = torch.empty(n, dtype=torch.float32, device=dev)
-        G = self.output_dim
-        ld = _up(G, 8)
-        scores = torch.empty(n, ld, dtype=torch.float32, device=dev)
+        scores = torch.empty(n, _up(self.output_dim, 8), dtype=torch.float32, device=dev)
         if n == 0:
             return scores, mask
-        ws, params = self._workspace(dev), self._params()
         with torch.cuda.device(dev):
-            _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(x), n, C, _lib.ptr(mask), st))
+            _lib.check(_lib.lib().sq_he2rna_tile_mask(_lib.ptr(x), n, C, _lib.ptr(mask), _lib.stream_ptr(dev)))
         for r0 in range(0, n, self.TILE_ROWS):
             r1 = min(n, r0 + self.TILE_ROWS)
-            _layer_stack(x[r0:r1], self.input_dim, params, ws, dst=scores[r0:r1])
+            _layer_stack(x[r0:r1], self, dst=scores[r0:r1])
         return scores, mask
 
     def window_predictions(self, scores, mask, members):
         """Eval-mode predictions (the mean over ``ks``, he2rna.py:88-91) of windows whose tile n is row members[w, n] of a
         ``tile_scores`` table (int32 [W, N], -1 = zero padding): sq_he2rna_window_topk_mean.  Returns f32 [W, G]."""
         _lib.require_gpu()
-        W, N = members.shape
-        G = self.output_dim
+        (W, N), G = members.shape, self.output_dim
         if members.dtype != torch.int32 or not members.is_contiguous() or scores.shape[1] < G or mask.shape[0] != scores.shape[0]:
             raise ValueError("window_predictions: members must be contiguous int32 [W, N] and scores / mask a tile_scores table")
         ks = np.asarray(self.ks, dtype=np.int32)
@@ -247,104 +269,69 @@ class HE2RNA(nn.Module, PyTorchModelHubMixin):
 
     def conv(self, x):
         """Per-tile scores [B, G, N] (he2rna.py:101-106); the fused forward never materialises this layout."""
-        eye = _ScoresFn.apply(x, self.p_drop if self.training else 0.0, self.input_dim, self._workspace(x.device), *self._params())
-        return eye
+        return _ScoresFn.apply(self.flat, x, self, self.p_drop if self.training else 0.0)
 
     def replace_head(self, n_genes):
         """The ``--change_num_genes`` step of the k-fold experiment (he2rna.py:403-409): a fresh ``Conv1d(layers[-1], n_genes, 1)``
-        becomes the last layer, for fine-tuning a model that was trained on another gene list."""
-        last = getattr(self, "conv" + str(self.n_layers - 1))
-        head = nn.Conv1d(last.in_channels, int(n_genes), kernel_size=1, stride=1, bias=True).to(last.weight.device)
-        setattr(self, "conv" + str(self.n_layers - 1), head)
+        becomes the last layer, for fine-tuning a model that was trained on another gene list.  ``flat`` is rebuilt in the new
+        layout; every layer in front of the head keeps its bits."""
+        body = [t for _, t in self.named_reference_tensors()][:-2]
+        head = nn.Conv1d(int(self.dims[-2]), int(n_genes), kernel_size=1, stride=1, bias=True).to(self.flat.device)
+        self.flat = nn.Parameter(self._pack(list(zip(body[0::2], body[1::2])) + [(head.weight, head.bias)]))
         self.output_dim = int(n_genes)
         return self
 
 
-class _ScoresFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, p_drop, input_dim, ws, *params):
-        B, C, N = x.shape
-        xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(B * N, C)
-        acts, _, _ = _layer_stack(xt, input_dim, params, ws, p_drop)
-        G = params[-2].shape[0]
-        return acts[-1][:, :G].reshape(B, N, G).transpose(1, 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        raise NotImplementedError("HE2RNA.conv is an inspection helper; train through forward / forward_fixed_k")
-
-
 # ---------------------------------------------------------------------------------------------
-# the training step as C calls on one flat parameter buffer (csrc/he2rna_train.hip)
+# the training step as C calls on the model's flat parameter buffer (csrc/he2rna_train.hip)
 # ---------------------------------------------------------------------------------------------
-def param_layout(dims):
-    """sq_he2rna_param_layout for ``dims = [input_dim, *layers, output_dim]``: (weight offsets, bias offsets, total), in floats.
-    Layer i's weight is ``[dims[i + 1], round_up(dims[i], 8)]`` row-major; every tensor starts on a 16-byte boundary."""
-    d = np.asarray(dims, dtype=np.int32)
-    n = len(d) - 1
-    w, b, total = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64), np.zeros(1, dtype=np.int64)
-    _lib.check(_lib.lib().sq_he2rna_param_layout(d.ctypes.data, n, w.ctypes.data, b.ctypes.data, total.ctypes.data))
-    return [int(v) for v in w], [int(v) for v in b], int(total[0])
-
-
 class He2rnaTrainStep:
-    """One training step of he2rna.py:108-127 -- forward, MSE loss, backward, Adam -- as four C calls
-    (sq_he2rna_train_forward, sq_he2rna_train_backward, sq_adamw_step) on flat fp32 buffers: parameters, gradient and
-    the two Adam moments share the padded layout of ``param_layout``.  The arithmetic of the update is
-    ``torch.optim.Adam(lr, betas, eps, weight_decay=0.)``.
-
-    The module's ``conv{i}.weight`` / ``conv{i}.bias`` become VIEWS of the flat parameter buffer, so ``state_dict()``,
-    ``torch.save(model)``, ``evaluate`` and ``he2rna_predict`` see the current values at any time and ``load_state_dict``
-    writes through.  The model has to be on its device before the step is built and must not be moved afterwards.
+    """One training step of he2rna.py:108-127 -- forward, MSE loss, backward, Adam -- as three C calls
+    (sq_he2rna_train_forward, sq_he2rna_train_backward, sq_adamw_step) on flat fp32 buffers: the model's own ``flat`` is trained
+    in place (so ``state_dict()``, ``torch.save(model)`` and ``evaluate`` see the current values at any time); the step owns the
+    gradient and the two Adam moments in the same layout, its workspace and its counters.  The arithmetic of the update is
+    ``torch.optim.Adam(lr, betas, eps, weight_decay=0.)``.  The model has to be on its device before the step is built; once the
+    model owns another buffer (``model.to(...)`` elsewhere, ``replace_head``) the step refuses to run.
 
     Dropout needs no stored mask: unit (row, column) of hidden layer i is kept in step s when Philox4x32-10, keyed by
     ``seed``, says so for (s, i, row, column); ``step_index`` is the s of the next step."""
 
     def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, seed=0):
         _lib.require_gpu()
-        params = model._params()
-        dev = params[0].device
-        if dev.type != "cuda":
+        if not model.flat.is_cuda:
             raise _lib.SequoiaHipError("He2rnaTrainStep needs the model on the GPU (no CPU fallback)")
-        self.model, self.device = model, dev
+        self.model, self.device = model, model.flat.device
         self.lr, self.betas, self.eps, self.seed = float(lr), (float(betas[0]), float(betas[1])), float(eps), int(seed)
-        self.dims = np.asarray([params[0].shape[1]] + [w.shape[0] for w in params[0::2]], dtype=np.int32)
-        self.n_layers = len(self.dims) - 1
-        self.w_off, self.b_off, self.total = param_layout(self.dims)
-        self.flat, self.grad, self.exp_avg, self.exp_avg_sq = (torch.zeros(self.total, dtype=torch.float32, device=dev) for _ in range(4))
-        for (_, view), p in zip(self._views(self.flat), params):
-            view.copy_(p.detach())
-            p.data = view
+        self._built_on = model.flat.detach()           # shares (and keeps alive) the memory this step's state describes
+        self.total = model.flat.numel()
+        self.grad, self.exp_avg, self.exp_avg_sq = (torch.zeros_like(self._built_on) for _ in range(3))
         self.t = 0                     # Adam's step count
         self.step_index = 0            # dropout stream position
         self.pred = None               # raw predictions of the last step, f32 [B, G]
         self._ws, self._shape, self._act_off = None, None, None
 
-    def _views(self, flat):
-        """(state_dict key, view of `flat`) per tensor, in ``model._params()`` order."""
-        for i in range(self.n_layers):
-            n_in, n_out = int(self.dims[i]), int(self.dims[i + 1])
-            ld = _up(n_in, 8)
-            yield f"conv{i}.weight", flat[self.w_off[i]:self.w_off[i] + n_out * ld].view(n_out, ld)[:, :n_in].unsqueeze(-1)
-            yield f"conv{i}.bias", flat[self.b_off[i]:self.b_off[i] + n_out]
+    @property
+    def flat(self):
+        """The model's parameter buffer, if it still is the one this step was built on."""
+        flat = self.model.flat.detach()
+        if flat.data_ptr() != self._built_on.data_ptr() or flat.numel() != self.total:
+            raise _lib.SequoiaHipError("He2rnaTrainStep: the model was moved or its head replaced after this step was built; build a new step")
+        return flat
 
     def param_views(self):
-        return dict(self._views(self.flat))
+        return self.model.grad_views(self.flat)
 
     def grad_views(self):
-        return dict(self._views(self.grad))
+        return self.model.grad_views(self.grad)
 
     def padding_mask(self):
-        """bool [total]: True where the flat layout holds padding (weight columns >= n_in, gaps behind a bias)."""
-        pad = torch.ones(self.total, dtype=torch.bool, device=self.device)
-        for _, v in self._views(pad):
-            v.fill_(False)
-        return pad
+        return self.model.padding_mask()
 
     def _workspace(self, B, N):
         if self._shape != (B, N):
-            off = np.zeros(self.n_layers + 1, dtype=np.int64)
-            need = _lib.lib().sq_he2rna_train_workspace_bytes(self.dims.ctypes.data, self.n_layers, B, N, off.ctypes.data)
+            m = self.model
+            off = np.zeros(m.n_layers + 1, dtype=np.int64)
+            need = _lib.lib().sq_he2rna_train_workspace_bytes(m.dims.ctypes.data, m.n_layers, B, N, off.ctypes.data)
             if need == 0:
                 raise _lib.SequoiaHipArgError(f"libsequoia_hip: {_lib.lib().sq_last_error().decode()}")
             if self._ws is None or self._ws.numel() < need:
@@ -354,35 +341,33 @@ class He2rnaTrainStep:
 
     def saved_activations(self):
         """Copies of what the last step's forward pass saved: the hidden layers' outputs after ReLU and dropout, f32 [B * N, width]."""
-        B, N = self._shape
-        ws = self._ws.view(torch.float32)
-        out = []
-        for i in range(1, self.n_layers):
-            ld = _up(int(self.dims[i]), 8)
-            out.append(ws[self._act_off[i]:self._act_off[i] + B * N * ld].view(B * N, ld)[:, :int(self.dims[i])].clone())
+        (B, N), dims, ws, out = self._shape, self.model.dims, self._ws.view(torch.float32), []
+        for i in range(1, len(dims) - 1):
+            ld = _up(int(dims[i]), 8)
+            out.append(ws[self._act_off[i]:self._act_off[i] + B * N * ld].view(B * N, ld)[:, :int(dims[i])].clone())
         return out
 
     def forward_backward(self, x, y, k):
         """Loss (device scalar) and flat gradient of one batch at top-k `k`, without the update.  x [B, N, C] as the loader
         gives it (tiles x channels), y [B, G]."""
-        lib, dev, m = _lib.lib(), self.device, self.model
+        lib, dev, m, flat = _lib.lib(), self.device, self.model, self.flat
         x = x.to(dev, torch.float32).contiguous()
         y = torch.as_tensor(y).to(dev, torch.float32).contiguous()
-        if x.dim() != 3 or x.shape[2] < m.input_dim or tuple(y.shape) != (x.shape[0], int(self.dims[-1])):
-            raise ValueError(f"He2rnaTrainStep: x must be [batch, tiles, channels >= {m.input_dim}] and y [batch, {int(self.dims[-1])}], "
+        G = m.output_dim
+        if x.dim() != 3 or x.shape[2] < m.input_dim or tuple(y.shape) != (x.shape[0], G):
+            raise ValueError(f"He2rnaTrainStep: x must be [batch, tiles, channels >= {m.input_dim}] and y [batch, {G}], "
                              f"got {tuple(x.shape)} and {tuple(y.shape)}")
         B, N, C = x.shape
-        G = int(self.dims[-1])
         ws = self._workspace(B, N)
         ks = np.asarray([int(k)], dtype=np.int32)
         self.pred = torch.empty(B, G, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
-            _lib.check(lib.sq_he2rna_train_forward(_lib.ptr(x), B, N, C, self.dims.ctypes.data, self.n_layers, _lib.ptr(self.flat), ks.ctypes.data, 1,
+            _lib.check(lib.sq_he2rna_train_forward(_lib.ptr(x), B, N, C, m.dims.ctypes.data, m.n_layers, _lib.ptr(flat), ks.ctypes.data, 1,
                                                    1.0, m.p_drop, self.seed, self.step_index, _lib.ptr(y), 2.0 / (B * G), _lib.ptr(self.pred),
                                                    _lib.ptr(loss), _lib.ptr(ws), ws.numel(), st))
-            _lib.check(lib.sq_he2rna_train_backward(B, N, self.dims.ctypes.data, self.n_layers, _lib.ptr(self.flat), m.p_drop, _lib.ptr(self.grad),
+            _lib.check(lib.sq_he2rna_train_backward(B, N, m.dims.ctypes.data, m.n_layers, _lib.ptr(flat), m.p_drop, _lib.ptr(self.grad),
                                                     _lib.ptr(ws), ws.numel(), st))
         return loss
 

@@ -1,10 +1,16 @@
-"""Host-side contract of the flat-parameter models (ViS, ViT, UniViT): one fp32 buffer ``flat`` in which every reference tensor
-is a slice (``_tmap``), shown to ``state_dict`` / ``load_state_dict`` under the reference's keys; head replacement of the two
-aggregators on the CPU.  Constructors and ``sq_*_layout_init`` are host code: no GPU, no compute calls."""
+"""Host-side contract of the flat-parameter models (ViS, ViT, UniViT, HE2RNA): one fp32 buffer ``flat`` in which every reference
+tensor is a slice (``_tmap``; HE2RNA's weights with padded rows, ``_pitch``), shown to ``state_dict`` / ``load_state_dict`` under the
+reference's keys; head replacement on the CPU; HE2RNA's initial values, padding and pickles.  Constructors and the layout entries
+are host code: no GPU, no compute calls."""
+import io
+import os
+
+import numpy as np
 import pytest
 import torch
 from torch import nn
 
+from sequoia_pub_amd.he2rna import HE2RNA
 from sequoia_pub_amd.uni import UniViT
 from sequoia_pub_amd.vis import ViS
 from sequoia_pub_amd.vit import ViT
@@ -13,6 +19,8 @@ MODELS = {
     "vis": lambda **kw: ViS(8, 64, 1, 1, 64, 64, 64, device="cpu", **kw),
     "vit": lambda **kw: ViT(num_outputs=8, dim=64, depth=1, heads=1, mlp_dim=128, device="cpu", **kw),
     "uni": lambda **kw: UniViT(embed_dim=128, depth=1, num_heads=2, img_size=32, **kw),
+    "he2rna": lambda **kw: HE2RNA(input_dim=30, output_dim=7, layers=[5, 12], device="cpu", **kw),      # row pitches 32, 8, 16: every row padded
+    "he2rna_aligned": lambda **kw: HE2RNA(input_dim=32, output_dim=8, layers=[16, 16], device="cpu", **kw),
 }
 KINDS = sorted(MODELS)
 
@@ -22,6 +30,15 @@ def _numel(shape):
     for s in shape:
         n *= s
     return n
+
+
+def _own(m, flat, k):
+    """A copy of the elements of `flat` that are tensor k's own, in its shape: one run, or one run per row of a padded-row tensor."""
+    off, shape = m._tmap[k]
+    ld = m._pitch.get(k)
+    if ld is None:
+        return flat[off:off + _numel(shape)].reshape(shape).clone()
+    return torch.stack([flat[off + r * ld:off + r * ld + shape[1]] for r in range(shape[0])]).reshape(shape)
 
 
 def _random_reference_dict(m, seed):
@@ -36,7 +53,7 @@ def test_state_dict_has_the_reference_keys_in_order_and_no_flat(kind):
     assert list(sd) == list(m._tmap) and "flat" not in sd
     for k, (off, shape) in m._tmap.items():
         assert tuple(sd[k].shape) == tuple(shape)
-        assert torch.equal(sd[k].reshape(-1), m.flat.detach()[off:off + _numel(shape)])
+        assert sd[k].is_contiguous() and torch.equal(sd[k], _own(m, m.flat.detach(), k))
     pre = nn.ModuleDict({"agg": m}).state_dict()                    # as a submodule: the prefix goes in front of every key
     assert list(pre) == ["agg." + k for k in m._tmap]
 
@@ -101,8 +118,7 @@ def test_named_reference_tensors_are_views_of_the_buffer(kind):
         assert t.data_ptr() == m.flat.data_ptr() + 4 * off, k
     k, t = named[-1]
     t.fill_(3.5)                                                    # a view: the write lands in the buffer
-    off, shape = m._tmap[k]
-    assert bool((m.flat.detach()[off:off + _numel(shape)] == 3.5).all())
+    assert bool((_own(m, m.flat.detach(), k) == 3.5).all())
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -137,3 +153,100 @@ def test_head_replacement_on_the_cpu(kind):
                        ("linear_head.1.weight", lin.weight), ("linear_head.1.bias", lin.bias)):
         assert torch.equal(sd[key], given.detach()), key
     assert "linear_head" not in dict(m.named_children())            # the head lives in the flat buffer, not in a submodule
+
+
+# ---- HE2RNA: what its padded layout adds ------------------------------------------------------------------------------------
+HE_KINDS = ["he2rna", "he2rna_aligned"]
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _assert_padding_is_zero_and_accounted_for(m):
+    pad = m.padding_mask()
+    assert pad.shape == m.flat.shape and pad.dtype == torch.bool
+    assert int(pad.sum()) + sum(_numel(shape) for _, shape in m._tmap.values()) == m.flat.numel()
+    assert bool((m.flat.detach()[pad] == 0).all())
+    own = torch.zeros_like(pad)
+    for k, (off, shape) in m._tmap.items():                         # the mask against the layout restated: rows of `pitch` floats
+        rows, width, ld = (shape[0], shape[1], m._pitch[k]) if k in m._pitch else (1, _numel(shape), 0)
+        for r in range(rows):
+            own[off + r * ld:off + r * ld + width] = True
+    assert torch.equal(pad, ~own)
+
+
+@pytest.mark.parametrize("kind", HE_KINDS)
+def test_he2rna_initial_weights_are_the_conv1d_draws_of_the_reference(kind):
+    torch.manual_seed(11)
+    m = MODELS[kind]()
+    dims = [int(v) for v in m.dims]
+    torch.manual_seed(11)
+    convs = [nn.Conv1d(dims[i], dims[i + 1], kernel_size=1, stride=1, bias=True) for i in range(len(dims) - 1)]
+    sd = m.state_dict()
+    assert list(sd) == [f"conv{i}.{p}" for i in range(len(convs)) for p in ("weight", "bias")]
+    for i, c in enumerate(convs):
+        assert torch.equal(sd[f"conv{i}.weight"], c.weight.detach()) and torch.equal(sd[f"conv{i}.bias"], c.bias.detach())
+    assert [n for n, _ in m.named_parameters()] == ["flat"] and not dict(m.named_children())
+    bias = torch.arange(dims[-1], dtype=torch.float32)
+    assert torch.equal(MODELS[kind](bias_init=bias).state_dict()[f"conv{len(convs) - 1}.bias"], bias)
+
+
+@pytest.mark.parametrize("kind", HE_KINDS)
+def test_he2rna_padding_stays_zero_through_load_and_head_replacement(kind):
+    m = MODELS[kind]()
+    assert [m._pitch[k] for k in m._tmap if k in m._pitch] == ([32, 8, 16] if kind == "he2rna" else [32, 16, 16])
+    _assert_padding_is_zero_and_accounted_for(m)
+    m.load_state_dict(_random_reference_dict(m, 5))
+    _assert_padding_is_zero_and_accounted_for(m)
+    m.replace_head(11)
+    _assert_padding_is_zero_and_accounted_for(m)
+
+
+@pytest.mark.parametrize("kind", HE_KINDS)
+def test_he2rna_head_replacement_keeps_the_body_bit_for_bit(kind):
+    m = MODELS[kind]()
+    m.load_state_dict(_random_reference_dict(m, 6))
+    before = m.state_dict()
+    body = m.flat.detach()[:m.w_off[-1]].clone()
+    last_in = int(m.dims[-2])
+    torch.manual_seed(12)
+    assert m.replace_head(11) is m
+    torch.manual_seed(12)
+    head = nn.Conv1d(last_in, 11, kernel_size=1, stride=1, bias=True)
+    assert isinstance(m.flat, nn.Parameter) and m.flat.requires_grad and m.output_dim == 11
+    assert torch.equal(m.flat.detach()[:m.w_off[-1]], body)          # everything in front of the old last layer, bit for bit
+    after = m.state_dict()
+    assert list(after) == list(before) == list(m._tmap)
+    for k in list(before)[:-2]:
+        assert torch.equal(after[k], before[k]), k
+    assert tuple(after[list(after)[-2]].shape) == (11, last_in, 1) and tuple(after[list(after)[-1]].shape) == (11,)
+    assert torch.equal(after[list(after)[-2]], head.weight.detach()) and torch.equal(after[list(after)[-1]], head.bias.detach())
+
+
+@pytest.mark.parametrize("kind", HE_KINDS)
+def test_he2rna_whole_module_pickle_round_trips(kind):
+    m = MODELS[kind](ks=[1, 5], dropout=0.25)
+    m.load_state_dict(_random_reference_dict(m, 7))
+    buf = io.BytesIO()
+    torch.save(m, buf)
+    buf.seek(0)
+    back = torch.load(buf, weights_only=False)
+    assert isinstance(back, HE2RNA) and torch.equal(back.flat, m.flat) and isinstance(back.flat, nn.Parameter)
+    assert (list(back.ks), back.p_drop, back.input_dim, back.output_dim, back._ws) == ([1, 5], 0.25, m.input_dim, m.output_dim, None)
+    sd = _random_reference_dict(m, 8)                                # the hooks came along: reference keys in, reference keys out
+    back.load_state_dict(sd)
+    assert all(torch.equal(v, sd[k]) for k, v in back.state_dict().items()) and list(back.state_dict()) == list(sd)
+
+
+def test_he2rna_pickle_written_before_the_flat_buffer_loads():
+    """tests/golden/he2rna_parent_module.pt: ``torch.save(HE2RNA(30, 7, layers=[5, 12], ks=[1, 5], dropout=0.25))`` by the commit
+    in front of the flat buffer (``conv{i}`` submodules, no ``flat``; tests/golden/make_he2rna_parity.py), its tensors beside it."""
+    m = torch.load(os.path.join(GOLDEN, "he2rna_parent_module.pt"), map_location="cpu", weights_only=False)
+    want = np.load(os.path.join(GOLDEN, "he2rna_parent_module.npz"))
+    assert isinstance(m, HE2RNA) and [n for n, _ in m.named_parameters()] == ["flat"] and not dict(m.named_children())
+    sd = m.state_dict()
+    assert list(sd) == list(want.files) == [f"conv{i}.{p}" for i in range(3) for p in ("weight", "bias")]
+    for k in want.files:
+        assert sd[k].shape == want[k].shape and np.array_equal(sd[k].numpy(), want[k]), k
+    assert (list(m.ks), m.p_drop, m.input_dim, m.output_dim, [int(v) for v in m.dims]) == ([1, 5], 0.25, 30, 7, [30, 5, 12, 7])
+    _assert_padding_is_zero_and_accounted_for(m)
+    m.load_state_dict({k: torch.from_numpy(want[k]) * 2 for k in want.files})      # and it is a working flat model afterwards
+    assert np.array_equal(m.state_dict()["conv1.weight"].numpy(), want["conv1.weight"] * 2)

@@ -82,4 +82,4 @@ def test_pipeline_clis(tmp_path):
     # the MLP comparator through the same CLI (pretrain_gtex.py:102-105,118-120): whole model pickled as model.pt
     hmodel, hdir = pretrain_gtex.main(["--path_csv", ref, "--feature_path", feat, "--save_dir", os.path.join(root, "pre"), "--exp_name", "h",
                                        "--quick", "1", "--batch_size", "4", "--model", "he2rna"])
-    assert os.path.exists(os.path.join(hdir, "model.pt")) and hmodel.conv2.weight.shape == (24, 256, 1)
+    assert os.path.exists(os.path.join(hdir, "model.pt")) and hmodel.state_dict()["conv2.weight"].shape == (24, 256, 1)

@@ -54,10 +54,10 @@ def test_gradients_match_reference_golden():
     m.eval()                                                   # dropout off, as in the golden run
     xg = x.clone().requires_grad_(True)
     (m.forward_fixed_k(xg, 20) * torch.from_numpy(d["r"]).cuda()).sum().backward()
-    for name, p in m.named_parameters():
+    for name, g in m.grad_views(m.flat.grad).items():
         ref = d["g_" + name]
-        assert p.grad.shape == ref.shape
-        np.testing.assert_allclose(p.grad.cpu().numpy(), ref, rtol=1e-4, atol=1e-4 * np.abs(ref).max())
+        assert g.shape == ref.shape
+        np.testing.assert_allclose(g.cpu().numpy(), ref, rtol=1e-4, atol=1e-4 * np.abs(ref).max())
     np.testing.assert_allclose(xg.grad.cpu().numpy(), d["grad_x"], rtol=1e-4, atol=1e-4 * np.abs(d["grad_x"]).max())
 
 
@@ -144,12 +144,12 @@ def test_gradients_of_narrow_and_unpadded_stacks_match_float64_autograd(name, fo
     (pred * r.cuda()).sum().backward()
     err = float(np.abs(pred.detach().cpu().numpy() - ref["pred"]).max() / np.abs(ref["pred"]).max())
     print(f"HE2RNA {name} {form}: prediction rel err {err:.2e}; " + ", ".join(
-        f"{k} {np.abs(p.grad.cpu().numpy() - ref['grads'][k]).max() / np.abs(ref['grads'][k]).max():.2e}" for k, p in m.named_parameters()))
+        f"{k} {np.abs(gk.cpu().numpy() - ref['grads'][k]).max() / np.abs(ref['grads'][k]).max():.2e}" for k, gk in m.grad_views(m.flat.grad).items()))
     assert err < 1e-4, err
-    for k, p in m.named_parameters():
+    for k, gk in m.grad_views(m.flat.grad).items():
         g = ref["grads"][k]
-        assert p.grad.shape == g.shape
-        np.testing.assert_allclose(p.grad.cpu().numpy(), g, rtol=1e-4, atol=1e-4 * np.abs(g).max(), err_msg=k)
+        assert gk.shape == g.shape
+        np.testing.assert_allclose(gk.cpu().numpy(), g, rtol=1e-4, atol=1e-4 * np.abs(g).max(), err_msg=k)
     np.testing.assert_allclose(xg.grad.cpu().numpy(), ref["gx"], rtol=1e-4, atol=1e-4 * np.abs(ref["gx"]).max())
 
 
@@ -171,11 +171,11 @@ def test_full_size_against_oracle_and_training_step():
     m.train()
     opt = torch.optim.AdamW(m.parameters(), lr=3e-3, weight_decay=0.0)
     y = torch.randn(B, G).cuda()
-    before = m.conv2.weight.detach().clone()
+    before = m.state_dict()["conv2.weight"]
     p1 = m(xc.cuda())
     loss = torch.nn.functional.mse_loss(p1, y)
     opt.zero_grad(); loss.backward(); opt.step()
-    assert torch.isfinite(loss) and not torch.equal(before, m.conv2.weight.detach())
+    assert torch.isfinite(loss) and not torch.equal(before, m.state_dict()["conv2.weight"])
     assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in m.parameters())
     with torch.no_grad():                                       # dropout is live in training mode
         a, b = m.forward_fixed_k(xc.cuda(), 10), m.forward_fixed_k(xc.cuda(), 10)

@@ -260,7 +260,7 @@ def test_dropout_p0_is_the_dropout_free_path_and_p1_is_refused():
     c, sd, batches, m = _model("l5x12", dropout=0.0)
     x, y = batches[0]
     xt = x.to(DEV).reshape(c["B"] * c["N"], c["C"]).contiguous()
-    stack, _, _ = he._layer_stack(xt, c["D"], m._params(), m._workspace(torch.device(DEV)))
+    stack, _ = he._layer_stack(xt, m)
     tr = He2rnaTrainStep(m, tc.LR)
     tr.forward_backward(x, y, 5)
     for a, b, width in zip(tr.saved_activations(), stack[1:-1], c["layers"]):
@@ -297,7 +297,7 @@ def test_full_size_step_matches_the_autograd_path():
     m.train()
     loss = torch.nn.functional.mse_loss(m.forward_fixed_k(x.to(DEV).transpose(1, 2), 10), y.to(DEV))
     loss.backward()
-    ref = {n: p.grad.clone() for n, p in m.named_parameters()}
+    ref = {n: g.clone() for n, g in m.grad_views(m.flat.grad).items()}
     tr = He2rnaTrainStep(m, 1e-3)
     got = tr.forward_backward(x, y, 10)
     assert abs(float(got) - float(loss.detach())) <= 1e-4 * abs(float(loss.detach()))
@@ -362,7 +362,7 @@ def _check_outputs(out, n_genes):
         assert s["preds"].shape == (2, n_genes) and s["random"].shape == (2, n_genes) and s["real"].shape == (2, n_genes)
         assert (s["preds"] >= 0).all() and (s["random"] >= 0).all() and not np.array_equal(s["preds"], s["random"])
         m = torch.load(os.path.join(out, f"model_{i}.pt"), weights_only=False)
-        assert isinstance(m, HE2RNA) and tuple(m.conv2.weight.shape) == (n_genes, 256, 1)
+        assert isinstance(m, HE2RNA) and tuple(m.state_dict()["conv2.weight"].shape) == (n_genes, 256, 1)
     return res
 
 
