@@ -747,6 +747,51 @@ size_t sq_map_gene_corr_workspace_bytes(int n, int K);
 int sq_map_gene_corr(const float* pred, int n, int ld, const int32_t* cols, int K, double* out, void* workspace,
                      size_t workspace_bytes, sq_stream_t stream);
 
+/* Map statistics, the cluster map: sns.clustermap(corrdf) of gbm_celltype_analysis.py:81,145 reorders the correlation
+ * matrix by scipy.cluster.hierarchy.linkage(corrdf.values, method='average', metric='euclidean') and the leaf order of its
+ * dendrogram.  The two entries compute that for B problems of one shape per call, bit for bit as scipy does, under the
+ * conventions above (every argument checked before the first launch, *_workspace_bytes 0 exactly for the refused
+ * arguments, asynchronous, no floating-point atomics, two calls give the same bytes).  2 <= K <= SQ_MAP_MAX_LINK_ROWS (what
+ * one workgroup's LDS holds of the chain, the cluster sizes, the union-find parents and the sort keys),
+ * 1 <= B <= SQ_MAP_MAX_LINK_BATCH, 1 <= M <= SQ_MAP_MAX_ROWS.
+ *
+ *   sq_map_row_distances   : pdist(A, 'euclidean') of B matrices a f64 [B, K, ld] of K observations x M features (M <= ld):
+ *                         dist f64 [B, K, K], symmetric (each pair computed once and stored on both sides), the diagonal
+ *                         exactly 0.  Per pair scipy's loop: s = 0; for t = 0 .. M-1: d = a[i][t] - a[j][t]; s = s + d d, the
+ *                         product and the sum rounded separately (no FMA), then sqrt(s).  status int32 [B]: 0, or 1 + the
+ *                         smallest row that has a distance to another row that is not finite (scipy's linkage raises
+ *                         ValueError there).
+ *   sq_map_linkage_average : scipy's nn_chain for method='average' on dist f64 [B, K, K] (symmetric, as above; OVERWRITTEN),
+ *                         one workgroup per problem.  A nearest-neighbour chain: from the chain's top x the nearest live
+ *                         cluster (the element below x in the chain on ties with it, otherwise the smallest index); a
+ *                         reciprocal pair a < b is merged at that distance: a dies, b takes na + nb members and
+ *                         D[i][b] = D[b][i] = (na D[i][a] + nb D[i][b]) / (na + nb) for every live i (two products, a sum and
+ *                         a quotient, each rounded); an empty chain restarts from the live cluster of smallest index.  The
+ *                         K - 1 merges, sorted stably by distance and relabelled by a union-find over 2K - 1 labels, are
+ *                         Z f64 [B, K-1, 4] = (smaller root, larger root, distance, members), row r creating label K + r;
+ *                         leaves int32 [B, K] is the depth-first walk from label 2K - 2, column 0 first: leaves_list(Z),
+ *                         dendrogram(Z, no_plot=True)['leaves'].  dist_status (NULL: none) is sq_map_row_distances' status:
+ *                         a problem whose word is not 0 is left alone (SQ_LINK_NONFINITE; Z, leaves and dist untouched).
+ *                         With or without it every search checks the row it reads on the device: a distance to a live
+ *                         cluster that is NaN, infinite or negative ends the problem with SQ_LINK_BAD_DISTANCE before any
+ *                         index is derived from it (Z and leaves untouched, dist partly merged), so a matrix nobody has
+ *                         checked cannot send the kernel outside its buffers.
+ *                         Bounded work: a chain makes at most 3 (K - 1) searches; the kernel counts them and ends the problem
+ *                         with SQ_LINK_SEARCH_BOUND past that.  status int32 [B], always written.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_MAP_MAX_LINK_ROWS 4096
+#define SQ_MAP_MAX_LINK_BATCH 65535
+#define SQ_LINK_OK 0
+#define SQ_LINK_NONFINITE 1            /* the problem's dist_status word was not 0: nothing was computed */
+#define SQ_LINK_SEARCH_BOUND 2         /* more than 3 (K - 1) nearest-neighbour searches */
+#define SQ_LINK_BAD_DISTANCE 3         /* a search met a distance that is NaN, infinite or negative */
+size_t sq_map_row_distances_workspace_bytes(int B, int K, int M);
+int sq_map_row_distances(const double* a, int B, int K, int M, int ld, double* dist, int32_t* status, void* workspace,
+                         size_t workspace_bytes, sq_stream_t stream);
+size_t sq_map_linkage_average_workspace_bytes(int B, int K);
+int sq_map_linkage_average(double* dist, int B, int K, const int32_t* dist_status, double* Z, int32_t* leaves, int32_t* status,
+                           void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Ground-truth alignment: what spatial_vis/get_emd.py computes between a predicted slide and its spatial-transcriptomics
  * spots before the EMD -- get_average (:27-38), median_filter (:41-51) and the np.unique counts of :204-205; the

@@ -9,6 +9,13 @@ category -- computed on the device (mapstats.py), and the mean correlation over 
 Writes ``<pred_folder>/corr_maps/<slide>_corr.csv``, ``<pred_folder>/corr_maps/total_corr.csv`` and
 ``<pred_folder>/spatial_maps/<slide>.csv`` (xcoord_tf, ycoord_tf, per label its mean and percentile, color).
 
+``--clustermap`` also writes what the reference's ``sns.clustermap`` figures (:81,145) are drawn from: per slide, and as
+``total_*`` for the mean matrix, ``corr_maps/<slide>_clustered.csv`` (the correlation frame with rows and columns in the
+leaf order of the average linkage of its rows), ``corr_maps/<slide>_linkage.csv`` (scipy's Z: left, right, distance, size)
+and ``corr_maps/<slide>_order.csv`` (gene, color in leaf order: the row colours of the figure).  The mean matrix is
+clustered over the genes present in every slide (its all-NaN rows and columns are dropped); a matrix that still holds a
+NaN -- a constant gene -- is skipped with a printed line.
+
 The gene list shrinks cumulatively over the slides as the reference's does (:70): slide k is correlated over the genes of
 ``all.npy`` present in slides 1..k; the maps (the reference's second loop, :91-111) use the genes present in every slide.
 Where the reference's ``set`` leaves the order to chance, the order of ``all.npy`` is kept and slides are taken in sorted
@@ -36,6 +43,8 @@ def build_parser():
     ap.add_argument("--all_genes", required=True, help="all.npy: the genes to correlate")
     ap.add_argument("--celltype_dir", required=True, help="holds " + ", ".join(f + ".npy" for f in CELLTYPE_FILES))
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--clustermap", action="store_true",
+                    help="also write corr_maps/<slide>_clustered.csv, _linkage.csv and _order.csv (and total_*): the cluster maps' content")
     return ap
 
 
@@ -46,6 +55,31 @@ def group_categories(lists):
 
 def load_categories(celltype_dir):
     return group_categories({f: np.load(os.path.join(celltype_dir, f + ".npy"), allow_pickle=True).tolist() for f in CELLTYPE_FILES})
+
+
+def gene_colors(categories, colors=None):
+    """gene -> hex colour of its cell-type group: the reference's ``mapper`` (:42-56), a later group overriding an earlier one."""
+    colors = mapstats.COLORS if colors is None else colors
+    mapper = {}
+    for label, genes in categories.items():
+        mapper.update(dict.fromkeys(genes, colors[label]))
+    return mapper
+
+
+def write_clustermap(corr, name, folder, mapper, device):
+    """The three files of one cluster map; returns False (and says why) where there is nothing to cluster."""
+    if corr.shape[0] < 2:
+        print(f"{name}: no cluster map -- the correlation matrix has {corr.shape[0]} genes, fewer than two")
+        return False
+    if bool(corr.isna().values.any()):
+        print(f"{name}: no cluster map -- the correlation matrix holds a NaN (a constant gene)")
+        return False
+    order, clustered, Z = mapstats.cluster_order(corr, device=device, return_linkage=True)
+    clustered.to_csv(os.path.join(folder, name + "_clustered.csv"))
+    pd.DataFrame(Z.cpu().numpy(), columns=["left", "right", "distance", "size"]).to_csv(os.path.join(folder, name + "_linkage.csv"), index=False)
+    genes = list(clustered.index)
+    pd.DataFrame({"gene": genes, "color": [mapper.get(g, "") for g in genes]}).to_csv(os.path.join(folder, name + "_order.csv"), index=False)
+    return True
 
 
 def cumulative_genes(all_genes, slide_columns):
@@ -90,14 +124,21 @@ def main(argv=None):
     paths = [os.path.join(args.pred_folder, name, "stride-1.csv") for name in names]
     gene_lists = cumulative_genes(all_genes, [pd.read_csv(p, nrows=0).columns for p in paths])
     corr_frames = []
+    mapper = gene_colors(categories) if args.clustermap else None
     for name, path, genes in zip(names, paths, gene_lists):
         print(name)
         corr, maps = slide_frames(pd.read_csv(path), genes, gene_lists[-1], categories, args.device)
         corr.to_csv(os.path.join(args.pred_folder, "corr_maps", name + "_corr.csv"))
         maps.to_csv(os.path.join(args.pred_folder, "spatial_maps", name + ".csv"), index=False)
         corr_frames.append(corr)
+        if args.clustermap:
+            write_clustermap(corr, name, os.path.join(args.pred_folder, "corr_maps"), mapper, args.device)
     total = mapstats.mean_correlation(corr_frames)
     total.to_csv(os.path.join(args.pred_folder, "corr_maps", "total_corr.csv"))
+    if args.clustermap:
+        # the reference's sum_df carries NaN for every gene a later slide lacks (:70,137-140) and its clustermap call fails there
+        shared = total.dropna(axis=0, how="all").dropna(axis=1, how="all")
+        write_clustermap(shared, "total", os.path.join(args.pred_folder, "corr_maps"), mapper, args.device)
     return total
 
 

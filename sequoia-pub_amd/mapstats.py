@@ -14,10 +14,11 @@ import torch
 
 from . import _lib
 from ._abi import CONSTANTS as _C
-from ._tables import call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table
+from ._tables import _on_device, call as _call, columns as _columns, empty as _empty, kept_rows as _kept_rows, table as _table
 
 MAX_ROWS = _C["SQ_MAP_MAX_ROWS"]
 MAX_CORR_COLS = _C["SQ_MAP_MAX_CORR_COLS"]
+MAX_LINK_ROWS = _C["SQ_MAP_MAX_LINK_ROWS"]                  # rows one average-linkage problem may have
 LABELS = ("ac", "cc", "mes", "lin")
 # gbm_celltype_analysis.py:44-47,102 (the reference's names: 'purple' is the teal, 'green' the ochre)
 COLORS = OrderedDict([("ac", "#36CEBC"), ("cc", "#CE3649"), ("mes", "#3648CE"), ("lin", "#CEBC36")])
@@ -141,3 +142,107 @@ def mean_correlation(frames):
     for f in frames[1:]:
         total = total + f
     return total / len(frames)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cluster map: sns.clustermap(corrdf) of gbm_celltype_analysis.py:81,145 without the figure
+# ---------------------------------------------------------------------------------------------------------------------
+def _observations(A, what):
+    """A f64 device tensor [K, M] or [B, K, M] -> ([B, K, M] view whose problems are K rows of leading dimension ld, B, K, M,
+    ld, whether a batch was given)."""
+    _on_device(A, what)
+    if A.dtype != torch.float64:
+        raise ValueError(f"{what}: dtype {A.dtype}, expected torch.float64")
+    if A.dim() not in (2, 3):
+        raise ValueError(f"{what}: a [K, M] matrix or a [B, K, M] batch is expected, got shape {tuple(A.shape)}")
+    batched = A.dim() == 3
+    t = A if batched else A.unsqueeze(0)
+    B, K, M = (int(s) for s in t.shape)
+    if B > 0 and K > 0 and M > 0:
+        rows_ok = t.stride(2) == 1 and (K == 1 or t.stride(1) >= M)
+        if not (rows_ok and (B == 1 or K == 1 or t.stride(0) == K * t.stride(1))):
+            t = t.contiguous()
+    ld = max(int(t.stride(1)), M, 1) if K > 1 and M > 0 else max(M, 1)
+    return t, B, K, M, ld, batched
+
+
+def _distances(t, B, K, M, ld, status):
+    L = _lib.lib()
+    need = int(L.sq_map_row_distances_workspace_bytes(B, K, M))
+    dist = _empty(torch.float64, t.device, *((B, K, K) if need else (1, 1, 1)))     # a refused K may be too many rows to square
+    src = t if t.numel() else _empty(torch.float64, t.device, 1)
+    _call(L.sq_map_row_distances, t.device, src, B, K, M, ld, dist, status, workspace=need)
+    return dist
+
+
+def _raise_not_finite(what, dist_status):
+    """dist_status: the downloaded int32 [B] words of sq_map_row_distances."""
+    bad = np.nonzero(dist_status)[0]
+    if bad.size:
+        b = int(bad[0])
+        where = f" of problem {b}" if dist_status.size > 1 else ""
+        raise ValueError(f"{what}: row {int(dist_status[b]) - 1}{where} has a distance that is not finite (a NaN or infinite entry; a constant "
+                         "gene makes its row and column of a correlation matrix NaN)")
+
+
+def row_distances(A):
+    """``scipy.spatial.distance.pdist(A, 'euclidean')`` as a square matrix, bit-equal to scipy: A f64 device tensor [K, M] (K
+    observations of M features; rows may be a view of a wider table) or a batch [B, K, M] -> f64 [K, K] or [B, K, K],
+    symmetric with an exactly-zero diagonal.  Per pair the features are summed in ascending order, product and sum rounded
+    separately.  2 <= K <= MAX_LINK_ROWS.  A distance that is not finite raises ValueError naming the first such row."""
+    _lib.require_gpu()
+    t, B, K, M, ld, batched = _observations(A, "row_distances")
+    status = _empty(torch.int32, t.device, B)
+    dist = _distances(t, B, K, M, ld, status)
+    _raise_not_finite("row_distances", status.cpu().numpy())
+    return dist if batched else dist[0]
+
+
+def linkage_average(A):
+    """``Z = scipy.cluster.hierarchy.linkage(A, method='average', metric='euclidean')`` and ``leaves_list(Z)`` (the order
+    ``dendrogram(Z, no_plot=True)['leaves']``, what seaborn's clustermap reorders by), bit-equal to scipy, ties and zero
+    distances included.  A f64 device tensor [K, M] or a batch [B, K, M]; returns (Z f64 [K-1, 4], leaves int32 [K]) on the
+    device, with a leading B for a batch (a batch equals the single calls byte for byte).  2 <= K <= MAX_LINK_ROWS: above
+    it the library refuses (SequoiaHipArgError).  A distance that is not finite raises ValueError naming the first such
+    row, as scipy raises; the status words are read once, after both launches."""
+    _lib.require_gpu()
+    t, B, K, M, ld, batched = _observations(A, "linkage_average")
+    L = _lib.lib()
+    status = _empty(torch.int32, t.device, 2, B)                # row 0: the distances' words, row 1: the linkage's
+    dist = _distances(t, B, K, M, ld, status[0])
+    need = int(L.sq_map_linkage_average_workspace_bytes(B, K))
+    Z = _empty(torch.float64, t.device, *((B, K - 1, 4) if need else (1, 1, 4)))
+    leaves = _empty(torch.int32, t.device, *((B, K) if need else (1, 1)))
+    _call(L.sq_map_linkage_average, t.device, dist, B, K, status[0], Z, leaves, status[1], workspace=need)
+    words = status.cpu().numpy()
+    _raise_not_finite("linkage_average", words[0])
+    if words[1].any():
+        b = int(np.nonzero(words[1])[0][0])
+        why = {_C["SQ_LINK_SEARCH_BOUND"]: "more than 3 (K - 1) nearest-neighbour searches",
+               _C["SQ_LINK_BAD_DISTANCE"]: "a search met a distance that is NaN, infinite or negative"}.get(int(words[1][b]), "unknown status")
+        raise _lib.SequoiaHipError(f"linkage_average: problem {b} ended with status {int(words[1][b])} ({why})")
+    return (Z, leaves) if batched else (Z[0], leaves[0])
+
+
+def cluster_order(matrix, device="cuda:0", return_linkage=False):
+    """The rows and columns of a square symmetric matrix in the leaf order of the average linkage of its rows: what
+    ``sns.clustermap(matrix)`` draws (seaborn clusters rows and columns separately; of a symmetric matrix both are this one
+    linkage).  matrix: a DataFrame (uploaded to ``device``) -> (leaf order as an int array, the reordered DataFrame); or an
+    f64 device tensor [K, K] -> (int32 leaves, ``matrix[leaves][:, leaves]``) on the device.  return_linkage: Z comes third.
+    The matrix must be symmetric bit for bit (ValueError otherwise: the one order would not serve both axes)."""
+    frame = None if torch.is_tensor(matrix) else matrix
+    M = matrix if frame is None else torch.as_tensor(np.ascontiguousarray(frame.values, dtype=np.float64)).to(device)
+    if M.dim() != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError(f"cluster_order: a square matrix is expected, got shape {tuple(M.shape)}")
+    if M.dtype != torch.float64:
+        raise ValueError(f"cluster_order: dtype {M.dtype}, expected torch.float64")
+    if not torch.equal(M.contiguous().view(torch.int64), M.t().contiguous().view(torch.int64)):
+        raise ValueError("cluster_order: the matrix is not symmetric bit for bit")
+    Z, leaves = linkage_average(M)
+    if frame is None:
+        idx = leaves.to(torch.int64)
+        out = (leaves, M[idx][:, idx])
+    else:
+        order = leaves.cpu().numpy()
+        out = (order, frame.iloc[order, order])
+    return out + (Z,) if return_linkage else out
