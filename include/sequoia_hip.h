@@ -574,6 +574,16 @@ int sq_he2rna_train_backward(int batch, int n_tiles, const int32_t* dims, int n_
  *                          plan of exactly these sizes and filter (device memory, 4-byte aligned).  One launch; the
  *                          intermediate image lives in LDS.  Sizes whose narrowest band of rows does not fit the 160 KiB
  *                          of LDS (very wide images under a large reduction) are refused with the byte count.
+ *   sq_resize_u8_gather  : the same kernels, plan and bytes with a gather in front and 3 or 4 bytes per source pixel:
+ *                          src_u8 uint8 [n_src, h_in, w_in, pixel_bytes] (pixel_bytes 3, or 4 = RGBA with the fourth byte
+ *                          ignored and the base 4-byte aligned) -> dst_u8 uint8 [m, h_out, w_out, 3], dst[j] = the resize of
+ *                          src[index[j]].  index: int32 [m] in device memory, or null for the identity with m = n_src.  An
+ *                          index outside [0, n_src) gives an all-zero image (it is compared before it addresses anything).
+ *                          m = 0 launches nothing.  sq_resize_u8 is its call with pixel_bytes 3 and a null index.
+ *   sq_pack_rgb_gather   : the same gather without a resize: src_u8 [n_src, h, w, pixel_bytes] -> dst_u8 [m, h, w, 3] dense
+ *                          RGB, dst[j] = src[index[j]][..., :3]; extents in 1..SQ_RESIZE_MAX_DIM; index, out-of-range
+ *                          entries and m = 0 as above.  Dword loads and stores where a tile starts dword-aligned.
+ *                          Both are asynchronous on `stream`; arguments are checked before the launch.
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_RESIZE_BILINEAR 0 /* PIL.Image.BILINEAR */
 #define SQ_RESIZE_BICUBIC 1  /* PIL.Image.BICUBIC, a = -0.5 */
@@ -582,6 +592,10 @@ size_t sq_resize_plan_bytes(int h_in, int w_in, int h_out, int w_out, int filter
 int sq_resize_plan_init(int h_in, int w_in, int h_out, int w_out, int filter, int32_t* plan, size_t plan_bytes);
 int sq_resize_u8(const uint8_t* src_u8, int n, int h_in, int w_in, uint8_t* dst_u8, int h_out, int w_out, int filter,
                  const int32_t* plan_dev, sq_stream_t stream);
+int sq_resize_u8_gather(const uint8_t* src_u8, int n_src, int pixel_bytes, const int32_t* index, int m, int h_in, int w_in,
+                        uint8_t* dst_u8, int h_out, int w_out, int filter, const int32_t* plan_dev, sq_stream_t stream);
+int sq_pack_rgb_gather(const uint8_t* src_u8, int n_src, int pixel_bytes, const int32_t* index, int m, int h, int w,
+                       uint8_t* dst_u8, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Patch filter: the per-tile tissue and contrast test of patch generation
@@ -614,6 +628,10 @@ int sq_resize_u8(const uint8_t* src_u8, int n, int h_in, int w_in, uint8_t* dst_
  *                          or null: thr_R, thr_G, thr_B, thr_S, mask_count, dilated_count, contrast_ratio, 0 (the counts are
  *                          exact); mask_raw / mask_dilated uint8 [n, h, w] (0 / 1), each may be null.  One launch, one
  *                          workgroup per tile, asynchronous on `stream`; arguments are checked before the launch.
+ *   sq_patch_filter_px   : the same with pixel_bytes bytes per pixel: 3 is sq_patch_filter; 4 takes [n, h, w, 4] (RGBA as a
+ *                          slide reader returns it), the base 4-byte aligned, the fourth byte of every pixel ignored.  Only
+ *                          the load differs (whole dwords, nothing staged): every output equals the 3-byte call on the same
+ *                          RGB values bit for bit.  The workspace does not depend on pixel_bytes.
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_PATCH_FILTER_MIN_DIM 8
 #define SQ_PATCH_FILTER_MAX_DIM 512
@@ -621,6 +639,9 @@ size_t sq_patch_filter_workspace_bytes(int n, int h, int w);
 int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, int rgb_min, double background_threshold,
                     double contrast_fraction, uint8_t* keep, double* stats, uint8_t* mask_raw, uint8_t* mask_dilated,
                     void* workspace, size_t workspace_bytes, sq_stream_t stream);
+int sq_patch_filter_px(const uint8_t* patches_u8, int n, int h, int w, int pixel_bytes, int rgb_min, double background_threshold,
+                       double contrast_fraction, uint8_t* keep, double* stats, uint8_t* mask_raw, uint8_t* mask_dilated,
+                       void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Slide mask: the whole-slide tissue mask of patch generation and its closing
@@ -645,6 +666,8 @@ int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, int rgb_min,
  *                          raw one.  Arguments are checked before anything is launched; the call clears the part of the
  *                          workspace it needs cleared on `stream`, is asynchronous on it and never synchronises.
  *                          The closing works on tiles of SQ_SLIDE_MASK_TILE_ROWS x SQ_SLIDE_MASK_TILE_COLS mask bits.
+ *   sq_slide_mask_px     : the same with pixel_bytes bytes per pixel: 3 is sq_slide_mask; 4 takes [h, w, 4], the base 4-byte
+ *                          aligned, the fourth byte ignored; same bounds, workspace and bytes out.
  * ---------------------------------------------------------------------------------------------------------- */
 #define SQ_SLIDE_MASK_MAX_DIM 32768
 #define SQ_SLIDE_MASK_MAX_ITERATIONS 8
@@ -654,6 +677,9 @@ size_t sq_slide_mask_workspace_bytes(int h, int w);
 int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, int iterations, int transpose,
                   uint8_t* mask_raw, uint8_t* mask_closed, double* stats,
                   void* workspace, size_t workspace_bytes, sq_stream_t stream);
+int sq_slide_mask_px(const uint8_t* img_u8, int h, int w, int pixel_bytes, int rgb_min, int iterations, int transpose,
+                     uint8_t* mask_raw, uint8_t* mask_closed, double* stats,
+                     void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Tile grid: which grid tiles of a slide the spatial maps read

@@ -10,15 +10,36 @@ upload of the slide's patches and batched HIP launches with the transform fused:
 Under torchrun the slide list is sharded across the GPUs (the reference's --start/--end, automatically)."""
 import argparse
 import os
-import random
 
 import numpy as np
 import torch
 
 from .. import store
 from ..data import shard_rows
+from ..features import patch_features, sample_keys
 from ..resnet import resnet50
 from .common import init_distributed, ref_frame, seed_everything
+
+
+def build_extractor(args, device):
+    """The extractor that ``--feat_type``, ``--compute_dtype`` and ``--weights`` name, on `device`, in eval mode."""
+    if args.feat_type == 'resnet':
+        model = resnet50(pretrained=args.weights is None, compute_dtype=args.compute_dtype)
+        if args.weights:
+            model.load_state_dict(torch.load(args.weights, map_location='cpu'))
+    elif args.feat_type == 'uni':                                            # compute_features_hdf5.py:62-68
+        if args.compute_dtype not in ('fp32', 'bf16', 'f16x3'):
+            raise SystemExit('--feat_type uni runs in fp32, bf16 or f16x3 (bf16x3 is the ResNet-50 embedder\'s; f16x3 is the split mode for uni)')
+        from ..uni import create_model
+        model = create_model("vit_large_patch16_224", img_size=224, patch_size=16, init_values=1e-5, num_classes=0,
+                             dynamic_img_size=True, compute_dtype=args.compute_dtype)
+        if args.weights:
+            model.load_state_dict(torch.load(args.weights, map_location='cpu'), strict=True)
+        elif os.environ.get("SEQUOIA_ALLOW_RANDOM_UNI") != "1":
+            raise SystemExit('--feat_type uni needs --weights <path to UNI pytorch_model.bin> (gated download, hf.co/MahmoodLab/UNI)')
+    else:
+        raise SystemExit('please specify feat_type "resnet" or "uni"')
+    return model.to(device).eval()
 
 
 def main(argv=None):
@@ -43,23 +64,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     seed_everything(args.seed)
     rank, world, device = init_distributed()
-    if args.feat_type == 'resnet':
-        model = resnet50(pretrained=args.weights is None, compute_dtype=args.compute_dtype)
-        if args.weights:
-            model.load_state_dict(torch.load(args.weights, map_location='cpu'))
-    elif args.feat_type == 'uni':                                            # compute_features_hdf5.py:62-68
-        if args.compute_dtype not in ('fp32', 'bf16', 'f16x3'):
-            raise SystemExit('--feat_type uni runs in fp32, bf16 or f16x3 (bf16x3 is the ResNet-50 embedder\'s; f16x3 is the split mode for uni)')
-        from ..uni import create_model
-        model = create_model("vit_large_patch16_224", img_size=224, patch_size=16, init_values=1e-5, num_classes=0,
-                             dynamic_img_size=True, compute_dtype=args.compute_dtype)
-        if args.weights:
-            model.load_state_dict(torch.load(args.weights, map_location='cpu'), strict=True)
-        elif os.environ.get("SEQUOIA_ALLOW_RANDOM_UNI") != "1":
-            raise SystemExit('--feat_type uni needs --weights <path to UNI pytorch_model.bin> (gated download, hf.co/MahmoodLab/UNI)')
-    else:
-        raise SystemExit('please specify feat_type "resnet" or "uni"')
-    model.to(device).eval()
+    model = build_extractor(args, device)
     df = ref_frame(args.ref_file, args.tcga_projects, args.start, args.end)
     lo, hi = shard_rows(df.shape[0], rank, world)
     df = df.iloc[lo:hi]
@@ -80,19 +85,10 @@ def main(argv=None):
             continue
         try:
             with store.File(path, 'r') as f_read:
-                keys = list(f_read.keys())
-                if len(keys) > args.max_patch_number:
-                    keys = random.sample(keys, args.max_patch_number)
+                keys = sample_keys(f_read.keys(), args.max_patch_number)
                 patches = np.stack([np.asarray(f_read[key][:]) for key in keys])
             patches = torch.from_numpy(patches)
-            if args.feat_type == 'uni' and patches.shape[1] != 224:              # transforms.Resize(224), :54
-                if args.resize == 'pil':
-                    from ..imgproc import resize_u8_pil
-                    patches = resize_u8_pil(patches.to(device), 224, "bilinear")
-                else:
-                    from ..uni import resize_u8
-                    patches = resize_u8(patches.to(device), 224)
-            feats = model.extract_patches_u8(patches, sub_batch=1000).cpu().numpy()      # clamped per mode / patch size by the extractor
+            feats = patch_features(model, patches, args.feat_type, args.resize, device).cpu().numpy()
             f_write = store.File(os.path.join(path_h5, WSI + '.h5'), "w")
             f_write.create_dataset(f"{args.feat_type}_features", data=feats)
             f_write.close()

@@ -11,7 +11,8 @@ import torch
 
 from .. import store
 from ..data import shard_rows
-from ..kmeans import kmeans_fit, kmeans_fit_ragged
+from ..features import cluster
+from ..kmeans import kmeans_fit_ragged
 from .common import init_distributed, ref_frame, seed_everything
 
 
@@ -89,7 +90,7 @@ def main(argv=None):
             if len(pending) >= args.batch_slides:
                 flush()
             continue
-        r = kmeans_fit(torch.from_numpy(features).to(device), args.num_clusters, random_state=0)
+        r = cluster(torch.from_numpy(features).to(device), args.num_clusters, random_state=0)
         write(WSI, f, r["cluster_features"][0].cpu().numpy())
     flush()
     print('Done!')

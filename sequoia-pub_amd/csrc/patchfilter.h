@@ -90,7 +90,27 @@ static __device__ double pf_otsu_s(const uint32_t* cnt, int total, double s_min,
     return (pf_edge(arg, s_min, s_max, step) + pf_edge(arg + 1, s_min, s_max, step)) / 2.0;
 }
 
-// Stages the npx <= PF_CHUNK_PX pixels at p0 (any alignment) in LDS with 16-byte loads aligned down; returns the skew: pixel
+// pixel_bytes = 4 (RGBA, the fourth byte ignored): f(i, r, g, b) for the npx pixels at p0, which is 4-byte aligned, so a pixel
+// is one dword and a wave's load 256 contiguous bytes: nothing to stage and no skew.  Thread t takes pixels t, t + THREADS,
+// ...; four loads are issued before the first is used.  No barrier.
+template <int THREADS, typename F>
+__device__ __forceinline__ void pf_pixels4(const uint8_t* p0, int npx, F&& f) {
+    const uint32_t* __restrict__ px = (const uint32_t*)p0;
+    int i = threadIdx.x;
+    for (; i + 3 * THREADS < npx; i += 4 * THREADS) {
+        uint32_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = px[i + u * THREADS];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f(i + u * THREADS, (int)(v[u] & 255u), (int)((v[u] >> 8) & 255u), (int)((v[u] >> 16) & 255u));
+    }
+    for (; i < npx; i += THREADS) {
+        const uint32_t v = px[i];
+        f(i, (int)(v & 255u), (int)((v >> 8) & 255u), (int)((v >> 16) & 255u));
+    }
+}
+
+// Stages the npx <= PF_CHUNK_PX 3-byte pixels at p0 (any alignment) in LDS with 16-byte loads aligned down; returns the skew: pixel
 // i's bytes are stage[skew + 3 i ..].  [src, send) is the whole buffer: only the 16-byte lines at its two ends are read by
 // the byte.  Every thread of the workgroup calls it; it ends with a barrier and begins with one (the previous chunk has
 // been read).

@@ -10,7 +10,9 @@
 //
 // Kernel: one workgroup of 512 threads per tile, three sweeps over the tile's bytes.  A sweep stages 4096 pixels at a time
 // in LDS with 16-byte global loads (tiles of an odd size start at every alignment: the loads are aligned down and the skew
-// is applied when the staged bytes are read), then every thread takes pixels tid, tid + 512, ...
+// is applied when the staged bytes are read), then every thread takes pixels tid, tid + 512, ...  With pixel_bytes = 4
+// (sq_patch_filter_px: RGBA as a slide reader returns it) a pixel is an aligned dword: a sweep loads the pixels straight from
+// global memory, nothing is staged, and the same lambdas see the same r, g, b -- so every output is the 3-byte call's.
 //   sweep 1   byte histograms of R, G, B; min and max of the saturation s; histogram of the upper 11 bits of the luminance
 //             key 2125 R + 7154 G + 721 B (22 bits)
 //             -> integer Otsu of the three channels (three lanes, one per channel: all sums are integers, one forward walk)
@@ -49,6 +51,7 @@ struct PfArgs {
     double count_bound;      // fl(background_threshold * (double)(h w))
     double fraction;
     int pitch;               // 32-bit words per mask row
+    int px;                  // bytes per pixel: 3, or 4 with the fourth ignored
 };
 
 struct alignas(16) PfShared {
@@ -133,10 +136,16 @@ __device__ __forceinline__ void pf_zero(uint32_t* p, int words) {
     for (int i = threadIdx.x; i < words; i += PF_THREADS) p[i] = 0u;
 }
 
-// f(pixel index, r, g, b) for every pixel of the tile, staged through LDS
-template <typename F>
+// f(pixel index, r, g, b) for every pixel of the tile: 3-byte pixels staged through LDS, 4-byte pixels loaded as dwords
+template <int PX, typename F>
 __device__ __forceinline__ void pf_sweep(const PfArgs& a, int img, uint8_t* stage, F&& f) {
     const int tid = threadIdx.x, hw = a.h * a.w;
+    if constexpr (PX == 4) {
+        __syncthreads();                       // what the caller cleared is cleared before the first f
+        pf_pixels4<PF_THREADS>(a.src + (size_t)img * hw * 4, hw, f);
+        __syncthreads();
+        return;
+    }
     const uint8_t* const simg = a.src + (size_t)img * hw * 3;
     const uint8_t* const send = a.src + (size_t)a.n * hw * 3;
     for (int base = 0; base < hw; base += PF_CHUNK_PX) {
@@ -148,11 +157,13 @@ __device__ __forceinline__ void pf_sweep(const PfArgs& a, int img, uint8_t* stag
     __syncthreads();
 }
 
+template <int PX>
 __global__ __launch_bounds__(PF_THREADS) void patch_filter_kernel(const PfArgs a) {
     extern __shared__ __align__(16) uint8_t pf_lds[];
+    constexpr int STAGE = PX == 3 ? PF_STAGE_BYTES : 0;                      // dword pixels are not staged
     uint8_t* const stage = pf_lds;
-    PfShared& sh = *(PfShared*)(pf_lds + PF_STAGE_BYTES);
-    uint32_t* const hist = (uint32_t*)(pf_lds + PF_STAGE_BYTES + sizeof(PfShared));
+    PfShared& sh = *(PfShared*)(pf_lds + STAGE);
+    uint32_t* const hist = (uint32_t*)(pf_lds + STAGE + sizeof(PfShared));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int img = blockIdx.x, hw = a.h * a.w;
 
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(PF_THREADS) void patch_filter_kernel(const PfArgs a
     {
         uint32_t* const my_bh = bh + (lane & (PF_BYTE_COPIES - 1)) * 768;
         uint32_t* const my_kh = kh + (lane & (PF_KEY_COPIES - 1)) * PF_KEY_BINS;
-        pf_sweep(a, img, stage, [&](int, int r, int g, int b) {
+        pf_sweep<PX>(a, img, stage, [&](int, int r, int g, int b) {
             atomicAdd(&my_bh[r], 1u);
             atomicAdd(&my_bh[256 + g], 1u);
             atomicAdd(&my_bh[512 + b], 1u);
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(PF_THREADS) void patch_filter_kernel(const PfArgs a
         const double step = (s_max - s_min) / 256.0;
         const double inv_step = s_const ? 0.0 : 256.0 / (s_max - s_min);
         uint32_t* const my_sh = shh + (lane & (PF_S_COPIES - 1)) * 256;
-        pf_sweep(a, img, stage, [&](int, int r, int g, int b) {
+        pf_sweep<PX>(a, img, stage, [&](int, int r, int g, int b) {
             if (!s_const) atomicAdd(&my_sh[pf_bin(pf_saturation(r, g, b), s_min, s_max, step, inv_step)], 1u);
             const uint32_t key = 2125u * r + 7154u * g + 721u * b;
             const uint32_t hi = key >> PF_KEY_LOW_BITS, low = key & (PF_KEY_BINS - 1);
@@ -274,7 +285,7 @@ __global__ __launch_bounds__(PF_THREADS) void patch_filter_kernel(const PfArgs a
     {
         const double thr_s = sh.thr_s;
         const int tr = sh.thr[0], tg = sh.thr[1], tb = sh.thr[2], lowest = a.rgb_min;
-        pf_sweep(a, img, stage, [&](int p, int r, int g, int b) {
+        pf_sweep<PX>(a, img, stage, [&](int p, int r, int g, int b) {
             const bool bright = r > tr && g > tg && b > tb;
             if (!bright && r > lowest && g > lowest && b > lowest && pf_saturation(r, g, b) > thr_s) {
                 const int y = p / a.w, x = p - y * a.w;
@@ -335,11 +346,11 @@ bool pf_shape_ok(const char* who, int n, int h, int w) {
     return true;
 }
 
-// stage | PfShared | the larger of the histograms (sweep 2: 4 KiB + 32 KiB) and the two bit masks
-size_t pf_lds_bytes(int h, int w) {
+// stage (3-byte pixels) | PfShared | the larger of the histograms (sweep 2: 4 KiB + 32 KiB) and the two bit masks
+size_t pf_lds_bytes(int h, int w, int px) {
     const size_t hists = (size_t)(PF_S_COPIES * 256 + 4 * PF_KEY_BINS) * 4;
     const size_t masks = 2 * (size_t)h * ((w + 31) / 32) * 4;
-    return PF_STAGE_BYTES + sizeof(PfShared) + (hists > masks ? hists : masks);
+    return (px == 3 ? PF_STAGE_BYTES : 0) + sizeof(PfShared) + (hists > masks ? hists : masks);
 }
 
 }  // namespace
@@ -353,12 +364,28 @@ extern "C" size_t sq_patch_filter_workspace_bytes(int n, int h, int w) {
     return sq_align_up((size_t)n * 8 * sizeof(double), 256);
 }
 
-extern "C" int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, int rgb_min, double background_threshold,
-                               double contrast_fraction, uint8_t* keep, double* stats, uint8_t* mask_raw, uint8_t* mask_dilated,
-                               void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+template <int PX>
+static int pf_launch(const PfArgs& a, size_t lds, hipStream_t st) {
+    static SqDevOnce attr;       // hipFuncSetAttribute is per device
+    if (attr.needed()) {
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)patch_filter_kernel<PX>, hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS_MAX));
+        attr.done();
+    }
+    hipLaunchKernelGGL(patch_filter_kernel<PX>, dim3((unsigned)a.n), dim3(PF_THREADS), lds, st, a);
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
+}
+
+extern "C" int sq_patch_filter_px(const uint8_t* patches_u8, int n, int h, int w, int pixel_bytes, int rgb_min,
+                                  double background_threshold, double contrast_fraction, uint8_t* keep, double* stats,
+                                  uint8_t* mask_raw, uint8_t* mask_dilated, void* workspace, size_t workspace_bytes,
+                                  sq_stream_t stream_) {
 #pragma clang fp contract(off)
     if (!pf_shape_ok("patch_filter", n, h, w)) return SQ_ERR_ARG;
+    SQ_REQUIRE(pixel_bytes == 3 || pixel_bytes == 4, "patch_filter: pixel_bytes = %d, must be 3 (RGB) or 4 (RGBA, the fourth byte ignored)",
+               pixel_bytes);
     SQ_REQUIRE(patches_u8 && keep, "patch_filter: null patches or keep pointer");
+    SQ_REQUIRE(pixel_bytes == 3 || ((uintptr_t)patches_u8 & 3) == 0, "patch_filter: pixel_bytes = 4 takes 4-byte aligned tiles");
     SQ_REQUIRE(((uintptr_t)stats & 7) == 0, "patch_filter: misaligned stats (doubles)");
     SQ_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "patch_filter: null or misaligned workspace (16 bytes)");
     const size_t need = sq_patch_filter_workspace_bytes(n, h, w);
@@ -373,13 +400,14 @@ extern "C" int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, i
     a.count_bound = background_threshold * (double)(h * w);
     a.fraction = contrast_fraction;
     a.pitch = (w + 31) / 32;
-    const size_t lds = pf_lds_bytes(h, w);
-    static SqDevOnce attr;       // hipFuncSetAttribute is per device
-    if (attr.needed()) {
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)patch_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS_MAX));
-        attr.done();
-    }
-    hipLaunchKernelGGL(patch_filter_kernel, dim3((unsigned)n), dim3(PF_THREADS), lds, (hipStream_t)stream_, a);
-    SQ_LAUNCH_CHECK();
-    return SQ_OK;
+    a.px = pixel_bytes;
+    const size_t lds = pf_lds_bytes(h, w, pixel_bytes);
+    return pixel_bytes == 3 ? pf_launch<3>(a, lds, (hipStream_t)stream_) : pf_launch<4>(a, lds, (hipStream_t)stream_);
+}
+
+extern "C" int sq_patch_filter(const uint8_t* patches_u8, int n, int h, int w, int rgb_min, double background_threshold,
+                               double contrast_fraction, uint8_t* keep, double* stats, uint8_t* mask_raw, uint8_t* mask_dilated,
+                               void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+    return sq_patch_filter_px(patches_u8, n, h, w, 3, rgb_min, background_threshold, contrast_fraction, keep, stats, mask_raw,
+                              mask_dilated, workspace, workspace_bytes, stream_);
 }

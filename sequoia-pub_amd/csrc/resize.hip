@@ -21,6 +21,9 @@
 // intermediate rows a dword (four byte lanes) at a time, one wave per output row with the row's coefficients in scalar
 // registers, and stores the output a dword per lane (256 contiguous bytes per wave instruction).  The intermediate image
 // never goes to HBM.  No matrix instructions: the kernel moves bytes and does 24-bit integer multiply-adds.
+// sq_resize_u8_gather puts a gather in front (image j is resized from src[index[j]]; an index out of range gives a zero image)
+// and takes 3- or 4-byte source pixels (RGBA, the fourth byte ignored: a staged pixel is then one aligned LDS dword per tap);
+// sq_resize_u8 is its call with 3-byte pixels and no index.  sq_pack_rgb_gather is the same gather without a resize.
 #include "../../include/sequoia_hip.h"
 #include "sq_common.h"
 
@@ -110,7 +113,9 @@ struct RsArgs {
     const uint8_t* src;
     uint8_t* dst;
     const int32_t* plan;
-    int n, h_in, w_in, h_out, w_out, ks_h, ks_v;
+    const int32_t* index;   // [n] source image of every output image, or null for the identity
+    int n, n_src;           // output images, source images
+    int h_in, w_in, h_out, w_out, ks_h, ks_v;
     int band, bands;        // output rows per block, blocks per image
     int rows_cap;           // intermediate rows the LDS image holds
     int group;              // input rows staged at a time
@@ -129,7 +134,7 @@ __device__ __forceinline__ uint32_t rs_mul(int k, uint32_t v) { return (uint32_t
 // row), o = its three bytes in the first intermediate row.  The two LDS regions are separate __restrict__ arguments so that the
 // reads of the next row may be issued before the byte stores of this one (both live in one LDS array, where the compiler has
 // to assume they overlap); two rows per trip.
-template <int KS>
+template <int KS, int PX>
 __device__ __forceinline__ void rs_hrows(const uint8_t* __restrict__ s, int s_pitch, uint8_t* __restrict__ o, int o_pitch, int rows,
                                          const int (&k)[KS > 0 ? KS : 1], const int32_t* __restrict__ kx, int nx) {
 #pragma unroll 2
@@ -138,16 +143,23 @@ __device__ __forceinline__ void rs_hrows(const uint8_t* __restrict__ s, int s_pi
         if constexpr (KS > 0) {
 #pragma unroll
             for (int i = 0; i < KS; ++i) {     // taps beyond nx: coefficient 0 on staged or padding bytes
-                c0 += rs_mul(k[i], s[3 * i]);
-                c1 += rs_mul(k[i], s[3 * i + 1]);
-                c2 += rs_mul(k[i], s[3 * i + 2]);
+                if constexpr (PX == 4) {       // the source is 4-byte aligned, so a staged pixel is an aligned dword
+                    const uint32_t v = *(const uint32_t*)(s + 4 * i);
+                    c0 += rs_mul(k[i], v & 255u);
+                    c1 += rs_mul(k[i], (v >> 8) & 255u);
+                    c2 += rs_mul(k[i], (v >> 16) & 255u);
+                } else {
+                    c0 += rs_mul(k[i], s[3 * i]);
+                    c1 += rs_mul(k[i], s[3 * i + 1]);
+                    c2 += rs_mul(k[i], s[3 * i + 2]);
+                }
             }
         } else {
             for (int i = 0; i < nx; ++i) {
                 const int kk = kx[i];
-                c0 += rs_mul(kk, s[3 * i]);
-                c1 += rs_mul(kk, s[3 * i + 1]);
-                c2 += rs_mul(kk, s[3 * i + 2]);
+                c0 += rs_mul(kk, s[PX * i]);
+                c1 += rs_mul(kk, s[PX * i + 1]);
+                c2 += rs_mul(kk, s[PX * i + 2]);
             }
         }
         o[0] = (uint8_t)rs_clip8(c0);
@@ -157,7 +169,8 @@ __device__ __forceinline__ void rs_hrows(const uint8_t* __restrict__ s, int s_pi
 }
 
 // KS > 0: ksize <= KS, coefficients in registers.  KS == 0: any ksize, coefficients read from the plan at every tap.
-template <int KS>
+// PX: bytes per source pixel, 3, or 4 with the fourth ignored; the output is always 3 bytes per pixel.
+template <int KS, int PX>
 __global__ __launch_bounds__(RS_THREADS) void resize_u8_kernel(const RsArgs a) {
     extern __shared__ __align__(16) uint8_t rs_lds[];
     uint8_t* const stage = rs_lds;
@@ -171,9 +184,16 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_kernel(const RsArgs a) {
     // input rows of the band; every table value is clamped before it addresses anything
     const int r0 = rs_clampi(vb[2 * y0], 0, a.h_in - 1);
     const int r1 = rs_clampi(vb[2 * (y1 - 1)] + vb[2 * (y1 - 1) + 1], r0 + 1, min(a.h_in, r0 + a.rows_cap));
-    const size_t iw3 = (size_t)a.w_in * 3, ow3 = (size_t)a.w_out * 3;
-    const uint8_t* const simg = a.src + (size_t)img * a.h_in * iw3;
-    const uint8_t* const send = a.src + (size_t)a.n * a.h_in * iw3;
+    const size_t iw3 = (size_t)a.w_in * PX, ow3 = (size_t)a.w_out * 3;      // bytes per input row, per output row
+    // the source image: an index outside [0, n_src) is compared before any address is formed from it and gives a zero tile
+    const int from = a.index ? a.index[img] : img;
+    if (from < 0 || from >= a.n_src) {
+        uint8_t* const z = a.dst + ((size_t)img * a.h_out + y0) * ow3;
+        for (size_t i = tid; i < (size_t)(y1 - y0) * ow3; i += RS_THREADS) z[i] = 0;
+        return;                                    // the whole block alike
+    }
+    const uint8_t* const simg = a.src + (size_t)from * a.h_in * iw3;
+    const uint8_t* const send = a.src + (size_t)a.n_src * a.h_in * iw3;
 
     // ---- horizontal pass: input rows [r0, r1) -> inter[r - r0][w_out * 3]
     for (int g0 = r0; g0 < r1; g0 += a.group) {
@@ -206,7 +226,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_kernel(const RsArgs a) {
 #pragma unroll
                 for (int i = 0; i < KS; ++i) k[i] = i < nx ? kx[i] : 0;
             }
-            rs_hrows<KS>(stage + skew + (size_t)xmin * 3, (int)iw3, inter + (size_t)(g0 - r0) * a.pitch + x * 3, a.pitch, g1 - g0, k, kx, nx);
+            rs_hrows<KS, PX>(stage + skew + (size_t)xmin * PX, (int)iw3, inter + (size_t)(g0 - r0) * a.pitch + x * 3, a.pitch, g1 - g0, k, kx, nx);
         }
     }
     __syncthreads();
@@ -261,8 +281,8 @@ __global__ __launch_bounds__(RS_THREADS) void resize_u8_kernel(const RsArgs a) {
 // 0.184 ms with 16 (22 KB, 7 blocks); 512 -> 256 bicubic 0.985 ms with 16 rows (42 KB), 0.92 ms with 8 (26 KB), 1.02 ms with 4.
 // A band of R rows covers at most (R - 1) scale + 2 support + 1 input rows (first window start to last window end), one
 // more for the truncations.
-bool rs_geometry(int h_in, int w_in, int h_out, int w_out, int filter, RsArgs* a, size_t* lds) {
-    const size_t iw3 = (size_t)w_in * 3;
+bool rs_geometry(int h_in, int w_in, int h_out, int w_out, int filter, int px, RsArgs* a, size_t* lds) {
+    const size_t iw3 = (size_t)w_in * px;
     a->pitch = (int)sq_align_up((size_t)w_out * 3, 4);
     a->group = (int)(8192 / iw3 < 1 ? 1 : 8192 / iw3 > 8 ? 8 : 8192 / iw3);
     a->stage_bytes = (int)sq_align_up((size_t)a->group * iw3 + 15 + 15 + RS_TAP_PAD, 16);
@@ -288,14 +308,14 @@ bool rs_geometry(int h_in, int w_in, int h_out, int w_out, int filter, RsArgs* a
     return false;
 }
 
-template <int KS>
+template <int KS, int PX>
 int rs_launch(const RsArgs& a, size_t lds, hipStream_t st) {
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
-        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)resize_u8_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_MAX));
+        SQ_HIP_CHECK(hipFuncSetAttribute((const void*)resize_u8_kernel<KS, PX>, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_MAX));
         attr.done();
     }
-    hipLaunchKernelGGL(resize_u8_kernel<KS>, dim3((unsigned)(a.n * a.bands)), dim3(RS_THREADS), lds, st, a);
+    hipLaunchKernelGGL((resize_u8_kernel<KS, PX>), dim3((unsigned)(a.n * a.bands)), dim3(RS_THREADS), lds, st, a);
     SQ_LAUNCH_CHECK();
     return SQ_OK;
 }
@@ -325,27 +345,144 @@ extern "C" int sq_resize_plan_init(int h_in, int w_in, int h_out, int w_out, int
     return SQ_OK;
 }
 
-extern "C" int sq_resize_u8(const uint8_t* src_u8, int n, int h_in, int w_in, uint8_t* dst_u8, int h_out, int w_out, int filter,
-                            const int32_t* plan_dev, sq_stream_t stream_) {
+namespace {
+
+constexpr int PK_THREADS = 256;
+
+struct PkArgs {
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* index;   // [m] or null for the identity
+    int n_src, hw;          // source tiles, pixels per tile
+    int quads, blocks;      // groups of four pixels per tile (the last may be short), blocks per tile
+};
+
+// dst[j] = the RGB bytes of src[index[j]]: a thread takes four pixels, 12 output bytes.  Where the tile's first byte is
+// dword-aligned on either side the quad is loaded / stored as dwords (16 bytes at once where an RGBA tile starts on 16), else
+// by the byte; the short last quad of a tile always goes by the byte.
+template <int PX>
+__global__ __launch_bounds__(PK_THREADS) void pack_rgb_kernel(const PkArgs a) {
+    const int j = blockIdx.x / a.blocks, q = (blockIdx.x % a.blocks) * PK_THREADS + threadIdx.x;
+    if (q >= a.quads) return;
+    const int px0 = q * 4, npx = min(4, a.hw - px0);
+    uint8_t* const o = a.dst + (size_t)j * a.hw * 3 + (size_t)px0 * 3;
+    const bool out_dwords = npx == 4 && ((uintptr_t)o & 3) == 0;
+    // the source tile: an index outside [0, n_src) is compared before any address is formed from it and gives a zero tile
+    const int from = a.index ? a.index[j] : j;
+    uint32_t w0 = 0u, w1 = 0u, w2 = 0u;            // the quad's 12 output bytes, little-endian
+    if (from >= 0 && from < a.n_src) {
+        const uint8_t* const s = a.src + ((size_t)from * a.hw + px0) * PX;
+        if (npx < 4) {
+            for (int i = 0; i < npx; ++i)
+                for (int c = 0; c < 3; ++c) o[3 * i + c] = s[PX * i + c];
+            return;
+        }
+        if constexpr (PX == 4) {                   // s is 4-byte aligned: the tile base is, and a pixel is 4 bytes
+            uint32_t v0, v1, v2, v3;
+            if (((uintptr_t)s & 15) == 0) {
+                const u32x4 v = *(const u32x4*)s;
+                v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3];
+            } else {
+                const uint32_t* const p = (const uint32_t*)s;
+                v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
+            }
+            v0 &= 0xffffffu, v1 &= 0xffffffu, v2 &= 0xffffffu, v3 &= 0xffffffu;
+            w0 = v0 | v1 << 24, w1 = v1 >> 8 | v2 << 16, w2 = v2 >> 16 | v3 << 8;
+        } else if (((uintptr_t)s & 3) == 0) {
+            const uint32_t* const p = (const uint32_t*)s;
+            w0 = p[0], w1 = p[1], w2 = p[2];
+        } else {
+            for (int b = 0; b < 4; ++b) {
+                w0 |= (uint32_t)s[b] << (8 * b);
+                w1 |= (uint32_t)s[4 + b] << (8 * b);
+                w2 |= (uint32_t)s[8 + b] << (8 * b);
+            }
+        }
+    } else if (npx < 4) {
+        for (int i = 0; i < 3 * npx; ++i) o[i] = 0;
+        return;
+    }
+    if (out_dwords) {
+        uint32_t* const p = (uint32_t*)o;
+        p[0] = w0, p[1] = w1, p[2] = w2;
+    } else {
+        for (int b = 0; b < 4; ++b) {
+            o[b] = (uint8_t)(w0 >> (8 * b));
+            o[4 + b] = (uint8_t)(w1 >> (8 * b));
+            o[8 + b] = (uint8_t)(w2 >> (8 * b));
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int sq_pack_rgb_gather(const uint8_t* src_u8, int n_src, int pixel_bytes, const int32_t* index, int m, int h, int w,
+                                  uint8_t* dst_u8, sq_stream_t stream_) {
+    SQ_REQUIRE(pixel_bytes == 3 || pixel_bytes == 4, "pack_rgb: pixel_bytes = %d, must be 3 (RGB) or 4 (RGBA, the fourth byte ignored)",
+               pixel_bytes);
+    SQ_REQUIRE(h >= 1 && h <= SQ_RESIZE_MAX_DIM && w >= 1 && w <= SQ_RESIZE_MAX_DIM, "pack_rgb: tiles of %d x %d: every extent must be in 1..%d",
+               h, w, SQ_RESIZE_MAX_DIM);
+    SQ_REQUIRE(m >= 0 && n_src >= 0, "pack_rgb: m = %d output tiles from n_src = %d", m, n_src);
+    SQ_REQUIRE(index || m == n_src, "pack_rgb: a null index is the identity and takes m = n_src, got m = %d, n_src = %d", m, n_src);
+    SQ_REQUIRE(((uintptr_t)index & 3) == 0, "pack_rgb: misaligned index (int32)");
+    if (m == 0) return SQ_OK;
+    SQ_REQUIRE(n_src >= 1, "pack_rgb: n_src = %d source tiles for m = %d output tiles", n_src, m);
+    SQ_REQUIRE(src_u8 && dst_u8, "pack_rgb: null tile pointer");
+    SQ_REQUIRE(pixel_bytes == 3 || ((uintptr_t)src_u8 & 3) == 0, "pack_rgb: pixel_bytes = 4 takes 4-byte aligned tiles");
+    PkArgs a;
+    a.src = src_u8; a.dst = dst_u8; a.index = index; a.n_src = n_src;
+    a.hw = h * w;                                  // <= 2^28
+    a.quads = (a.hw + 3) / 4;
+    a.blocks = (a.quads + PK_THREADS - 1) / PK_THREADS;
+    SQ_REQUIRE((size_t)m * a.blocks <= 0x7fffffffu, "pack_rgb: %d tiles x %d blocks exceed the grid", m, a.blocks);
+    const dim3 grid((unsigned)((size_t)m * a.blocks));
+    if (pixel_bytes == 3) hipLaunchKernelGGL(pack_rgb_kernel<3>, grid, dim3(PK_THREADS), 0, (hipStream_t)stream_, a);
+    else hipLaunchKernelGGL(pack_rgb_kernel<4>, grid, dim3(PK_THREADS), 0, (hipStream_t)stream_, a);
+    SQ_LAUNCH_CHECK();
+    return SQ_OK;
+}
+
+extern "C" int sq_resize_u8_gather(const uint8_t* src_u8, int n_src, int pixel_bytes, const int32_t* index, int m, int h_in, int w_in,
+                                   uint8_t* dst_u8, int h_out, int w_out, int filter, const int32_t* plan_dev, sq_stream_t stream_) {
     if (!rs_sizes_ok("resize_u8", h_in, w_in, h_out, w_out, filter)) return SQ_ERR_ARG;
-    SQ_REQUIRE(src_u8 && dst_u8, "resize_u8: null image pointer");
+    SQ_REQUIRE(pixel_bytes == 3 || pixel_bytes == 4, "resize_u8: pixel_bytes = %d, must be 3 (RGB) or 4 (RGBA, the fourth byte ignored)",
+               pixel_bytes);
+    SQ_REQUIRE(m >= 0 && n_src >= 0, "resize_u8: m = %d output images from n_src = %d", m, n_src);
+    SQ_REQUIRE(index || m == n_src, "resize_u8: a null index is the identity and takes m = n_src, got m = %d, n_src = %d", m, n_src);
+    SQ_REQUIRE(((uintptr_t)index & 3) == 0, "resize_u8: misaligned index (int32)");
     SQ_REQUIRE(plan_dev && ((uintptr_t)plan_dev & 3) == 0, "resize_u8: null or misaligned plan (upload what sq_resize_plan_init filled)");
-    SQ_REQUIRE(n >= 1, "resize_u8: n = %d images", n);
+    if (m == 0) return SQ_OK;
+    SQ_REQUIRE(n_src >= 1, "resize_u8: n_src = %d source images for m = %d output images", n_src, m);
+    SQ_REQUIRE(src_u8 && dst_u8, "resize_u8: null image pointer");
+    SQ_REQUIRE(pixel_bytes == 3 || ((uintptr_t)src_u8 & 3) == 0, "resize_u8: pixel_bytes = 4 takes 4-byte aligned images");
     RsArgs a;
-    a.src = src_u8; a.dst = dst_u8; a.plan = plan_dev;
-    a.n = n; a.h_in = h_in; a.w_in = w_in; a.h_out = h_out; a.w_out = w_out;
+    a.src = src_u8; a.dst = dst_u8; a.plan = plan_dev; a.index = index;
+    a.n = m; a.n_src = n_src; a.h_in = h_in; a.w_in = w_in; a.h_out = h_out; a.w_out = w_out;
     a.ks_h = rs_ksize(w_in, w_out, filter);
     a.ks_v = rs_ksize(h_in, h_out, filter);
     size_t lds = 0;
-    if (!rs_geometry(h_in, w_in, h_out, w_out, filter, &a, &lds)) {
+    if (!rs_geometry(h_in, w_in, h_out, w_out, filter, pixel_bytes, &a, &lds)) {
         sq_set_error("resize_u8: %d x %d -> %d x %d: one output row's band needs %zu bytes of LDS, a CU has %d", h_in, w_in, h_out, w_out,
                      lds, RS_LDS_MAX);
         return SQ_ERR_UNSUPPORTED;
     }
-    SQ_REQUIRE((size_t)n * a.bands <= 0x7fffffffu, "resize_u8: %d images x %d bands exceed the grid", n, a.bands);
+    SQ_REQUIRE((size_t)m * a.bands <= 0x7fffffffu, "resize_u8: %d images x %d bands exceed the grid", m, a.bands);
     const int ks = a.ks_h > a.ks_v ? a.ks_h : a.ks_v;
     hipStream_t st = (hipStream_t)stream_;
-    if (ks <= 5) return rs_launch<5>(a, lds, st);       // bilinear down to 1/2, bicubic up
-    if (ks <= 9) return rs_launch<9>(a, lds, st);       // bicubic down to 1/2, bilinear down to 1/4
-    return rs_launch<0>(a, lds, st);
+    if (pixel_bytes == 3) {
+        if (ks <= 5) return rs_launch<5, 3>(a, lds, st);       // bilinear down to 1/2, bicubic up
+        if (ks <= 9) return rs_launch<9, 3>(a, lds, st);       // bicubic down to 1/2, bilinear down to 1/4
+        return rs_launch<0, 3>(a, lds, st);
+    }
+    if (ks <= 5) return rs_launch<5, 4>(a, lds, st);
+    if (ks <= 9) return rs_launch<9, 4>(a, lds, st);
+    return rs_launch<0, 4>(a, lds, st);
+}
+
+extern "C" int sq_resize_u8(const uint8_t* src_u8, int n, int h_in, int w_in, uint8_t* dst_u8, int h_out, int w_out, int filter,
+                            const int32_t* plan_dev, sq_stream_t stream_) {
+    if (!rs_sizes_ok("resize_u8", h_in, w_in, h_out, w_out, filter)) return SQ_ERR_ARG;
+    SQ_REQUIRE(src_u8 && dst_u8, "resize_u8: null image pointer");
+    SQ_REQUIRE(n >= 1, "resize_u8: n = %d images", n);
+    return sq_resize_u8_gather(src_u8, n, 3, nullptr, n, h_in, w_in, dst_u8, h_out, w_out, filter, plan_dev, stream_);
 }

@@ -17,7 +17,8 @@
 // min and max of s are integer atomics on the bit patterns of the non-negative doubles.  No floating-point sum crosses a
 // workgroup, so two runs give the same bytes.  With h w <= 2^30 every count fits 32 bits and counts x centre sums stay
 // below 2^53.  s is recomputed in every sweep (one double division per pixel) rather than stored: 8 bytes per pixel of
-// traffic against 3.
+// traffic against 3.  With pixel_bytes = 4 (sq_slide_mask_px: the RGBA image a slide reader returns, the fourth byte ignored)
+// the three sweeps load aligned dwords from global memory instead of staging 3-byte pixels; everything behind the load is the same.
 #include "../../include/sequoia_hip.h"
 #include "sq_common.h"
 #include "patchfilter.h"
@@ -57,16 +58,27 @@ struct SmArgs {
     int h, w, rgb_min, iterations, transpose;
     int pitch;               // 32-bit words per mask row
     int hw;
+    int px;                  // bytes per pixel: 3, or 4 with the fourth ignored
 };
 
 __device__ __forceinline__ double sm_s_min(const SmHead* hd) { return __longlong_as_double((long long)~hd->s_min_inv); }
 __device__ __forceinline__ double sm_s_max(const SmHead* hd) { return __longlong_as_double((long long)hd->s_max_bits); }
 
-// f(r, g, b) for every pixel of the image: workgroup b takes the chunks b, b + gridDim.x, ...
-template <typename F>
+// f(r, g, b) for every pixel of the image: workgroup b takes the chunks b, b + gridDim.x, ...  3-byte pixels are staged in
+// LDS, 4-byte pixels (the image 4-byte aligned) are loaded as dwords.
+template <int PX, typename F>
 __device__ __forceinline__ void sm_sweep(const SmArgs& a, uint8_t* stage, F&& f) {
     const uint8_t* const send = a.src + (size_t)a.hw * 3;
     const int chunks = (a.hw + PF_CHUNK_PX - 1) / PF_CHUNK_PX;
+    if constexpr (PX == 4) {
+        __syncthreads();                       // what the caller cleared is cleared before the first f
+        for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
+            const int base = c * PF_CHUNK_PX, npx = min(PF_CHUNK_PX, a.hw - base);
+            pf_pixels4<SM_THREADS>(a.src + (size_t)base * 4, npx, [&](int, int r, int g, int b) { f(r, g, b); });
+        }
+        __syncthreads();
+        return;
+    }
     for (int c = blockIdx.x; c < chunks; c += gridDim.x) {
         const int base = c * PF_CHUNK_PX, npx = min(PF_CHUNK_PX, a.hw - base);
         const uint8_t* const s = stage + pf_stage<SM_THREADS>(a.src, send, a.src + (size_t)base * 3, npx, stage);
@@ -75,15 +87,16 @@ __device__ __forceinline__ void sm_sweep(const SmArgs& a, uint8_t* stage, F&& f)
     __syncthreads();
 }
 
+template <int PX>
 __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep1_kernel(const SmArgs a) {
-    __shared__ __align__(16) uint8_t stage[PF_STAGE_BYTES];
+    __shared__ __align__(16) uint8_t stage[PX == 3 ? PF_STAGE_BYTES : 16];
     __shared__ uint32_t bh[SM_BYTE_COPIES * 768];
     __shared__ double wave_min[SM_WAVES], wave_max[SM_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < SM_BYTE_COPIES * 768; i += SM_THREADS) bh[i] = 0u;
     double s_lo = 2.0, s_hi = 0.0;
     uint32_t* const my_bh = bh + (lane & (SM_BYTE_COPIES - 1)) * 768;
-    sm_sweep(a, stage, [&](int r, int g, int b) {          // its first barrier orders the clearing before the adds
+    sm_sweep<PX>(a, stage, [&](int r, int g, int b) {          // its first barrier orders the clearing before the adds
         atomicAdd(&my_bh[r], 1u);
         atomicAdd(&my_bh[256 + g], 1u);
         atomicAdd(&my_bh[512 + b], 1u);
@@ -112,9 +125,10 @@ __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep1_kernel(const SmA
     }
 }
 
+template <int PX>
 __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep2_kernel(const SmArgs a) {
 #pragma clang fp contract(off)
-    __shared__ __align__(16) uint8_t stage[PF_STAGE_BYTES];
+    __shared__ __align__(16) uint8_t stage[PX == 3 ? PF_STAGE_BYTES : 16];
     __shared__ uint32_t shh[SM_S_COPIES * 256];
     const int tid = threadIdx.x, lane = tid & 63;
     const double s_min = sm_s_min(a.head), s_max = sm_s_max(a.head);
@@ -123,7 +137,7 @@ __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep2_kernel(const SmA
     const double step = (s_max - s_min) / 256.0;
     const double inv_step = 256.0 / (s_max - s_min);
     uint32_t* const my_sh = shh + (lane & (SM_S_COPIES - 1)) * 256;
-    sm_sweep(a, stage, [&](int r, int g, int b) { atomicAdd(&my_sh[pf_bin(pf_saturation(r, g, b), s_min, s_max, step, inv_step)], 1u); });
+    sm_sweep<PX>(a, stage, [&](int r, int g, int b) { atomicAdd(&my_sh[pf_bin(pf_saturation(r, g, b), s_min, s_max, step, inv_step)], 1u); });
     for (int i = tid; i < 256; i += SM_THREADS) {
         uint32_t c = 0;
         for (int q = 0; q < SM_S_COPIES; ++q) c += shh[q * 256 + i];
@@ -149,8 +163,9 @@ __global__ __launch_bounds__(256) void slide_mask_otsu_kernel(const SmArgs a) {
 }
 
 // mask bits: a piece is up to 4096 pixels of one row from a multiple of 4096 on
+template <int PX>
 __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep3_kernel(const SmArgs a) {
-    __shared__ __align__(16) uint8_t stage[PF_STAGE_BYTES];
+    __shared__ __align__(16) uint8_t stage[PX == 3 ? PF_STAGE_BYTES : 16];
     __shared__ uint32_t wave_count[SM_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint8_t* const send = a.src + (size_t)a.hw * 3;
@@ -162,13 +177,21 @@ __global__ __launch_bounds__(SM_THREADS) void slide_mask_sweep3_kernel(const SmA
     for (long long pc = blockIdx.x; pc < pieces; pc += gridDim.x) {
         const int y = (int)(pc / per_row), x0 = (int)(pc - (long long)y * per_row) * PF_CHUNK_PX;
         const int npx = min(PF_CHUNK_PX, a.w - x0);
-        const uint8_t* const s = stage + pf_stage<SM_THREADS>(a.src, send, a.src + ((size_t)y * a.w + x0) * 3, npx, stage);
+        const uint8_t* s = stage;
+        const uint32_t* const px = (const uint32_t*)(a.src + ((size_t)y * a.w + x0) * 4);      // PX == 4: the piece's dwords
+        if constexpr (PX == 3) s += pf_stage<SM_THREADS>(a.src, send, a.src + ((size_t)y * a.w + x0) * 3, npx, stage);
         uint32_t* const row = a.bits + (size_t)y * a.pitch;
         for (int i0 = wave * 64; i0 < npx; i0 += SM_THREADS) {             // whole waves: the ballot needs every lane
             const int i = i0 + lane;
             bool on = false;
             if (i < npx) {
-                const int r = s[3 * i], g = s[3 * i + 1], b = s[3 * i + 2];
+                int r, g, b;
+                if constexpr (PX == 3) {
+                    r = s[3 * i], g = s[3 * i + 1], b = s[3 * i + 2];
+                } else {
+                    const uint32_t v = px[i];
+                    r = (int)(v & 255u), g = (int)((v >> 8) & 255u), b = (int)((v >> 16) & 255u);
+                }
                 const bool bright = r > tr && g > tg && b > tb;
                 on = !bright && r > lowest && g > lowest && b > lowest && pf_saturation(r, g, b) > thr_s;
             }
@@ -294,10 +317,22 @@ extern "C" size_t sq_slide_mask_workspace_bytes(int h, int w) {
     return SM_HEAD_BYTES + sq_align_up((size_t)h * ((w + 31) / 32) * sizeof(uint32_t), 256);
 }
 
-extern "C" int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, int iterations, int transpose, uint8_t* mask_raw,
-                             uint8_t* mask_closed, double* stats, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+template <int PX>
+static void sm_launch_sweeps(const SmArgs& a, unsigned sweep_grid, unsigned piece_grid, hipStream_t stream) {
+    hipLaunchKernelGGL(slide_mask_sweep1_kernel<PX>, dim3(sweep_grid), dim3(SM_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(slide_mask_sweep2_kernel<PX>, dim3(sweep_grid), dim3(SM_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(slide_mask_otsu_kernel, dim3(1), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(slide_mask_sweep3_kernel<PX>, dim3(piece_grid), dim3(SM_THREADS), 0, stream, a);
+}
+
+extern "C" int sq_slide_mask_px(const uint8_t* img_u8, int h, int w, int pixel_bytes, int rgb_min, int iterations, int transpose,
+                                uint8_t* mask_raw, uint8_t* mask_closed, double* stats, void* workspace, size_t workspace_bytes,
+                                sq_stream_t stream_) {
     if (!sm_shape_ok("slide_mask", h, w)) return SQ_ERR_ARG;
+    SQ_REQUIRE(pixel_bytes == 3 || pixel_bytes == 4, "slide_mask: pixel_bytes = %d, must be 3 (RGB) or 4 (RGBA, the fourth byte ignored)",
+               pixel_bytes);
     SQ_REQUIRE(img_u8 && mask_closed, "slide_mask: null image or mask_closed pointer");
+    SQ_REQUIRE(pixel_bytes == 3 || ((uintptr_t)img_u8 & 3) == 0, "slide_mask: pixel_bytes = 4 takes a 4-byte aligned image");
     SQ_REQUIRE(iterations >= 0 && iterations <= SQ_SLIDE_MASK_MAX_ITERATIONS, "slide_mask: iterations = %d, must be in 0..%d", iterations,
                SQ_SLIDE_MASK_MAX_ITERATIONS);
     SQ_REQUIRE(((uintptr_t)stats & 7) == 0, "slide_mask: misaligned stats (doubles)");
@@ -312,18 +347,23 @@ extern "C" int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, i
     a.src = img_u8; a.head = (SmHead*)workspace; a.bits = (uint32_t*)((uint8_t*)workspace + SM_HEAD_BYTES);
     a.mask_raw = mask_raw; a.mask_closed = mask_closed; a.stats = stats;
     a.h = h; a.w = w; a.rgb_min = rgb_min; a.iterations = iterations; a.transpose = transpose != 0;
-    a.pitch = (w + 31) / 32; a.hw = h * w;
+    a.pitch = (w + 31) / 32; a.hw = h * w; a.px = pixel_bytes;
     SQ_HIP_CHECK(hipMemsetAsync(workspace, 0, SM_HEAD_BYTES, stream));
     const int chunks = (a.hw + PF_CHUNK_PX - 1) / PF_CHUNK_PX;
     const unsigned sweep_grid = (unsigned)(chunks < SM_MAX_BLOCKS ? chunks : SM_MAX_BLOCKS);
-    hipLaunchKernelGGL(slide_mask_sweep1_kernel, dim3(sweep_grid), dim3(SM_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(slide_mask_sweep2_kernel, dim3(sweep_grid), dim3(SM_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(slide_mask_otsu_kernel, dim3(1), dim3(256), 0, stream, a);
     const long long pieces = (long long)h * ((w + PF_CHUNK_PX - 1) / PF_CHUNK_PX);
-    hipLaunchKernelGGL(slide_mask_sweep3_kernel, dim3((unsigned)(pieces < SM_MAX_BLOCKS ? pieces : SM_MAX_BLOCKS)), dim3(SM_THREADS), 0, stream, a);
+    const unsigned piece_grid = (unsigned)(pieces < SM_MAX_BLOCKS ? pieces : SM_MAX_BLOCKS);
+    if (pixel_bytes == 3) sm_launch_sweeps<3>(a, sweep_grid, piece_grid, stream);
+    else sm_launch_sweeps<4>(a, sweep_grid, piece_grid, stream);
     const dim3 tiles((unsigned)((w + SM_TILE_COLS - 1) / SM_TILE_COLS), (unsigned)((h + SM_TILE_ROWS - 1) / SM_TILE_ROWS));
     hipLaunchKernelGGL(slide_mask_close_kernel, tiles, dim3(SM_CLOSE_THREADS), 0, stream, a);
     if (stats) hipLaunchKernelGGL(slide_mask_finish_kernel, dim3(1), dim3(64), 0, stream, a);
     SQ_LAUNCH_CHECK();
     return SQ_OK;
+}
+
+extern "C" int sq_slide_mask(const uint8_t* img_u8, int h, int w, int rgb_min, int iterations, int transpose, uint8_t* mask_raw,
+                             uint8_t* mask_closed, double* stats, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+    return sq_slide_mask_px(img_u8, h, w, 3, rgb_min, iterations, transpose, mask_raw, mask_closed, stats, workspace, workspace_bytes,
+                            stream_);
 }

@@ -54,10 +54,63 @@ def _device_plan(h_in, w_in, h_out, w_out, flt, dev):
     return hit
 
 
-def resize_u8_pil(patches_u8, size, resample="bilinear"):
+def _gather_args(who, x, index):
+    """The checks the gather entries share: ``x`` uint8 [n, H, W, 3 or 4] on the device, ``index`` None or an int32 [m]
+    tensor on the same device.  Returns (x contiguous, index contiguous or None, m)."""
+    if torch.is_tensor(x) and (x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] not in (3, 4)):      # refused without a GPU too
+        raise ValueError(f"{who} takes uint8 [n, H, W, 3 or 4], got {x.dtype} {tuple(x.shape)}")
+    _lib.require_gpu()
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.SequoiaHipError(f"{who} needs a CUDA tensor (no CPU fallback)")
+    if index is None:
+        return x.contiguous(), None, x.shape[0]
+    if not (torch.is_tensor(index) and index.is_cuda and index.device == x.device):
+        raise _lib.SequoiaHipError(f"{who}: index must be a tensor on the device of the tiles")
+    if index.dtype != torch.int32 or index.dim() != 1:
+        raise ValueError(f"{who}: index must be int32 [m], got {index.dtype} {tuple(index.shape)}")
+    return x.contiguous(), index.contiguous(), index.shape[0]
+
+
+def resize_u8_pil(patches_u8, size, resample="bilinear", index=None):
     """uint8 [n, H, W, 3] CUDA tensor -> uint8 [n, h, w, 3], every byte equal to
     ``PIL.Image.fromarray(patch).resize((w, h), resample)``.  ``size``: an int (a square output, what ``Resize(224)`` gives a
-    square patch) or ``(h, w)``; ``resample``: "bilinear" or "bicubic".  Asynchronous on the current stream; no CPU fallback."""
+    square patch) or ``(h, w)``; ``resample``: "bilinear" or "bicubic".  A fourth channel (RGBA as a slide reader returns it)
+    is ignored: the result is that of ``patches_u8[..., :3]``.  ``index``: an int32 [m] tensor on the same device; the
+    result is then [m, h, w, 3], row j the resize of ``patches_u8[index[j]]`` (``sq_resize_u8_gather``: no gathered copy is
+    made); an index outside [0, n) gives a zero image.  Asynchronous on the current stream; no CPU fallback."""
+    if index is None and torch.is_tensor(patches_u8) and patches_u8.dim() == 4 and patches_u8.shape[3] == 3:
+        return _resize_rgb(patches_u8, size, resample)
+    x, idx, m = _gather_args("resize_u8_pil", patches_u8, index)
+    h, w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    flt = _filter_id(resample)
+    n, H, W, C = x.shape
+    dev = x.device
+    plan = _device_plan(H, W, h, w, flt, dev)          # refuses a bad size with the library's message before anything is allocated
+    out = torch.empty(m, h, w, 3, dtype=torch.uint8, device=dev)
+    if m == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().sq_resize_u8_gather(_lib.ptr(x), n, C, _lib.ptr(idx), m, H, W, _lib.ptr(out), h, w, flt, _lib.ptr(plan),
+                                                  _lib.stream_ptr(dev)))
+    return out
+
+
+def pack_rgb(tiles_u8, index=None):
+    """uint8 [n, H, W, 3 or 4] CUDA tensor -> dense uint8 [m, H, W, 3]: row j is ``tiles_u8[index[j]][..., :3]``
+    (``sq_pack_rgb_gather``); ``index`` an int32 [m] tensor on the same device, None for all tiles in order.  An index outside
+    [0, n) gives a zero tile.  Asynchronous on the current stream; no CPU fallback."""
+    x, idx, m = _gather_args("pack_rgb", tiles_u8, index)
+    n, H, W, C = x.shape
+    out = torch.empty(m, H, W, 3, dtype=torch.uint8, device=x.device)
+    if m == 0:
+        return out
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().sq_pack_rgb_gather(_lib.ptr(x), n, C, _lib.ptr(idx), m, H, W, _lib.ptr(out), _lib.stream_ptr(x.device)))
+    return out
+
+
+def _resize_rgb(patches_u8, size, resample):
+    """resize_u8_pil for three channels and no index: ``sq_resize_u8``."""
     _lib.require_gpu()
     if not (torch.is_tensor(patches_u8) and patches_u8.is_cuda):
         raise _lib.SequoiaHipError("resize_u8_pil needs a CUDA tensor (no CPU fallback)")

@@ -13,6 +13,10 @@ level and the closing: seconds per slide in numpy / scipy on one core) has a dev
 (``sq_slide_mask``, csrc/slidemask.hip) and ``extract_patches(..., device=..., slide_mask="device")``, every mask bit and
 the bytes of ``mask.npy`` the host's (tools/slide_mask_rate.py, profiles/slide_mask_rate.txt).  With both, what is left of
 the stage is reading the regions; slide decoding itself has not been measured, openslide is absent.
+The device forms take RGBA as OpenSlide's ``read_region`` returns it (the kernels skip the fourth byte, so the host copies a
+region whole instead of repacking it: 4.3 against 171 us per 256 x 256 region, profiles/region_path_rate.txt), and
+``embed_slide`` runs the same walk with the kept tiles staying on the device -- order, ``random.sample`` cut, extractor and
+k-Means as the patch file, cli.compute_features and cli.kmean_features would have them -- so that no patch store is written.
 What is restated here are the scikit-image functions the reference calls (scikit-image is not installed in this image):
 ``rgb2hsv`` (saturation channel), ``threshold_otsu`` (integer and float histograms), ``is_low_contrast`` -- pinned
 against scikit-image 0.18.3 itself by tests/golden/patchgen.npz (made with the image's conda interpreter,
@@ -135,20 +139,21 @@ def _resize_like_reference(patch, size):
 
 def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_threshold=0.05, return_stats=False,
                    return_masks=False):
-    """The per-tile filter of extract_patches (patch_gen_hdf5.py:110-115) for a uint8 [n, H, W, 3] CUDA tensor, 8 <= H, W <=
-    512: bool [n], True where ``binary_dilation(get_mask_image(tile, rgb_min), iterations=3).sum() > background_threshold *
+    """The per-tile filter of extract_patches (patch_gen_hdf5.py:110-115) for a uint8 [n, H, W, 3] CUDA tensor (or
+    [n, H, W, 4]: RGBA as a slide reader returns it, the fourth channel ignored, every result that of the RGB values), 8 <= H,
+    W <= 512: bool [n], True where ``binary_dilation(get_mask_image(tile, rgb_min), iterations=3).sum() > background_threshold *
     H * W and not is_low_contrast(tile, fraction_threshold)``.  ``return_stats``: also float64 [n, 8] = thr_R, thr_G, thr_B,
     thr_S, mask count, dilated count, contrast ratio, 0 -- thresholds and counts equal to the host functions' bit for bit,
     the ratio to 1e-12 (include/sequoia_hip.h).  ``return_masks``: also the bool [n, H, W] masks before and after the
     dilation.  Asynchronous on the current stream; no CPU fallback."""
     import torch
+    if torch.is_tensor(patches_u8) and (patches_u8.dtype != torch.uint8 or patches_u8.dim() != 4 or patches_u8.shape[3] not in (3, 4)):
+        raise ValueError(f"filter_patches takes uint8 [n, H, W, 3 or 4], got {patches_u8.dtype} {tuple(patches_u8.shape)}")
     _lib.require_gpu()
     if not (torch.is_tensor(patches_u8) and patches_u8.is_cuda):
         raise _lib.SequoiaHipError("filter_patches needs a CUDA tensor (no CPU fallback)")
-    if patches_u8.dtype != torch.uint8 or patches_u8.dim() != 4 or patches_u8.shape[3] != 3:
-        raise ValueError(f"filter_patches takes uint8 [n, H, W, 3], got {patches_u8.dtype} {tuple(patches_u8.shape)}")
     x = patches_u8.contiguous()
-    n, H, W, _ = x.shape
+    n, H, W, C = x.shape
     dev = x.device
     L = _lib.lib()
     need = L.sq_patch_filter_workspace_bytes(max(n, 1), H, W)       # refuses a bad size with the library's message
@@ -161,9 +166,9 @@ def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_th
     if n:
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.sq_patch_filter(_lib.ptr(x), n, H, W, int(rgb_min), float(background_threshold), float(fraction_threshold),
-                                         _lib.ptr(keep), _lib.ptr(stats), _lib.ptr(raw), _lib.ptr(dil), _lib.ptr(ws), need,
-                                         _lib.stream_ptr(dev)))
+            _lib.check(L.sq_patch_filter_px(_lib.ptr(x), n, H, W, C, int(rgb_min), float(background_threshold), float(fraction_threshold),
+                                            _lib.ptr(keep), _lib.ptr(stats), _lib.ptr(raw), _lib.ptr(dil), _lib.ptr(ws), need,
+                                            _lib.stream_ptr(dev)))
     out = (keep.bool(),)
     if return_stats:
         out += (stats,)
@@ -173,21 +178,21 @@ def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_th
 
 
 def slide_mask(img_u8, rgb_min=50, iterations=3, transpose=False, return_raw=False, return_stats=False):
-    """The whole-slide mask of extract_patches (patch_gen_hdf5.py:25-50,69-72) for ONE uint8 [H, W, 3] CUDA tensor of any
-    size up to 32768 x 32768 and 2^30 pixels: bool [H, W] = ``binary_erosion(binary_dilation(get_mask_image(img, rgb_min),
+    """The whole-slide mask of extract_patches (patch_gen_hdf5.py:25-50,69-72) for ONE uint8 [H, W, 3] CUDA tensor (or
+    [H, W, 4], the fourth channel ignored) of any size up to 32768 x 32768 and 2^30 pixels: bool [H, W] = ``binary_erosion(binary_dilation(get_mask_image(img, rgb_min),
     iterations=iterations), iterations=iterations)``, every bit the host's; ``iterations`` in 0..8, 0 leaves the mask as it
     is.  ``transpose``: the results as C-contiguous [W, H], equal to the host's on the transposed image (the layout of the
     reference's mask.npy) without a transposing copy.  ``return_raw``: also the mask before the closing.  ``return_stats``:
     also float64 [8] = thr_R, thr_G, thr_B, thr_S, raw count, closed count, min and max of the saturation, all exact.
     Asynchronous on the current stream; no CPU fallback."""
     import torch
+    if torch.is_tensor(img_u8) and (img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] not in (3, 4)):
+        raise ValueError(f"slide_mask takes uint8 [H, W, 3 or 4], got {img_u8.dtype} {tuple(img_u8.shape)}")
     _lib.require_gpu()
     if not (torch.is_tensor(img_u8) and img_u8.is_cuda):
         raise _lib.SequoiaHipError("slide_mask needs a CUDA tensor (no CPU fallback)")
-    if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
-        raise ValueError(f"slide_mask takes uint8 [H, W, 3], got {img_u8.dtype} {tuple(img_u8.shape)}")
     x = img_u8.contiguous()
-    H, W, _ = x.shape
+    H, W, C = x.shape
     dev = x.device
     L = _lib.lib()
     need = L.sq_slide_mask_workspace_bytes(H, W)                    # refuses a bad size with the library's message
@@ -199,8 +204,8 @@ def slide_mask(img_u8, rgb_min=50, iterations=3, transpose=False, return_raw=Fal
     stats = torch.empty(8, dtype=torch.float64, device=dev) if return_stats else None
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.sq_slide_mask(_lib.ptr(x), H, W, int(rgb_min), int(iterations), int(bool(transpose)), _lib.ptr(raw),
-                                   _lib.ptr(closed), _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+        _lib.check(L.sq_slide_mask_px(_lib.ptr(x), H, W, C, int(rgb_min), int(iterations), int(bool(transpose)), _lib.ptr(raw),
+                                      _lib.ptr(closed), _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
     out = (closed.view(torch.bool),)
     if return_raw:
         out += (raw.view(torch.bool),)
@@ -270,11 +275,14 @@ def _mask_level_size(slide):
 
 
 def _closed_mask_on_device(slide, device):
-    """get_mask + the closing of extract_patches on `device`: the level image as get_mask reads it, uploaded through pinned
+    """get_mask + the closing of extract_patches on `device`: the level image as get_mask reads it (RGB, or RGBA as
+    OpenSlide returns it: ``sq_slide_mask_px`` reads 4-byte pixels, so the host does not repack them), uploaded through pinned
     memory, ``slide_mask(transpose=True)``, and the bool [W, H] array back on the host."""
     import torch
     level, size = _mask_level_size(slide)
-    img = np.asarray(slide.read_region((0, 0), level, size))[:, :, :3]
+    img = np.asarray(slide.read_region((0, 0), level, size))
+    if img.shape[2] != 4:                    # RGBA goes up whole, one contiguous copy: the kernels skip the fourth byte
+        img = img[:, :, :3]
     pinned = torch.empty(img.shape, dtype=torch.uint8).pin_memory()
     pinned.numpy()[...] = img
     mask = slide_mask(pinned.to(device, non_blocking=True), transpose=True)
@@ -293,16 +301,30 @@ def _filtered_on_host(slide, candidates, size_read, patch_size, resize_factor, b
             yield xy, patch
 
 
-def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget, device, batch):
-    """The kept tiles of `candidates` (visiting order) as ((x, y), uint8 array) pairs, at most `budget` of them: regions are
-    read in chunks of `batch` into pinned memory, filtered on `device` and, for a 40x slide, shrunk there with the
-    Pillow-exact bicubic resize.  No chunk is read once the budget is met.  A read error ends the reading; the tiles read
-    before it are still filtered and yielded, then the error is raised -- unless the budget was met by then, where the
-    host loop would not have reached the failing read."""
+def _as_layout(region, channels):
+    """One region as read (RGB or RGBA) in the layout of a pinned buffer of `channels` channels: as it is when the channel
+    counts agree, else converted on the host."""
+    if region.shape[2] == channels:
+        return region
+    if channels == 3:
+        return region[:, :, :3]
+    out = np.full(region.shape[:2] + (4,), 255, dtype=np.uint8)
+    out[:, :, :3] = region[:, :, :3]
+    return out
+
+
+def _kept_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget, device, batch):
+    """The kept tiles of `candidates` (visiting order), at most `budget` of them, chunk by chunk as (list of (x, y), uint8
+    [k, patch_h, patch_w, 3] tensor on `device`) pairs: regions are read in chunks of `batch` into pinned memory, filtered on
+    `device` and the kept ones gathered there -- for a 40x slide through the Pillow-exact bicubic shrink
+    (``resize_u8_pil(index=)``), else as they are (``pack_rgb(index=)``).  The first region read decides the buffer's layout:
+    an RGBA region (what OpenSlide returns) is copied whole, one contiguous copy, and the kernels skip the fourth byte; a
+    later region with the other channel count is converted on the host.  No chunk is read once the budget is met.  A read
+    error ends the reading; the tiles read before it are still filtered and yielded, then the error is raised -- unless
+    the budget was met by then, where the host loop would not have reached the failing read."""
     import torch
     from . import imgproc
-    pinned = torch.empty((batch, size_read[1], size_read[0], 3), dtype=torch.uint8).pin_memory()
-    view = pinned.numpy()
+    pinned = view = channels = None
     pos, error = 0, None
     while pos < len(candidates) and budget > 0 and error is None:
         chunk = candidates[pos:pos + batch]
@@ -310,7 +332,12 @@ def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor,
         k = 0
         for xy in chunk:
             try:
-                view[k] = np.asarray(slide.read_region(xy, 0, size_read))[:, :, :3]
+                region = np.asarray(slide.read_region(xy, 0, size_read))
+                if pinned is None:
+                    channels = 4 if region.shape[2] == 4 else 3
+                    pinned = torch.empty((batch, size_read[1], size_read[0], channels), dtype=torch.uint8).pin_memory()
+                    view = pinned.numpy()
+                view[k] = _as_layout(region, channels)
             except Exception as e:
                 error = e
                 break
@@ -318,31 +345,28 @@ def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor,
         if k == 0:
             break
         tiles = pinned[:k].to(device, non_blocking=True)
-        kept = torch.nonzero(filter_patches(tiles, background_threshold=background_threshold)).flatten()[:budget]
-        if kept.numel():
-            out = tiles[kept]
+        kept = torch.nonzero(filter_patches(tiles, background_threshold=background_threshold)).flatten()[:budget].to(torch.int32)
+        n_kept = int(kept.numel())            # nonzero has waited for the upload and the filter: `pinned` may be written again
+        if n_kept:
             if resize_factor != 1.0:
-                out = imgproc.resize_u8_pil(out, (int(patch_size[1]), int(patch_size[0])), "bicubic")
-            out = out.cpu().numpy()                      # also orders the next chunk's writes to `pinned` behind this upload
-            for i, j in enumerate(kept.tolist()):
-                yield chunk[j], out[i]
-            budget -= int(kept.numel())
-        else:
-            torch.cuda.current_stream(tiles.device).synchronize()
+                out = imgproc.resize_u8_pil(tiles, (int(patch_size[1]), int(patch_size[0])), "bicubic", index=kept)
+            else:
+                out = imgproc.pack_rgb(tiles, index=kept)
+            yield [chunk[j] for j in kept.tolist()], out
+            budget -= n_kept
     if error is not None and budget > 0:
         raise error
 
 
-def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide=2000,
-                    background_threshold=0.2, device=None, batch=256, slide_mask="host"):
-    """patch_gen_hdf5.py:51-137 for an already opened slide.  Returns the number of patches written (None when the slide
-    had been completed before).  ``device`` (a CUDA device) runs the per-tile filter and the 40x shrink there, `batch`
-    candidate tiles at a time (``filter_patches``, ``imgproc.resize_u8_pil``); the slide mask and the visiting order stay
-    on the host, and the datasets, ``mask.npy`` and ``complete.txt`` are the host path's byte for byte.  Up to batch - 1
-    more regions than the host path may be read near the cap; none of them is written.  ``slide_mask="device"`` (needs
-    ``device``) also computes the slide mask and its closing there (``slide_mask``, ``sq_slide_mask``) from the same level
-    image; ``mask.npy`` keeps the host path's header and bytes.  The level image must be within the library's bounds
-    (extents up to 32768, 2^30 pixels)."""
+def _filtered_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget, device, batch):
+    """``_kept_on_device`` as ((x, y), uint8 array) pairs on the host, the form ``_filtered_on_host`` yields."""
+    for coords, tiles in _kept_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget,
+                                         device, batch):
+        yield from zip(coords, tiles.cpu().numpy())
+
+
+def _check_device_request(slide, patch_size, device, batch, slide_mask):
+    """What extract_patches and embed_slide refuse before they touch a file."""
     if slide_mask not in ("host", "device"):
         raise ValueError(f"slide_mask={slide_mask!r}: 'host' or 'device'")
     if slide_mask == "device" and device is None:
@@ -360,6 +384,97 @@ def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, 
             if not (1 <= lw <= SLIDE_MASK_MAX_DIM and 1 <= lh <= SLIDE_MASK_MAX_DIM and lw * lh <= SLIDE_MASK_MAX_PIXELS):
                 raise ValueError(f"device slide mask: level {level} is {lw} x {lh} pixels, every extent must be in 1..{SLIDE_MASK_MAX_DIM} "
                                  f"and the image at most 2^30 pixels")
+
+
+def _candidate_walk(slide, slide_id, patch_size, slide_mask, device, mask_file):
+    """patch_gen_hdf5.py:65-107: the closed slide mask (saved to `mask_file` unless that is None) and the seed-5 shuffled grid
+    of level-0 tiles.  Returns (candidates, size_read, resize_factor, n_grid): `candidates` generates the (x, y) that lie on
+    the mask, looked up as they are visited; n_grid is the size of the whole grid (the cap when none is given)."""
+    if slide_mask == "device":
+        mask, mask_level = _closed_mask_on_device(slide, device)
+    else:
+        mask, mask_level = get_mask(slide)
+        mask = binary_erosion(binary_dilation(mask, iterations=3), iterations=3)
+    if mask_file is not None:
+        np.save(mask_file, mask)
+    ratio_x = slide.level_dimensions[0][0] / slide.level_dimensions[mask_level][0]
+    ratio_y = slide.level_dimensions[0][1] / slide.level_dimensions[mask_level][1]
+    xmax, ymax = slide.level_dimensions[0]
+    resize_factor = float(slide.properties.get('aperio.AppMag', 20)) / 20.0          # 40x slides: read 2x the size, shrink
+    size_read = (int(resize_factor * patch_size[0]), int(resize_factor * patch_size[1]))
+    print(f"patch size for {slide_id}: {size_read}")
+    indices = [(x, y) for x in range(0, xmax, size_read[0]) for y in range(0, ymax, size_read[0])]
+    np.random.seed(5)
+    np.random.shuffle(indices)
+    candidates = ((x, y) for x, y in indices if mask[int(x / ratio_x), int(y / ratio_y)] == 1)      # looked up as they are visited
+    return candidates, size_read, resize_factor, len(indices)
+
+
+def embed_slide(slide, model, *, patch_size, max_patches_per_slide, max_patch_number, n_clusters, random_state=0, feat_type,
+                resize, device, batch=256, slide_mask="host", background_threshold=0.2, mask_path=None, slide_id=None):
+    """Slide regions -> patch features -> cluster tokens without a patch store: what ``extract_patches(device=...)``,
+    ``cli.compute_features`` and ``cli.kmean_features`` compute one after another through two sets of files, with the kept
+    tiles staying on `device`.  The candidate walk is extract_patches's (same mask, seed-5 order, cap and read-error rule: a
+    failing read prints the error and the tiles kept before it still count); the kept tiles are put in the order in which
+    the patch file's ``keys()`` would list their ``"{x}_{y}"`` datasets (``store.key_order``), cut to ``max_patch_number`` by
+    ``random.sample`` on that list exactly where cli.compute_features cuts (``features.sample_keys``: seed ``random`` as that
+    CLI does to get its rows), embedded by ``model.extract_patches_u8`` (``features.patch_features``; `feat_type`, `resize`
+    as the CLI's flags) and clustered by ``kmeans_fit`` when there are at least `n_clusters` of them.
+    ``patch_size``: an int or (w, h) as extract_patches takes it; ``max_patches_per_slide`` may be None (no cap).
+    Returns a dict: ``coords`` int32 [n, 2] numpy (x, y of each row), ``features`` f32 [n, D], ``labels`` i32 [n] and
+    ``cluster_features`` f32 [n_clusters, D] device tensors -- the last two None below `n_clusters` rows, ``features`` None
+    when no tile was kept.  Writes ``<mask_path>/<slide_id>/mask.npy`` when ``mask_path`` is given and nothing else."""
+    import torch
+    from . import features as steps, imgproc
+    if device is None:
+        raise ValueError("embed_slide needs device=")
+    if mask_path is not None and slide_id is None:
+        raise ValueError("embed_slide: mask_path needs slide_id (the mask goes to <mask_path>/<slide_id>/mask.npy)")
+    patch_size = (int(patch_size), int(patch_size)) if isinstance(patch_size, int) else tuple(patch_size)
+    _check_device_request(slide, patch_size, device, batch, slide_mask)
+    mask_file = None
+    if mask_path is not None:
+        os.makedirs(os.path.join(mask_path, slide_id), exist_ok=True)
+        mask_file = os.path.join(mask_path, slide_id, "mask.npy")
+    coords, chunks = [], []
+    try:          # as extract_patches: an unreadable slide prints its error; what was kept before it stays
+        candidates, size_read, resize_factor, n_grid = _candidate_walk(slide, slide_id, patch_size, slide_mask, device, mask_file)
+        budget = n_grid if max_patches_per_slide is None else int(max_patches_per_slide)
+        for xy, tiles in _kept_on_device(slide, list(candidates), size_read, patch_size, resize_factor, background_threshold, budget,
+                                         device, int(batch)):
+            coords += xy
+            chunks.append(tiles)
+    except Exception as e:
+        print("error with slide id {} patch {}".format(slide_id, len(coords)))
+        print(e)
+    names = [f"{x}_{y}" for x, y in coords]
+    row_of = {name: i for i, name in enumerate(names)}
+    order = [row_of[key] for key in steps.sample_keys(store.key_order(names), max_patch_number)]
+    out = dict(coords=np.array([coords[i] for i in order], dtype=np.int32).reshape(-1, 2), features=None, labels=None,
+               cluster_features=None)
+    if not order:
+        return out
+    tiles = chunks[0] if len(chunks) == 1 else torch.cat(chunks)
+    patches = imgproc.pack_rgb(tiles, index=torch.tensor(order, dtype=torch.int32, device=tiles.device))
+    del tiles, chunks
+    out["features"] = steps.patch_features(model, patches, feat_type, resize, device)
+    if out["features"].shape[0] >= n_clusters:
+        r = steps.cluster(out["features"], n_clusters, random_state=random_state)
+        out["labels"], out["cluster_features"] = r["labels"][0], r["cluster_features"][0]
+    return out
+
+
+def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide=2000,
+                    background_threshold=0.2, device=None, batch=256, slide_mask="host"):
+    """patch_gen_hdf5.py:51-137 for an already opened slide.  Returns the number of patches written (None when the slide
+    had been completed before).  ``device`` (a CUDA device) runs the per-tile filter and the 40x shrink there, `batch`
+    candidate tiles at a time (``filter_patches``, ``imgproc.resize_u8_pil``); the slide mask and the visiting order stay
+    on the host, and the datasets, ``mask.npy`` and ``complete.txt`` are the host path's byte for byte.  Up to batch - 1
+    more regions than the host path may be read near the cap; none of them is written.  ``slide_mask="device"`` (needs
+    ``device``) also computes the slide mask and its closing there (``slide_mask``, ``sq_slide_mask``) from the same level
+    image; ``mask.npy`` keeps the host path's header and bytes.  The level image must be within the library's bounds
+    (extents up to 32768, 2^30 pixels)."""
+    _check_device_request(slide, patch_size, device, batch, slide_mask)
     patch_folder = os.path.join(patches_output_dir, slide_id)
     os.makedirs(patch_folder, exist_ok=True)
     mask_folder = os.path.join(mask_path, slide_id)
@@ -370,24 +485,10 @@ def extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, 
     hdf = store.File(os.path.join(patch_folder, f"{slide_id}.hdf5"), 'w')
     n_written = 0
     try:          # patch_gen_hdf5.py:78,135-137: one unreadable slide prints its error and must not end the whole run
-        if slide_mask == "device":
-            mask, mask_level = _closed_mask_on_device(slide, device)
-        else:
-            mask, mask_level = get_mask(slide)
-            mask = binary_erosion(binary_dilation(mask, iterations=3), iterations=3)
-        np.save(os.path.join(mask_folder, "mask.npy"), mask)
-        ratio_x = slide.level_dimensions[0][0] / slide.level_dimensions[mask_level][0]
-        ratio_y = slide.level_dimensions[0][1] / slide.level_dimensions[mask_level][1]
-        xmax, ymax = slide.level_dimensions[0]
-        resize_factor = float(slide.properties.get('aperio.AppMag', 20)) / 20.0          # 40x slides: read 2x the size, shrink
-        size_read = (int(resize_factor * patch_size[0]), int(resize_factor * patch_size[1]))
-        print(f"patch size for {slide_id}: {size_read}")
-        indices = [(x, y) for x in range(0, xmax, size_read[0]) for y in range(0, ymax, size_read[0])]
+        candidates, size_read, resize_factor, n_grid = _candidate_walk(slide, slide_id, patch_size, slide_mask, device,
+                                                                       os.path.join(mask_folder, "mask.npy"))
         if max_patches_per_slide is None:
-            max_patches_per_slide = len(indices)
-        np.random.seed(5)
-        np.random.shuffle(indices)
-        candidates = ((x, y) for x, y in indices if mask[int(x / ratio_x), int(y / ratio_y)] == 1)      # looked up as they are visited
+            max_patches_per_slide = n_grid
         if device is None:
             kept = _filtered_on_host(slide, candidates, size_read, patch_size, resize_factor, background_threshold)
         else:

@@ -81,5 +81,13 @@ def File(path, mode="r"):
     return _NpyDirFile(path, "a" if mode == "r+" else mode)
 
 
+def key_order(names):
+    """`names` in the order ``File(...).keys()`` lists datasets of these names, whichever backend wrote them: HDF5 iterates a
+    group's links by name (h5py and h5lite both ask for H5_INDEX_NAME, increasing), which compares the bytes of the names as
+    ``strcmp`` does, and the directory mirror sorts its file names, for which Python compares code points -- the same order for
+    UTF-8.  So ``"1024_0" < "256_1024" < "256_256"``: digit by digit, ``"_"`` behind every digit, not by the numbers."""
+    return sorted(names, key=lambda name: name.encode("utf-8"))
+
+
 def exists(path):
     return os.path.isfile(path) or os.path.isdir(path + ".d")
