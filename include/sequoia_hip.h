@@ -1069,6 +1069,81 @@ int sq_dbg_kmeans_lloyd(const float* X, int n_slides, int n_samples, int dim, in
                         int large_lists, int max_iter, double tol, int32_t* labels, float* cluster_features, float* final_centers,
                         int32_t* n_iter, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * JPEG tiles: the tiles of a JPEG-compressed tiled TIFF / Aperio SVS level decoded and composed into RGBA regions on the
+ * device.  Replaces the host decoding behind the region reads of pre_processing/patch_gen_hdf5.py (slide.read_region at
+ * :45 and :108, through OpenSlide) and of spatial_vis/visualize.py:58-66,173; sequoia-pub_amd/wsi.py (TiffSlide) is the
+ * caller.  Every output byte is libjpeg's (baseline Huffman, "islow" IDCT, "fancy" upsampling, the 16-bit fixed-point
+ * YCbCr -> RGB), integer throughout; sequoia-pub_amd/csrc/jpeg_core.h holds the arithmetic as host-and-device functions:
+ *   entropy     interleaved scan in MCU order; FF 00 -> FF; EXTEND(v, s) = v if v >= 2^(s-1) else v - 2^s + 1; AC symbol rs:
+ *               r = rs >> 4, s = rs & 15; s == 0: r == 15 skips 16 coefficients, else end of block; otherwise skip r and read
+ *               one coefficient at the zigzag position.  Restart interval Ri: before MCU n > 0 with n % Ri == 0 the partial
+ *               byte goes, FF D0+((n / Ri - 1) & 7) is expected and the DC predictors are reset.  Quantisation tables are in
+ *               zigzag order; dequantisation is the plain product.
+ *   IDCT        13-bit constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172; columns first with a
+ *               descale of 11 bits, then rows with 18, each (v + (1 << (n - 1))) >> n; then clamp(v + 128, 0, 255).  libjpeg's
+ *               range table wraps rather than clamps for |v| beyond about 512; no encoder of 8-bit images produces that.
+ *   upsampling  chroma 2 x 1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2, the end
+ *               samples copied; 2 x 2: cs[i] = 3 near[i] + far[i] (far row r - 1 for output row 2r, r + 1 for 2r + 1,
+ *               replicated at the tile's edge), out[2i] = (3 cs[i] + cs[i-1] + 8) >> 4, out[2i+1] = (3 cs[i] + cs[i+1] + 7) >> 4,
+ *               first column (4 cs[0] + 8) >> 4, last (4 cs[n-1] + 7) >> 4.  Per tile image: edges replicate inside the tile.
+ *   colour      transform != 0 (TIFF photometric 6): cb -= 128, cr -= 128, R = y + ((91881 cr + 32768) >> 16),
+ *               G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768) >> 16), clamped; 0: as stored.
+ * Frames: three components, 8 bits, luma sampling hs x vs in {1 x 1, 2 x 1, 2 x 2} over chroma 1 x 1, extents multiples of
+ * 16 in 16..SQ_JPEG_MAX_TILE, the same for every tile of a call.
+ *
+ * Device inputs of sq_jpeg_decode_tiles (the caller uploads them; all are re-checked on the device, where they live):
+ *   scans        the entropy-coded bytes of the tiles, base 16-byte aligned, scans_bytes a multiple of 16 (a lane fetches 16
+ *                bytes at a time); a tile's scan may start at any byte.
+ *   tile_table   int32 [n_tiles][SQ_JPEG_TILE_WORDS]: scan offset, scan length (bytes of `scans`), table set, restart
+ *                interval in MCUs (0: none), selectors (component c at bits 4c: quantisation table in 2 bits, DC table in
+ *                1 bit, AC table in 1 bit), three zeros.  Lanes of a wave run as long as the longest scan among them: order
+ *                the tiles by scan length.  Up to SQ_JPEG_WAVE_PER_TILE_MAX tiles every tile has a wave to itself (a scan is serial and a wave executes the union
+ *                of its lanes' paths); above, 2 to 64 tiles share one.
+ *   table_sets   uint8 [n_table_sets][SQ_JPEG_TABLE_SET_BYTES]: four quantisation tables of 64 little-endian uint16 in
+ *                zigzag order, then the Huffman tables DC0, DC1, AC0, AC1, each 16 counts and 256 symbols.
+ * Outputs: planes uint8 [n_tiles][sq_jpeg_planes_bytes(1, ...)] (Y [tile_h][tile_w], then Cb and Cr [tile_h / vs][tile_w / hs])
+ * and status int32 [n_tiles]: SQ_JPEG_OK or why the tile's lane stopped -- a table set index outside the block or a Huffman
+ * table whose counts do not make a prefix code or name more than 256 symbols (SQ_JPEG_BAD_TABLE), a scan range outside
+ * `scans` or empty or a restart interval or selector word out of range (SQ_JPEG_BAD_RANGE), a scan that ends before its last
+ * MCU (SQ_JPEG_TRUNCATED), a code that matches no table entry (SQ_JPEG_BAD_CODE), a run past coefficient 63
+ * (SQ_JPEG_BAD_COEF), a missing or wrong restart marker (SQ_JPEG_BAD_RESTART).  A failing tile touches no other tile; its
+ * planes hold what was decoded before the stop.  Nothing is read outside the buffers whatever they contain.
+ *
+ *   sq_jpeg_workspace_bytes : workspace of sq_jpeg_decode_tiles (derived Huffman tables and int16 coefficients); 0 (and an
+ *                          sq_last_error message) for a frame outside the above or n_tiles, n_table_sets < 1.
+ *   sq_jpeg_planes_bytes : bytes of `planes` for n_tiles tiles; 0 likewise.
+ *   sq_jpeg_decode_tiles : three launches (table derivation, entropy decode with one lane per tile and the look-ahead tables
+ *                          in LDS, IDCT through LDS with one thread per column and then per row) and one memset, all on `stream`.
+ *   sq_jpeg_compose_regions : planes of n_slots tiles -> rgba uint8 [k][h][w][4], the layout sq_patch_filter_px,
+ *                          sq_slide_mask_px, sq_resize_u8_gather and sq_pack_rgb_gather take.  regions int32 [k][2]: x, y of
+ *                          each region's corner in level pixels (may be negative); tile_slot int32 [tiles_y][tiles_x]: the
+ *                          slot in `planes` of each tile of the level, or -1.  A pixel outside 0..level_w-1 x 0..level_h-1, or
+ *                          on a tile without a slot (or with a slot outside 0..n_slots-1), is (0, 0, 0, 0); every other has
+ *                          alpha 255.  Four adjacent pixels per thread, one 16-byte store where w is a multiple of 4.
+ * Entries check scalars and sizes before launching (SQ_ERR_ARG / SQ_ERR_WORKSPACE); they allocate nothing and do not wait.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_JPEG_MAX_TILE 1024
+#define SQ_JPEG_TILE_WORDS 8
+#define SQ_JPEG_TABLE_SET_BYTES 1600
+#define SQ_JPEG_MAX_REGION 32768
+#define SQ_JPEG_WAVE_PER_TILE_MAX 4096 /* up to this many tiles each has a wave to itself; above, 2 to 64 share one */
+#define SQ_JPEG_OK 0
+#define SQ_JPEG_BAD_TABLE 1
+#define SQ_JPEG_BAD_RANGE 2
+#define SQ_JPEG_TRUNCATED 3
+#define SQ_JPEG_BAD_CODE 4
+#define SQ_JPEG_BAD_COEF 5
+#define SQ_JPEG_BAD_RESTART 6
+size_t sq_jpeg_workspace_bytes(int n_tiles, int n_table_sets, int tile_w, int tile_h, int hs, int vs);
+size_t sq_jpeg_planes_bytes(int n_tiles, int tile_w, int tile_h, int hs, int vs);
+int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles, const uint8_t* table_sets,
+                         int n_table_sets, int tile_w, int tile_h, int hs, int vs, uint8_t* planes, int32_t* status,
+                         void* workspace, size_t workspace_bytes, sq_stream_t stream);
+int sq_jpeg_compose_regions(const uint8_t* planes, int n_slots, int tile_w, int tile_h, int hs, int vs, int transform,
+                            const int32_t* tile_slot, int tiles_x, int tiles_y, int level_w, int level_h, const int32_t* regions,
+                            int k, int h, int w, uint8_t* rgba, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

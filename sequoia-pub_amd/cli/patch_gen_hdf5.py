@@ -1,6 +1,7 @@
 """WSI -> patch HDF5 files -- counterpart of /root/reference/pre_processing/patch_gen_hdf5.py:148-208 (same flags,
 same outputs: ``<patch_path>/<slide>/<slide>.hdf5`` + ``complete.txt``, ``<mask_path>/<slide>/mask.npy``).  Reading
-real ``.svs`` / ``.tiff`` slides needs openslide-python, exactly like the reference; the mask / tiling / filter logic is
+real ``.svs`` / ``.tiff`` slides needs openslide-python, exactly like the reference, or ``--reader tiff`` (``wsi.TiffSlide``:
+JPEG-tiled TIFF / SVS without openslide, decoded on the GPU, with ``--filter device``); the mask / tiling / filter logic is
 sequoia-pub_amd/patchgen.py.  ``--filter device`` runs the per-tile tissue / contrast filter (and the 40x shrink) on the
 GPU, ``--filter_batch`` candidate tiles at a time, with the same files as a result; the slides then go through the calling
 process one after another -- forked pool workers must not share a process's GPU state -- and ``--parallel`` only prints
@@ -13,6 +14,7 @@ from multiprocessing import Pool
 import pandas as pd
 
 from ..patchgen import extract_patches
+from ..wsi import open_slide
 
 
 def get_slide_id(slide_name):
@@ -21,13 +23,9 @@ def get_slide_id(slide_name):
 
 def process(opts):
     slide_path, patch_size, patches_output_dir, mask_path, slide_id, max_patches_per_slide = opts[:6]
-    device, batch, slide_mask = opts[6:] if len(opts) > 6 else (None, 256, "host")
-    try:
-        from openslide import OpenSlide
-    except ImportError as e:
-        raise SystemExit("openslide-python is required to read whole-slide images (pip install openslide-python); "
-                         "sequoia-pub_amd.patchgen.extract_patches also accepts any object with OpenSlide's interface") from e
-    extract_patches(OpenSlide(slide_path), mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide,
+    device, batch, slide_mask = opts[6:9] if len(opts) > 6 else (None, 256, "host")
+    slide = open_slide(slide_path, opts[9] if len(opts) > 9 else "openslide", device or "cuda:0")
+    extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide,
                     device=device, batch=batch, slide_mask=slide_mask)
 
 
@@ -50,9 +48,14 @@ def main(argv=None):
     p.add_argument('--slide_mask', default='host', choices=['host', 'device'],
                    help="where the whole-slide tissue mask and its closing are computed: host = numpy / scipy as in the reference; "
                         "device = sq_slide_mask on the GPU (needs --filter device)")
+    p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
+                   help="what opens a slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without "
+                        "openslide; the tiles are decoded on the GPU, so it needs --filter device)")
     args = p.parse_args(argv)
     if args.slide_mask == 'device' and args.filter != 'device':
         p.error("--slide_mask device needs --filter device")
+    if args.reader == 'tiff' and args.filter != 'device':
+        p.error("--reader tiff decodes on the GPU: it needs --filter device")
 
     slide_list = [s for s in os.listdir(args.wsi_path) if s.endswith('.svs') or s.endswith('.tiff')]
     if args.ref_file:
@@ -71,7 +74,7 @@ def main(argv=None):
         if args.parallel:
             print("--filter device: slides are processed one after another in this process (--parallel is not used)")
         for o in opts:
-            process(o + ("cuda:0", args.filter_batch, args.slide_mask))
+            process(o + ("cuda:0", args.filter_batch, args.slide_mask, args.reader))
     elif args.parallel:
         with Pool(processes=4) as pool:
             pool.map(process, opts)

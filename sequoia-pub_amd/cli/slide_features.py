@@ -5,7 +5,8 @@
 The kept tiles never leave the GPU (``patchgen.embed_slide``): no ``<patch_path>/<slide>/<slide>.hdf5`` is written, read
 back and uploaded again.  The datasets are byte for byte the chain's: same candidate walk and filter, rows in the order the
 patch file's keys would have had, ``random.sample`` at the same point with the same ``--seed``, the same extractor and
-k-Means calls (``features.py``).  Flags are those of the three CLIs; ``--mask_path`` (optional here) also writes
+k-Means calls (``features.py``).  ``--reader tiff`` opens JPEG-tiled TIFF / SVS slides with ``wsi.TiffSlide`` (no openslide; the
+tiles are decoded on the GPU and the regions never touch the host).  Flags are those of the three CLIs; ``--mask_path`` (optional here) also writes
 ``<mask_path>/<slide>/mask.npy``.
 
     python -m sequoia_pub_amd.cli.slide_features --feat_type resnet --ref_file ref.csv --wsi_path HE \\
@@ -13,7 +14,7 @@ k-Means calls (``features.py``).  Flags are those of the three CLIs; ``--mask_pa
 Slides are the rows of ``--ref_file`` (``<wsi_path>/<wsi_file_name>.svs``, or ``.tiff``), in the order cli.compute_features
 visits them; under torchrun the list is sharded across the GPUs like there.  A slide that fails is printed and skipped; a
 slide whose reading fails part-way keeps the tiles read before, as the chain does.  Every project's slides are clustered
-(cli.kmean_features looks for all of them under the first row's project).  Needs openslide-python to read real slides."""
+(cli.kmean_features looks for all of them under the first row's project).  The default reader needs openslide-python."""
 import argparse
 import os
 
@@ -22,18 +23,9 @@ import numpy as np
 from .. import store
 from ..data import shard_rows
 from ..patchgen import embed_slide
+from ..wsi import open_slide                     # the one opener of the slide CLIs: --reader openslide | tiff
 from .common import init_distributed, ref_frame, seed_everything
 from .compute_features import build_extractor
-
-
-def open_slide(path):
-    """As cli.patch_gen_hdf5 opens one."""
-    try:
-        from openslide import OpenSlide
-    except ImportError as e:
-        raise SystemExit("openslide-python is required to read whole-slide images (pip install openslide-python); "
-                         "sequoia-pub_amd.patchgen.embed_slide also accepts any object with OpenSlide's interface") from e
-    return OpenSlide(path)
 
 
 def main(argv=None):
@@ -48,6 +40,9 @@ def main(argv=None):
     p.add_argument('--slide_mask', default='host', choices=['host', 'device'],
                    help="where the whole-slide tissue mask and its closing are computed (as cli.patch_gen_hdf5)")
     p.add_argument('--batch', default=256, type=int, help="candidate tiles read, uploaded and filtered at a time")
+    p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
+                   help="what opens a slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without "
+                        "openslide, the tiles decoded on the GPU)")
     p.add_argument('--feat_type', default="resnet", type=str, required=True, help='"resnet" or "uni"')
     p.add_argument('--feature_path', type=str, default="/examples/features", help='Output directory to save features')
     p.add_argument('--max_patch_number', type=int, default=4000, help='Max number of patches to use per slide')
@@ -90,7 +85,7 @@ def main(argv=None):
                 print(f'{WSI}: Cluster feature already available')
                 continue
         try:
-            r = embed_slide(open_slide(slide_path), model, patch_size=(args.patch_size, args.patch_size),
+            r = embed_slide(open_slide(slide_path, args.reader, device), model, patch_size=(args.patch_size, args.patch_size),
                             max_patches_per_slide=args.max_patches_per_slide, max_patch_number=args.max_patch_number,
                             n_clusters=args.num_clusters, random_state=0, feat_type=args.feat_type, resize=args.resize, device=device,
                             batch=args.batch, slide_mask=args.slide_mask, mask_path=args.mask_path, slide_id=WSI_slide)

@@ -127,7 +127,13 @@ def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chu
     feats = []
     starts = list(range(0, len(df), chunk))
     for lo in starts[rank::world]:
-        t = read_tiles(slide, df, patch_size_resized, lo, min(lo + chunk, len(df))).to(device)
+        hi = min(lo + chunk, len(df))
+        if hasattr(slide, "read_regions"):       # wsi.TiffSlide: the chunk's regions decoded on the device, the alpha byte dropped there
+            from ..imgproc import pack_rgb
+            corners = [(int(c), int(r)) for c, r in zip(df['xcoord'][lo:hi], df['ycoord'][lo:hi])]
+            t = pack_rgb(slide.read_regions(corners, 0, (patch_size_resized, patch_size_resized)).to(device))
+        else:
+            t = read_tiles(slide, df, patch_size_resized, lo, hi).to(device)
         if patch_size_resized != out_size:
             t = resize_u8(t, out_size)
         feats.append(feat_model.extract_patches_u8(t))
@@ -144,11 +150,13 @@ def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chu
     return allf[gathered_row_of_window(torch.arange(len(df), device=device), chunk, world, slots)]
 
 
-def open_slide(path):
+def open_slide(path, reader="openslide", device="cuda:0"):
+    """``reader``: 'openslide' (openslide-python, when it is installed) or 'tiff' (``wsi.TiffSlide``: JPEG-tiled TIFF / SVS,
+    decoded on `device`); an ``.npy`` RGB array is an ``ArraySlide`` whatever the reader."""
     if path.endswith('.npy'):
         return ArraySlide([np.load(path)])
-    import openslide                                   # absent from this image; real .svs / .tif need it
-    return openslide.OpenSlide(path)
+    from .. import wsi
+    return wsi.open_slide(path, reader, device)
 
 
 def build_model(model_type, input_dim, n_genes, device, compute_dtype):
@@ -188,6 +196,9 @@ def build_parser():
     p.add_argument('--resnet_input', default='256x256', choices=['256x256', 'reference'],
                    help='--feat_type resnet: 256x256 = square tiles (default); reference = every tile resized to height 256, width 265 as '
                         'the reference\'s Resize((256, 265)) does, byte for byte PIL\'s BILINEAR resize whatever --resize says')
+    p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
+                   help='what opens the slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without '
+                        'openslide, the tiles decoded on the GPU)')
     p.add_argument('--valid_tiles', default='host', choices=['host', 'device'],
                    help='where the grid of valid tiles is decided: host = the scipy loop over every grid tile (default); device = one kernel '
                         'launch on the rank\'s device (patchgen.valid_tile_grid), the same frame')
@@ -216,7 +227,7 @@ def main(argv=None):
     stem = args.wsi_file_name.replace('.svs', '').replace('.tif', '').replace('.npy', '')
     slide_dir = args.slide_path or f'./TCGA/{args.project}/'
     mask = np.load(args.mask_path or f'./TCGA/{args.project}_Masks/{stem}/mask.npy')
-    slide = open_slide(os.path.join(slide_dir, args.wsi_file_name))
+    slide = open_slide(os.path.join(slide_dir, args.wsi_file_name), args.reader, device)
     resize_factor = args.resize_factor if args.resize_factor is not None else float(slide.properties.get('aperio.AppMag', 20)) / 20.0
     patch_size_resized = int(resize_factor * patch_size)
     if args.valid_tiles == 'device':                    # under torchrun every rank computes it: deterministic, cheaper than a broadcast

@@ -12,7 +12,8 @@ filters side by side: profiles/patch_filter_rate.txt).  The whole-slide mask in 
 level and the closing: seconds per slide in numpy / scipy on one core) has a device form as well: ``slide_mask``
 (``sq_slide_mask``, csrc/slidemask.hip) and ``extract_patches(..., device=..., slide_mask="device")``, every mask bit and
 the bytes of ``mask.npy`` the host's (tools/slide_mask_rate.py, profiles/slide_mask_rate.txt).  With both, what is left of
-the stage is reading the regions; slide decoding itself has not been measured, openslide is absent.
+the stage is reading the regions: ``wsi.TiffSlide`` decodes JPEG-tiled TIFF / SVS slides on the device and hands whole batches of
+regions over as device tensors (``read_regions``; profiles/slide_read_rate.txt), other slide objects are read region by region.
 The device forms take RGBA as OpenSlide's ``read_region`` returns it (the kernels skip the fourth byte, so the host copies a
 region whole instead of repacking it: 4.3 against 171 us per 256 x 256 region, profiles/region_path_rate.txt), and
 ``embed_slide`` runs the same walk with the kept tiles staying on the device -- order, ``random.sample`` cut, extractor and
@@ -280,6 +281,9 @@ def _closed_mask_on_device(slide, device):
     memory, ``slide_mask(transpose=True)``, and the bool [W, H] array back on the host."""
     import torch
     level, size = _mask_level_size(slide)
+    if hasattr(slide, "read_regions"):       # wsi.TiffSlide: the level image is decoded on the device and never leaves it
+        mask = slide_mask(slide.read_regions([(0, 0)], level, size)[0].to(device), transpose=True)
+        return mask.cpu().numpy(), level
     img = np.asarray(slide.read_region((0, 0), level, size))
     if img.shape[2] != 4:                    # RGBA goes up whole, one contiguous copy: the kernels skip the fourth byte
         img = img[:, :, :3]
@@ -313,6 +317,31 @@ def _as_layout(region, channels):
     return out
 
 
+def _read_batch(slide, chunk, size_read):
+    """``slide.read_regions`` of a chunk of level-0 corners as (uint8 [k, h, w, 4] device tensor or None, k, error): k is the
+    whole chunk and the error None when every region was read; else the regions in front of the first one that fails, as the
+    per-region loop would have read them, and the error of that one.  Only the reader's own two errors are taken apart that
+    way -- tiles that did not decode, and a tile the container parser refuses when it is read; any other error (a device out
+    of memory, a library error) ends the reading at once with nothing of the chunk."""
+    from .wsi import TileDecodeError, WsiFormatError
+    try:
+        return slide.read_regions(chunk, 0, size_read), len(chunk), None
+    except TileDecodeError as e:             # every other region of the batch is there
+        k = e.first_failed_region
+        return (e.regions[:k] if k else None), k, e
+    except WsiFormatError as e:              # refused on the host before anything ran: a tile's header, its range in the file
+        k = 0
+        for xy in chunk:
+            try:
+                slide.read_regions([xy], 0, size_read)
+            except WsiFormatError:
+                break
+            k += 1
+        return (slide.read_regions(chunk[:k], 0, size_read) if k else None), k, e
+    except Exception as e:
+        return None, 0, e
+
+
 def _kept_on_device(slide, candidates, size_read, patch_size, resize_factor, background_threshold, budget, device, batch):
     """The kept tiles of `candidates` (visiting order), at most `budget` of them, chunk by chunk as (list of (x, y), uint8
     [k, patch_h, patch_w, 3] tensor on `device`) pairs: regions are read in chunks of `batch` into pinned memory, filtered on
@@ -321,30 +350,36 @@ def _kept_on_device(slide, candidates, size_read, patch_size, resize_factor, bac
     an RGBA region (what OpenSlide returns) is copied whole, one contiguous copy, and the kernels skip the fourth byte; a
     later region with the other channel count is converted on the host.  No chunk is read once the budget is met.  A read
     error ends the reading; the tiles read before it are still filtered and yielded, then the error is raised -- unless
-    the budget was met by then, where the host loop would not have reached the failing read."""
+    the budget was met by then, where the host loop would not have reached the failing read.  A slide with ``read_regions``
+    (``wsi.TiffSlide``) hands each chunk over as a device tensor instead -- every tile the chunk touches decoded once, no
+    pixel on the host -- with the same order, budget and read-error rule."""
     import torch
     from . import imgproc
     pinned = view = channels = None
+    batched = hasattr(slide, "read_regions")
     pos, error = 0, None
     while pos < len(candidates) and budget > 0 and error is None:
         chunk = candidates[pos:pos + batch]
         pos += len(chunk)
         k = 0
-        for xy in chunk:
-            try:
-                region = np.asarray(slide.read_region(xy, 0, size_read))
-                if pinned is None:
-                    channels = 4 if region.shape[2] == 4 else 3
-                    pinned = torch.empty((batch, size_read[1], size_read[0], channels), dtype=torch.uint8).pin_memory()
-                    view = pinned.numpy()
-                view[k] = _as_layout(region, channels)
-            except Exception as e:
-                error = e
-                break
-            k += 1
+        if batched:
+            tiles, k, error = _read_batch(slide, chunk, size_read)
+        else:
+            for xy in chunk:
+                try:
+                    region = np.asarray(slide.read_region(xy, 0, size_read))
+                    if pinned is None:
+                        channels = 4 if region.shape[2] == 4 else 3
+                        pinned = torch.empty((batch, size_read[1], size_read[0], channels), dtype=torch.uint8).pin_memory()
+                        view = pinned.numpy()
+                    view[k] = _as_layout(region, channels)
+                except Exception as e:
+                    error = e
+                    break
+                k += 1
         if k == 0:
             break
-        tiles = pinned[:k].to(device, non_blocking=True)
+        tiles = tiles.to(device) if batched else pinned[:k].to(device, non_blocking=True)
         kept = torch.nonzero(filter_patches(tiles, background_threshold=background_threshold)).flatten()[:budget].to(torch.int32)
         n_kept = int(kept.numel())            # nonzero has waited for the upload and the filter: `pinned` may be written again
         if n_kept:

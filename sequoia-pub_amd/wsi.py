@@ -1,0 +1,562 @@
+"""JPEG-tiled TIFF and Aperio SVS slides without openslide: ``TiffSlide`` is the drop-in for ``openslide.OpenSlide`` over
+the interface subset this package uses (``dimensions``, ``level_count``, ``level_dimensions``, ``level_downsamples``,
+``properties``, ``read_region``, ``close``), replacing the region reads of pre_processing/patch_gen_hdf5.py:45,108 and
+spatial_vis/visualize.py:58-66,173.  The container is parsed here in Python (``struct`` + ``os.pread``, no GPU needed); the
+tiles are decoded by the library on the device (``sq_jpeg_decode_tiles``, ``sq_jpeg_compose_regions``: csrc/jpegdec.hip), every
+byte libjpeg's, and ``read_regions`` hands a whole batch of regions over as one uint8 [k, h, w, 4] device tensor in the layout
+the patch filter, the slide mask, the resize and the pack kernels read -- no pixel is ever on the host.  Reading pixels needs
+the GPU: there is no CPU fallback.
+
+Accepted: classic TIFF (magic 42) and BigTIFF (43), little-endian; a level is an IFD with TileWidth / TileLength, levels
+ordered by decreasing width; stripped IFDs (thumbnail, label, macro of an SVS) are skipped as OpenSlide skips them.  A tiled
+IFD must have compression 7 (JPEG), 8 bits per sample, 3 samples per pixel, planar configuration 1, photometric 2 (RGB) or 6
+(YCbCr), tile extents that are multiples of 16 in 16..1024, and baseline frames of exactly the tile extent with luma sampling
+1x1, 2x1 or 2x2 over chroma 1x1.  Everything else -- big-endian files, JPEG 2000 (33003 / 33005) and any other compression,
+progressive, arithmetic or 12-bit frames, 1 or 4 components, other samplings, a tile with byte count 0 -- is refused with a
+``WsiFormatError`` that names the tag or marker and its value.  The TIFF photometric tag decides the colour transform as libtiff
+does (6: YCbCr -> RGB, 2: components as stored); JFIF and Adobe markers of the stream are ignored.
+
+Region semantics: ``location`` is in level-0 pixels, the level origin is ``(int(x / downsample), int(y / downsample))`` with
+``downsample = level0_width / level_width``; pixels outside the level are (0, 0, 0, 0), inside alpha is 255.  At level 0 and
+for reads from (0, 0) -- the only reads this package makes -- that is what OpenSlide returns.  OpenSlide interpolates a
+fractional origin at higher levels; this reader does not."""
+import os
+import struct
+
+import numpy as np
+
+from . import _lib
+from ._abi import CONSTANTS as _C
+
+TILE_WORDS, TABLE_SET_BYTES, MAX_TILE = _C["SQ_JPEG_TILE_WORDS"], _C["SQ_JPEG_TABLE_SET_BYTES"], _C["SQ_JPEG_MAX_TILE"]
+STATUS_NAMES = {_C["SQ_JPEG_BAD_TABLE"]: "a Huffman table that is no prefix code or a missing table set",
+                _C["SQ_JPEG_BAD_RANGE"]: "a scan range outside the uploaded bytes",
+                _C["SQ_JPEG_TRUNCATED"]: "the scan ends before its last MCU",
+                _C["SQ_JPEG_BAD_CODE"]: "a code that matches no Huffman table entry",
+                _C["SQ_JPEG_BAD_COEF"]: "a zero run past coefficient 63",
+                _C["SQ_JPEG_BAD_RESTART"]: "a missing or wrong restart marker"}
+SCAN_BYTES_MAX = (1 << 31) - 64            # scan offsets in the tile table are int32
+DEFAULT_WORKSPACE_BUDGET = 1 << 30        # bytes of device workspace (planes, coefficients, uploaded scans) per chunk of a batch
+
+_TYPE = {1: "B", 2: "c", 3: "H", 4: "I", 5: "II", 6: "b", 7: "B", 8: "h", 9: "i", 10: "ii", 11: "f", 12: "d", 16: "Q", 17: "q", 18: "Q"}
+_TAG_NAMES = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 262: "PhotometricInterpretation",
+              270: "ImageDescription", 277: "SamplesPerPixel", 284: "PlanarConfiguration", 322: "TileWidth", 323: "TileLength",
+              324: "TileOffsets", 325: "TileByteCounts", 347: "JPEGTables", 530: "YCbCrSubSampling"}
+
+
+class WsiFormatError(ValueError):
+    """The file is not one this reader takes; the message names the tag or marker and its value."""
+
+
+class TileDecodeError(RuntimeError):
+    """Tiles of a batch did not decode.  ``tiles``: [(level, tile_x, tile_y, status)]; ``regions``: the batch's device tensor,
+    every tile but the failing ones decoded; ``first_failed_region``: the first region of the batch that lies on one of them."""
+
+    def __init__(self, message, tiles, regions, first_failed_region):
+        super().__init__(message)
+        self.tiles, self.regions, self.first_failed_region = tiles, regions, first_failed_region
+
+
+# ---- TIFF container ---------------------------------------------------------------------------------------------------
+def read_ifds(fd, size):
+    """Every IFD of a little-endian classic or BigTIFF file as a dict tag -> tuple of values (ASCII and UNDEFINED: bytes)."""
+    head = os.pread(fd, 16, 0)
+    if head[:2] == b"MM":
+        raise WsiFormatError("byte order 'MM' (big-endian TIFF) is not supported: little-endian ('II') files only")
+    if len(head) < 8 or head[:2] != b"II":
+        raise WsiFormatError(f"not a TIFF file: it starts with {head[:4]!r}")
+    magic = struct.unpack_from("<H", head, 2)[0]
+    if magic == 42:
+        big, offset = False, struct.unpack_from("<I", head, 4)[0]
+    elif magic == 43:
+        if len(head) < 16 or struct.unpack_from("<HH", head, 4) != (8, 0):
+            raise WsiFormatError("BigTIFF header: offset size must be 8")
+        big, offset = True, struct.unpack_from("<Q", head, 8)[0]
+    else:
+        raise WsiFormatError(f"TIFF magic {magic}: 42 (classic) or 43 (BigTIFF)")
+    count_fmt, entry_fmt, inline = ("<Q", "<HHQ8s", 8) if big else ("<H", "<HHI4s", 4)
+    entry_size, count_size = struct.calcsize(entry_fmt), struct.calcsize(count_fmt)
+    ifds, seen = [], set()
+    while offset:
+        if offset in seen or offset + count_size > size:
+            raise WsiFormatError(f"IFD offset {offset} is outside the file of {size} bytes or repeats")
+        seen.add(offset)
+        n = struct.unpack(count_fmt, os.pread(fd, count_size, offset))[0]
+        raw = os.pread(fd, n * entry_size + inline, offset + count_size)
+        if len(raw) < n * entry_size + inline:
+            raise WsiFormatError(f"IFD at {offset} with {n} entries runs past the end of the file")
+        tags = {}
+        for i in range(n):
+            tag, kind, count, value = struct.unpack_from(entry_fmt, raw, i * entry_size)
+            if kind not in _TYPE:
+                continue
+            item = struct.calcsize("<" + _TYPE[kind])
+            nbytes = item * count
+            if nbytes <= inline:
+                data = value[:nbytes]
+            else:
+                at = struct.unpack("<Q" if big else "<I", value)[0]
+                if at + nbytes > size:
+                    raise WsiFormatError(f"tag {tag} ({_TAG_NAMES.get(tag, '?')}): {nbytes} bytes at offset {at} run past the end of the file")
+                data = os.pread(fd, nbytes, at)
+            if kind in (2, 7):
+                tags[tag] = data
+            elif kind in (5, 10):
+                tags[tag] = tuple(np.frombuffer(data, dtype="<u4" if kind == 5 else "<i4").reshape(-1, 2).tolist())
+            else:
+                tags[tag] = np.frombuffer(data, dtype=np.dtype(_TYPE[kind]).newbyteorder("<"))
+        ifds.append(tags)
+        offset = struct.unpack("<Q" if big else "<I", raw[n * entry_size:n * entry_size + inline])[0]
+    return ifds, big
+
+
+def _one(tags, tag, default=None):
+    v = tags.get(tag)
+    if v is None:
+        return default
+    return int(v[0])
+
+
+# ---- JPEG headers -----------------------------------------------------------------------------------------------------
+class JpegHeader:
+    """Tables and frame of one (possibly abbreviated) stream: quant {id: uint16[64] zigzag}, huff {(class, id): (counts, symbols)},
+    frame (marker, precision, height, width, [(id, h, v, tq)]), scan [(component id, td, ta)], restart interval, and the byte
+    range [scan_start, scan_end) of the entropy-coded segment."""
+    __slots__ = ("quant", "huff", "frame", "scan", "restart", "scan_start", "scan_end", "own_tables")
+
+    def __init__(self):
+        self.quant, self.huff, self.frame, self.scan = {}, {}, None, None
+        self.restart, self.scan_start, self.scan_end, self.own_tables = 0, None, None, False
+
+
+def parse_jpeg(data, base=None, what="JPEG stream"):
+    """Walk the marker segments of `data` (bytes).  `base`: a JpegHeader whose tables this stream starts from (JPEGTables)."""
+    h = JpegHeader()
+    if base is not None:
+        h.quant, h.huff, h.restart = dict(base.quant), dict(base.huff), base.restart
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise WsiFormatError(f"{what}: no SOI marker at its start")
+    pos = 2
+    while pos + 4 <= n:
+        if data[pos] != 0xFF:
+            raise WsiFormatError(f"{what}: byte {data[pos]:#x} at {pos} where a marker was expected")
+        m = data[pos + 1]
+        if m == 0xFF:
+            pos += 1
+            continue
+        if m == 0xD9:
+            break
+        length = (data[pos + 2] << 8) | data[pos + 3]
+        seg, end = pos + 4, pos + 2 + length
+        if length < 2 or end > n:
+            raise WsiFormatError(f"{what}: segment {m:#x} at {pos} of length {length} runs past the end")
+        need = {0xDD: 2, 0xDA: 1}.get(m, 0)                     # payload bytes indexed below (SOF0 and SOS check theirs as they go)
+        if end - seg < need:
+            raise WsiFormatError(f"{what}: segment {m:#x} at {pos} has a payload of {end - seg} bytes, at least {need} are needed")
+        if m == 0xDB:
+            h.own_tables = True
+            while seg < end:
+                pq, tq = data[seg] >> 4, data[seg] & 15
+                if pq not in (0, 1) or tq > 3 or seg + 1 + 64 * (pq + 1) > end:
+                    raise WsiFormatError(f"{what}: DQT with precision {pq}, table {tq}")
+                vals = np.frombuffer(data, dtype=">u2" if pq else np.uint8, count=64, offset=seg + 1).astype(np.uint16)
+                h.quant[tq] = vals
+                seg += 1 + 64 * (pq + 1)
+        elif m == 0xC4:
+            h.own_tables = True
+            while seg < end:
+                tc, th = data[seg] >> 4, data[seg] & 15
+                counts = bytes(data[seg + 1:seg + 17])
+                total = sum(counts)
+                if tc > 1 or th > 1 or len(counts) < 16 or total > 256 or seg + 17 + total > end:
+                    raise WsiFormatError(f"{what}: DHT class {tc}, table {th} with {total} symbols: baseline takes classes 0..1, tables 0..1, "
+                                         f"at most 256 symbols")
+                h.huff[(tc, th)] = (counts, bytes(data[seg + 17:seg + 17 + total]))
+                seg += 17 + total
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            if m != 0xC0:
+                kind = {0xC1: "extended sequential", 0xC2: "progressive", 0xC9: "arithmetic-coded"}.get(m, "not baseline")
+                raise WsiFormatError(f"{what}: frame marker SOF{m - 0xC0} ({m:#x}, {kind}) is not supported: baseline (SOF0) only")
+            if end - seg < 6:
+                raise WsiFormatError(f"{what}: segment {m:#x} at {pos} has a payload of {end - seg} bytes, at least 6 are needed")
+            precision, height, width, nc = data[seg], (data[seg + 1] << 8) | data[seg + 2], (data[seg + 3] << 8) | data[seg + 4], data[seg + 5]
+            if precision != 8:
+                raise WsiFormatError(f"{what}: SOF0 sample precision {precision}: 8 bits only")
+            if nc != 3:
+                raise WsiFormatError(f"{what}: SOF0 with {nc} components: 3 only")
+            if end - seg < 15:
+                raise WsiFormatError(f"{what}: SOF0 of 3 components has a payload of {end - seg} bytes, 15 are needed")
+            comps = [(data[seg + 6 + 3 * i], data[seg + 7 + 3 * i] >> 4, data[seg + 7 + 3 * i] & 15, data[seg + 8 + 3 * i]) for i in range(3)]
+            h.frame = (m, precision, height, width, comps)
+        elif m == 0xDD:
+            h.restart = (data[seg] << 8) | data[seg + 1]
+        elif m == 0xDA:
+            ns = data[seg]
+            if ns != 3 or h.frame is None:
+                raise WsiFormatError(f"{what}: SOS with {ns} components: one interleaved scan of 3 only")
+            if end - seg < 10:
+                raise WsiFormatError(f"{what}: SOS of 3 components has a payload of {end - seg} bytes, 10 are needed")
+            h.scan = [(data[seg + 1 + 2 * i], data[seg + 2 + 2 * i] >> 4, data[seg + 2 + 2 * i] & 15) for i in range(3)]
+            h.scan_start = end
+            tail = data.rfind(b"\xff\xd9", end) if isinstance(data, (bytes, bytearray)) else -1
+            h.scan_end = tail if tail >= 0 else n
+            return h
+        pos = end
+    return h
+
+
+def _sampling(frame, what):
+    comps = frame[4]
+    (hs, vs), chroma = (comps[0][1], comps[0][2]), [(c[1], c[2]) for c in comps[1:]]
+    if chroma != [(1, 1), (1, 1)] or (hs, vs) not in ((1, 1), (2, 1), (2, 2)):
+        raise WsiFormatError(f"{what}: SOF0 sampling factors {[(c[1], c[2]) for c in comps]}: luma 1x1, 2x1 or 2x2 over chroma 1x1 only")
+    return hs, vs
+
+
+def table_set_bytes(h):
+    """The SQ_JPEG_TABLE_SET_BYTES block of a parsed stream's tables."""
+    out = np.zeros(TABLE_SET_BYTES, dtype=np.uint8)
+    quant = out[:512].view("<u2").reshape(4, 64)
+    for tq, vals in h.quant.items():
+        quant[tq] = vals
+    for (tc, th), (counts, symbols) in h.huff.items():
+        at = 512 + (tc * 2 + th) * 272
+        out[at:at + 16] = np.frombuffer(counts, dtype=np.uint8)
+        out[at + 16:at + 16 + len(symbols)] = np.frombuffer(symbols, dtype=np.uint8)
+    return out.tobytes()
+
+
+def selectors(h, what):
+    """The selector word of a parsed stream: component c at bits 4c, quantisation table | DC table << 2 | AC table << 3."""
+    sel = 0
+    by_id = {cid: (td, ta) for cid, td, ta in h.scan}
+    for c, (cid, _, _, tq) in enumerate(h.frame[4]):
+        if cid not in by_id:
+            raise WsiFormatError(f"{what}: SOS does not name component {cid} of the frame")
+        td, ta = by_id[cid]
+        if tq not in h.quant or (0, td) not in h.huff or (1, ta) not in h.huff or td > 1 or ta > 1:
+            raise WsiFormatError(f"{what}: component {cid} names quantisation table {tq}, DC table {td}, AC table {ta}, not all defined")
+        sel |= (tq | (td << 2) | (ta << 3)) << (4 * c)
+    return sel
+
+
+class _Level:
+    __slots__ = ("width", "height", "tile_w", "tile_h", "tiles_x", "tiles_y", "offsets", "counts", "base", "transform", "hs", "vs",
+                 "index", "info", "shared")
+
+
+class TiffSlide:
+    """``openslide.OpenSlide(path)`` for a JPEG-tiled TIFF / SVS file (module docstring).  ``read_region`` returns an RGBA
+    ``PIL.Image``; ``read_regions`` the same pixels for a batch as a device tensor.  Opening and the properties need no GPU."""
+
+    def __init__(self, path, device="cuda:0", workspace_budget=DEFAULT_WORKSPACE_BUDGET):
+        self.path, self.device, self.workspace_budget = path, device, int(workspace_budget)
+        self._fd = os.open(path, os.O_RDONLY)
+        self._pinned = None
+        self.last_batch_tiles = []           # (tile_x, tile_y) of every tile decode of the last read_regions call, chunk by chunk
+        try:
+            self._size = os.fstat(self._fd).st_size
+            ifds, self.bigtiff = read_ifds(self._fd, self._size)
+            self._levels = [self._level(i, t) for i, t in enumerate(ifds) if 322 in t or 323 in t]
+            if not self._levels:
+                raise WsiFormatError("no tiled IFD (TileWidth / TileLength) in the file: stripped images are not levels")
+            self._levels.sort(key=lambda lv: -lv.width)
+            self.level_count = len(self._levels)
+            self.level_dimensions = tuple((lv.width, lv.height) for lv in self._levels)
+            self.dimensions = self.level_dimensions[0]
+            self.level_downsamples = tuple(self.dimensions[0] / lv.width for lv in self._levels)
+            self.properties = self._properties(ifds[self._levels[0].index].get(270, b""))
+            self.properties["openslide.level-count"] = str(self.level_count)         # a string, as OpenSlide gives it
+        except Exception:
+            os.close(self._fd)
+            self._fd = None
+            raise
+
+    # -- container --
+    def _level(self, index, tags):
+        what = f"IFD {index}"
+
+        def need(tag, allowed, text):
+            v = tags.get(tag)
+            v = tuple(int(x) for x in v) if v is not None else None
+            if v is None or any(x not in allowed for x in v):
+                raise WsiFormatError(f"{what}: {_TAG_NAMES[tag]} = {v if v is None or len(v) != 1 else v[0]}: {text}")
+            return v
+        comp = _one(tags, 259, 1)
+        if comp != 7:
+            name = {33003: " (Aperio JPEG 2000, YCbCr)", 33005: " (Aperio JPEG 2000, RGB)", 1: " (uncompressed)", 5: " (LZW)",
+                    8: " (deflate)", 34712: " (JPEG 2000)"}.get(comp, "")
+            raise WsiFormatError(f"{what}: Compression = {comp}{name} is not supported: 7 (JPEG) only")
+        need(258, (8,), "8 bits per sample only")
+        if len(need(277, (3,), "3 samples per pixel only")) != 1 or len(tags[258]) != 3:
+            raise WsiFormatError(f"{what}: BitsPerSample = {tuple(int(x) for x in tags[258])}: three samples of 8 bits only")
+        if _one(tags, 284, 1) != 1:
+            raise WsiFormatError(f"{what}: PlanarConfiguration = {_one(tags, 284)}: 1 (chunky) only")
+        photometric = need(262, (2, 6), "2 (RGB) or 6 (YCbCr) only")[0]
+        lv = _Level()
+        lv.index, lv.width, lv.height = index, _one(tags, 256, 0), _one(tags, 257, 0)
+        lv.tile_w, lv.tile_h = _one(tags, 322, 0), _one(tags, 323, 0)
+        if lv.width < 1 or lv.height < 1:
+            raise WsiFormatError(f"{what}: ImageWidth = {lv.width}, ImageLength = {lv.height}")
+        for tag, v in ((322, lv.tile_w), (323, lv.tile_h)):
+            if v % 16 or not 16 <= v <= MAX_TILE:
+                raise WsiFormatError(f"{what}: {_TAG_NAMES[tag]} = {v}: a multiple of 16 in 16..{MAX_TILE} only")
+        lv.tiles_x, lv.tiles_y = -(-lv.width // lv.tile_w), -(-lv.height // lv.tile_h)
+        if 324 not in tags or 325 not in tags or len(tags[324]) != lv.tiles_x * lv.tiles_y or len(tags[325]) != len(tags[324]):
+            raise WsiFormatError(f"{what}: TileOffsets / TileByteCounts must have {lv.tiles_x * lv.tiles_y} entries each")
+        lv.offsets, lv.counts = tags[324].astype(np.int64), tags[325].astype(np.int64)
+        if (lv.counts == 0).any():
+            t = int(np.flatnonzero(lv.counts == 0)[0])
+            raise WsiFormatError(f"{what}: TileByteCounts[{t}] = 0 (tile {t % lv.tiles_x}, {t // lv.tiles_x}): empty tiles are not supported")
+        lv.transform = 1 if photometric == 6 else 0
+        lv.base = parse_jpeg(bytes(tags[347]), what=f"{what} JPEGTables") if 347 in tags else None
+        lv.shared = table_set_bytes(lv.base) if lv.base is not None else None      # ONE object for every tile without tables of its own
+        lv.info = {}
+        lv.hs, lv.vs = None, None
+        past = np.flatnonzero(lv.offsets + lv.counts > self._size)
+        if past.size == 0:                  # a range past the end of the file is reported when that tile is read
+            self._tile_info(lv, 0, level_name=what)
+        return lv
+
+    def _tile_info(self, lv, t, level_name=None):
+        """(file offset of the scan, its length, table-set bytes, restart interval, selectors) of tile t, parsed once.  A tile
+        without DQT / DHT of its own gets the level's shared table-set object (``lv.shared``, from JPEGTables), not a copy."""
+        got = lv.info.get(t)
+        if got is not None:
+            return got
+        what = f"{level_name or f'IFD {lv.index}'} tile ({t % lv.tiles_x}, {t // lv.tiles_x})"
+        off, count = int(lv.offsets[t]), int(lv.counts[t])
+        if off < 0 or off + count > self._size:
+            raise WsiFormatError(f"{what}: TileOffsets = {off} with TileByteCounts = {count} runs past the end of the file ({self._size} bytes)")
+        data = os.pread(self._fd, count, off)
+        h = parse_jpeg(data, lv.base, what)
+        if h.frame is None or h.scan is None:
+            raise WsiFormatError(f"{what}: no SOF0 / SOS in the tile's stream")
+        if (h.frame[3], h.frame[2]) != (lv.tile_w, lv.tile_h):
+            raise WsiFormatError(f"{what}: SOF0 frame of {h.frame[3]} x {h.frame[2]} pixels in tiles of {lv.tile_w} x {lv.tile_h}: they must be equal")
+        hs, vs = _sampling(h.frame, what)
+        if lv.hs is None:
+            lv.hs, lv.vs = hs, vs
+        elif (hs, vs) != (lv.hs, lv.vs):
+            raise WsiFormatError(f"{what}: SOF0 luma sampling {hs}x{vs} where the level's first tile has {lv.hs}x{lv.vs}")
+        sel = selectors(h, what)
+        tables = lv.shared if (lv.shared is not None and not h.own_tables) else table_set_bytes(h)
+        got = (off + h.scan_start, h.scan_end - h.scan_start, tables, h.restart, sel)
+        if got[1] < 1:
+            raise WsiFormatError(f"{what}: an empty entropy-coded segment")
+        lv.info[t] = got
+        return got
+
+    @staticmethod
+    def _properties(description):
+        text = bytes(description).split(b"\0")[0].decode("latin-1")
+        props = {"openslide.vendor": "aperio" if text.startswith("Aperio") else "generic-tiff"}
+        if text:
+            props["tiff.ImageDescription"] = text
+        for part in text.split("|")[1:]:
+            key, eq, value = part.partition("=")
+            if eq:
+                props[f"aperio.{key.strip()}"] = value.strip()
+        if "aperio.MPP" in props:
+            props["openslide.mpp-x"] = props["openslide.mpp-y"] = props["aperio.MPP"]
+        return props
+
+    def tile_ranges(self, level):
+        """(offsets, byte counts) of the level's tiles as the file lists them, row-major."""
+        lv = self._levels[level]
+        return lv.offsets.copy(), lv.counts.copy()
+
+    def close(self):
+        if self._fd is not None:
+            os.close(self._fd)
+            self._fd = None
+        self._pinned = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- pixels --
+    def _origin(self, level, location):
+        ds = self.dimensions[0] / self._levels[level].width
+        return int(location[0] / ds), int(location[1] / ds)
+
+    def read_regions(self, locations, level, size):
+        """uint8 [k, h, w, 4] on ``self.device``: region i is ``read_region(locations[i], level, size)``.  The tiles the batch
+        touches are decoded once per chunk; a batch is cut between regions into chunks whose device workspace (planes,
+        coefficients, uploaded bytes) stays under ``workspace_budget`` bytes, and a batch that fits decodes every tile once.
+        Outside the budget: the returned tensor itself (k h w 4 bytes), and a single region whose own tiles need more than the
+        budget -- a region is never split, so it is decoded in one chunk whatever it takes (the whole-level read of the slide
+        mask is one).  A chunk's scans are addressed by int32 offsets: chunks are cut below 2 GiB of scan bytes, and one region
+        above that is refused with a ValueError.  The tile bytes go up in one pinned buffer with the tile table.  A tile that does not decode raises ``TileDecodeError`` (a RuntimeError naming
+        the level and the tile) after the whole batch has run; every other tile of the batch is unaffected."""
+        import torch
+        _lib.require_gpu()
+        if self._fd is None:
+            raise ValueError("the slide is closed")
+        if not 0 <= int(level) < self.level_count:
+            raise ValueError(f"level {level}: the slide has levels 0..{self.level_count - 1}")
+        lv = self._levels[int(level)]
+        w, h = int(size[0]), int(size[1])
+        if w < 1 or h < 1 or w > _C["SQ_JPEG_MAX_REGION"] or h > _C["SQ_JPEG_MAX_REGION"]:
+            raise ValueError(f"region size {size}: extents in 1..{_C['SQ_JPEG_MAX_REGION']}")
+        origins = [self._origin(level, xy) for xy in locations]
+        if any(abs(x) >= 1 << 30 or abs(y) >= 1 << 30 for x, y in origins):
+            raise ValueError("region origin beyond 2^30 pixels")
+        k = len(origins)
+        dev = torch.device(self.device)
+        out = torch.empty((k, h, w, 4), dtype=torch.uint8, device=dev)
+        self.last_batch_tiles = []
+        if k == 0:
+            return out
+        touched = []
+        for x0, y0 in origins:
+            tx0, tx1 = max(x0, 0) // lv.tile_w, min(x0 + w - 1, lv.width - 1) // lv.tile_w
+            ty0, ty1 = max(y0, 0) // lv.tile_h, min(y0 + h - 1, lv.height - 1) // lv.tile_h
+            touched.append([ty * lv.tiles_x + tx for ty in range(ty0, ty1 + 1) for tx in range(tx0, tx1 + 1)]
+                           if x0 < lv.width and y0 < lv.height and x0 + w > 0 and y0 + h > 0 else [])
+        L = _lib.lib()
+        self._tile_info(lv, 0)                                              # fixes the level's sampling
+        per_tile = L.sq_jpeg_workspace_bytes(2, 1, lv.tile_w, lv.tile_h, lv.hs, lv.vs) - L.sq_jpeg_workspace_bytes(1, 1, lv.tile_w, lv.tile_h, lv.hs, lv.vs) \
+            + L.sq_jpeg_planes_bytes(1, lv.tile_w, lv.tile_h, lv.hs, lv.vs) + int(lv.counts.max())
+        max_tiles = max(1, min(self.workspace_budget // per_tile, SCAN_BYTES_MAX // (int(lv.counts.max()) + 3)))
+        failures, start = [], 0
+        while start < k:
+            tiles, stop = set(), start
+            while stop < k:
+                new = [t for t in touched[stop] if t not in tiles]
+                if stop > start and len(tiles) + len(new) > max_tiles:
+                    break
+                tiles.update(new)
+                stop += 1
+            failures += self._decode_chunk(lv, level, sorted(tiles), origins[start:stop], out[start:stop])
+            start = stop
+        if failures:
+            names = ", ".join(f"({tx}, {ty}): {STATUS_NAMES.get(st, st)}" for _, tx, ty, st in failures[:8])
+            bad = {ty * lv.tiles_x + tx for _, tx, ty, _ in failures}
+            first = min(i for i, t in enumerate(touched) if bad & set(t))
+            raise TileDecodeError(f"{self.path}: level {level}: {len(failures)} tile(s) did not decode: tile {names}", failures, out, first)
+        return out
+
+    def _plan(self, lv, tiles):
+        """The device inputs of a set of tiles (row-major tile numbers) but for the scan bytes: the slot order (longest scan
+        first, so that the lanes of a wave end together), the tile table, the distinct table sets, the size of the scans buffer
+        and the level's tile -> slot map."""
+        infos = [self._tile_info(lv, t) for t in tiles]
+        order = sorted(range(len(tiles)), key=lambda i: -infos[i][1])
+        set_index, sets = {}, []
+        table = np.zeros((len(tiles), TILE_WORDS), dtype=np.int32)
+        slot_map = np.full(lv.tiles_x * lv.tiles_y, -1, dtype=np.int32)
+        at = 0
+        for slot, i in enumerate(order):
+            off, length, tables, restart, sel = infos[i]
+            if tables not in set_index:
+                set_index[tables] = len(sets)
+                sets.append(tables)
+            if at + length > SCAN_BYTES_MAX:
+                raise ValueError(f"{self.path}: the tiles of one region hold more than {SCAN_BYTES_MAX} bytes of scans (the tile table's "
+                                 f"offsets are int32): read the region in parts")
+            table[slot] = (at, length, set_index[tables], restart, sel, 0, 0, 0)
+            slot_map[tiles[i]] = slot
+            at += (length + 3) & ~3
+        return order, table, sets, max((at + 15) & ~15, 16), slot_map
+
+    def _read_scans(self, lv, level, tiles, order, table, host):
+        """The entropy-coded bytes of the planned tiles from the file into `host` (uint8 numpy [scans_bytes])."""
+        view = memoryview(host)
+        for slot, i in enumerate(order):
+            a, length = int(table[slot, 0]), int(table[slot, 1])
+            got = os.preadv(self._fd, [view[a:a + length]], self._tile_info(lv, tiles[i])[0])
+            if got != length:
+                raise WsiFormatError(f"{self.path}: level {level} tile ({tiles[i] % lv.tiles_x}, {tiles[i] // lv.tiles_x}): read {got} of {length} bytes")
+            host[a + length:a + ((length + 3) & ~3)] = 0
+
+    def tile_job(self, level, tiles=None):
+        """What ``read_regions`` uploads for `tiles` (row-major tile numbers, default all) of `level`, on the host: a dict with
+        ``geom`` (tile_w, tile_h, hs, vs), ``transform``, ``tiles`` (the tile number of every slot), ``table`` int32 [n, 8],
+        ``sets`` (list of table-set byte strings) and ``scans`` (uint8 array).  Needs no GPU: the host check program and the
+        tests read it."""
+        lv = self._levels[level]
+        tiles = list(range(lv.tiles_x * lv.tiles_y)) if tiles is None else list(tiles)
+        order, table, sets, scans_bytes, _ = self._plan(lv, tiles)
+        scans = np.zeros(scans_bytes, dtype=np.uint8)
+        self._read_scans(lv, level, tiles, order, table, scans)
+        return dict(geom=(lv.tile_w, lv.tile_h, lv.hs, lv.vs), transform=lv.transform, tiles=[tiles[i] for i in order], table=table,
+                    sets=sets, scans=scans)
+
+    def _decode_chunk(self, lv, level, tiles, origins, out):
+        """Decode `tiles` (row-major tile numbers) and compose `origins` into `out`; returns the failing tiles."""
+        import torch
+        L = _lib.lib()
+        dev = out.device
+        k, h, w = out.shape[0], out.shape[1], out.shape[2]
+        regions = np.asarray(origins, dtype=np.int32).reshape(-1, 2)
+        if not tiles:
+            out.zero_()
+            return []
+        order, table, sets, scans_bytes, slot_map = self._plan(lv, tiles)
+        n = len(tiles)
+        parts = [table.tobytes(), b"".join(sets), slot_map.tobytes(), regions.tobytes()]
+        parts = [p + b"\0" * (-len(p) % 16) for p in parts]                   # the scans behind them start 16-byte aligned
+        head = sum(len(p) for p in parts)
+        total = head + scans_bytes
+        if self._pinned is None or self._pinned.numel() < total:
+            self._pinned = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
+        host = self._pinned.numpy()
+        host[:head] = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        self._read_scans(lv, level, tiles, order, table, host[head:total])
+        self.last_batch_tiles += [(t % lv.tiles_x, t // lv.tiles_x) for t in tiles]
+        blob = self._pinned[:total].to(dev, non_blocking=True)
+        base = blob.data_ptr()
+        o_sets = len(parts[0])
+        o_slots = o_sets + len(parts[1])
+        o_regions = o_slots + len(parts[2])
+        geom = (lv.tile_w, lv.tile_h, lv.hs, lv.vs)
+        need = L.sq_jpeg_workspace_bytes(n, len(sets), *geom)
+        plane_bytes = L.sq_jpeg_planes_bytes(n, *geom)
+        if need == 0 or plane_bytes == 0:
+            raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        planes = torch.empty(plane_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        import ctypes
+        with torch.cuda.device(dev):
+            stream = _lib.stream_ptr(dev)
+            _lib.check(L.sq_jpeg_decode_tiles(ctypes.c_void_p(base + head), scans_bytes, ctypes.c_void_p(base), n, ctypes.c_void_p(base + o_sets),
+                                              len(sets), *geom, _lib.ptr(planes), _lib.ptr(status), _lib.ptr(ws), need, stream))
+            _lib.check(L.sq_jpeg_compose_regions(_lib.ptr(planes), n, *geom, lv.transform, ctypes.c_void_p(base + o_slots), lv.tiles_x,
+                                                 lv.tiles_y, lv.width, lv.height, ctypes.c_void_p(base + o_regions), k, h, w, _lib.ptr(out),
+                                                 stream))
+        st = status.cpu().numpy()            # waits for the chunk: the pinned buffer may be written again
+        return [(level, tiles[order[s]] % lv.tiles_x, tiles[order[s]] // lv.tiles_x, int(st[s])) for s in np.flatnonzero(st)]
+
+    def read_region(self, location, level, size):
+        """``openslide.OpenSlide.read_region``: an RGBA ``PIL.Image`` of `size` = (width, height) pixels of `level` whose corner
+        is at `location` in level-0 pixels (module docstring: a fractional level origin is truncated, not interpolated).
+        ``read_regions`` of one region, downloaded."""
+        from PIL import Image
+        return Image.fromarray(self.read_regions([location], level, size)[0].cpu().numpy(), "RGBA")
+
+
+MISSING_OPENSLIDE = ("openslide-python is required to read whole-slide images (pip install openslide-python); "
+                     "sequoia-pub_amd.patchgen.extract_patches and embed_slide also accept any object with OpenSlide's interface.  "
+                     "JPEG-tiled TIFF and Aperio SVS files open without it: pass --reader tiff.")
+
+
+def open_slide(path, reader="openslide", device="cuda:0"):
+    """The slide object of the CLIs' ``--reader`` flag: 'tiff' is ``TiffSlide``, 'openslide' is ``openslide.OpenSlide`` (and a
+    SystemExit that points to ``--reader tiff`` when openslide-python is not installed)."""
+    if reader == "tiff":
+        return TiffSlide(path, device=device)
+    if reader != "openslide":
+        raise ValueError(f"reader={reader!r}: 'openslide' or 'tiff'")
+    try:
+        import openslide
+    except ImportError:
+        raise SystemExit(MISSING_OPENSLIDE) from None
+    return openslide.OpenSlide(path)
+
+
