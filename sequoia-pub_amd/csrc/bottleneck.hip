@@ -28,26 +28,11 @@
 // Results are bit-identical to the three separate launches of the GEMM engine (same bf16 roundings of t2 / y, same
 // ascending-K fp32 accumulation): tests/test_gpu_resnet.py::test_fused_bottleneck_tail_is_bit_identical.
 #include "gemm.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-__device__ __forceinline__ u32x2 lds64(const char* p) { return *reinterpret_cast<const u32x2*>(p); }
-__device__ __forceinline__ void st_lds64(char* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
-
-__device__ __forceinline__ f32x16 mma(const u32x4& w, const u32x4& x, f32x16 acc) {
-    union { u32x4 u; bf16x8 h; } a, b;
-    a.u = w; b.u = x;
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-}
 
 struct BtlArgs {
     const bf16_t* t1;      // [P, 64]   input of the 3x3
@@ -84,29 +69,25 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
 
-    int t;
-    {   // each XCD (block id % 8) walks a contiguous run of tiles: neighbouring tiles share halo rows in its L2
-        const int b = blockIdx.x, q = p.tiles >> 3, r = p.tiles & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, p.tiles);     // neighbouring tiles share halo rows in the XCD's L2
     const int p0 = t * 128;
     const int W = p.W;
     const int halo0 = p0 - W - 1;                  // flat pixel of LDS row 0 of the halo tile
     const int halo_slots = (128 + 2 * W + 2) * 8;  // 16-byte slots
 
-    const auto rsT1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, p.P * 128, 0x00020000);
-    const auto rsRes = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, p.P * 512, 0x00020000);
-    const auto rsW2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, (int)p.w2_bytes, 0x00020000);
-    const auto rsW3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, (int)p.w3_bytes, 0x00020000);
-    const auto rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1n, 0, (int)p.w1n_bytes, 0x00020000);
-    const auto rsWd = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.wd : p.w3), 0, (int)(DS ? p.wd_bytes : p.w3_bytes), 0x00020000);
-    const auto rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.xin : p.t1), 0, p.P * 128, 0x00020000);
+    const auto rsT1 = sq_rsrc(p.t1, p.P * 128);
+    const auto rsRes = sq_rsrc(p.res, p.P * 512);
+    const auto rsW2 = sq_rsrc(p.w2, (int)p.w2_bytes);
+    const auto rsW3 = sq_rsrc(p.w3, (int)p.w3_bytes);
+    const auto rsW1 = sq_rsrc(p.w1n, (int)p.w1n_bytes);
+    const auto rsWd = sq_rsrc(DS ? p.wd : p.w3, (int)(DS ? p.wd_bytes : p.w3_bytes));
+    const auto rsX = sq_rsrc(DS ? p.xin : p.t1, p.P * 128);
     // stores go through descriptors as well: rows past P are dropped by the range check, no branch per piece (-4...5 %
     // for three of the four instantiations; hipcc schedules the branch-free <64, false> with 168 registers and no
     // fragment read-ahead, +14 %, so that one keeps the guarded stores)
     constexpr bool BRANCHY = CN == 64 && !DS;
-    const auto rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.P * 512, 0x00020000);
-    const auto rsT1n = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1n, 0, p.P * CN * 2, 0x00020000);
+    const auto rsY = sq_rsrc(p.y, p.P * 512);
+    const auto rsT1n = sq_rsrc(p.t1n, p.P * CN * 2);
 
     // ---- weight chunk stream -------------------------------------------------------------------------------
     // chunk ids: 0..4 = 3x3 taps (2i, 2i+1), rows [64 n][256 B];  then per 128-channel slice nc of y:
@@ -156,7 +137,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int row = q >> 3, c = (q & 7) ^ ((row >> 1) & 7);
         const int px = halo0 + row;
         const bool ok = q < halo_slots && px >= 0 && px < p.P;
-        glds16(rsT1, R0 + u * 4096 + wave * 1024, ok ? (uint32_t)(px * 64 + c * 8) * 2u : OOB);
+        glds16(rsT1, R0 + u * 4096 + wave * 1024, ok ? (uint32_t)(px * 64 + c * 8) * 2u : SQ_OOB);
     }
     issue_chunk(0, 0);
 
@@ -211,7 +192,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
                         const int n = nt * 32 + l31;
-                        acc2[nt] = mma(lds128(wb + n * 256 + ((c16 ^ (n & 15)) << 4)), x, acc2[nt]);
+                        acc2[nt] = mfma_bf16(lds128(wb + n * 256 + ((c16 ^ (n & 15)) << 4)), x, acc2[nt]);
                     }
                 }
             }
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 const int q = u * 64 + lane;
                 const int ml = q >> 3, c = (q & 7) ^ ((ml >> 1) & 7);
                 const int pr = p0 + wave * 32 + ml;
-                glds16(rsX, xreg + u * 1024, pr < p.P ? (uint32_t)(pr * 64 + c * 8) * 2u : OOB);
+                glds16(rsX, xreg + u * 1024, pr < p.P ? (uint32_t)(pr * 64 + c * 8) * 2u : SQ_OOB);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             f32x16 accd[4];
@@ -266,7 +247,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                     for (int nt = 0; nt < 4; ++nt) {
                         const int n = nt * 32 + l31;
-                        accd[nt] = mma(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, accd[nt]);
+                        accd[nt] = mfma_bf16(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, accd[nt]);
                     }
                 }
             }
@@ -294,7 +275,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 const int q = u * 64 + lane;
                 const int row = wave * 32 + (q >> 4), c = (q & 15) ^ (row & 15);
                 const int pr = p0 + row;
-                glds16(rsRes, R0 + (wave * 32 + u * 4) * 256, pr < p.P ? (uint32_t)(pr * 256 + nc * 128 + c * 8) * 2u : OOB);
+                glds16(rsRes, R0 + (wave * 32 + u * 4) * 256, pr < p.P ? (uint32_t)(pr * 256 + nc * 128 + c * 8) * 2u : SQ_OOB);
             }
         }
         f32x16 accy[4];
@@ -312,7 +293,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
                     const int n = nt * 32 + l31;
-                    accy[nt] = mma(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, accy[nt]);
+                    accy[nt] = mfma_bf16(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, accy[nt]);
                 }
             }
         }
@@ -365,7 +346,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
                         const int n = nt * 32 + l31;
-                        acc1n[nt] = mma(lds128(wb + n * 256 + (((2 * ks + lh) ^ (n & 15)) << 4)), x, acc1n[nt]);
+                        acc1n[nt] = mfma_bf16(lds128(wb + n * 256 + (((2 * ks + lh) ^ (n & 15)) << 4)), x, acc1n[nt]);
                     }
                 }
             } else {
@@ -375,7 +356,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                     for (int nt = 0; nt < 4; ++nt) {
                         const int n = nt * 32 + l31;
-                        acc1n[nt] = mma(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, acc1n[nt]);
+                        acc1n[nt] = mfma_bf16(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, acc1n[nt]);
                     }
                 }
             }
@@ -454,8 +435,7 @@ int sq_launch_bottleneck_tail_c64(const bf16_t* t1, const bf16_t* res, bf16_t* y
     a.t1 = t1; a.res = res; a.y = y; a.t1n = t1n; a.w2 = w2; a.w3 = w3; a.w1n = w1n; a.b2 = b2; a.b3 = b3; a.b1n = b1n;
     a.xin = xin; a.wd = wd; a.bd = bd;
     a.P = (int)P; a.W = W; a.HW = H * W; a.tiles = (int)((P + 127) / 128);
-    auto clamp = [](size_t b) { return (uint32_t)(b < 0x7fffffffu ? b : 0x7fffffffu); };
-    a.w2_bytes = clamp(w2_bytes); a.w3_bytes = clamp(w3_bytes); a.w1n_bytes = clamp(w1n_bytes); a.wd_bytes = clamp(wd_bytes);
+    a.w2_bytes = sq_desc_extent(w2_bytes); a.w3_bytes = sq_desc_extent(w3_bytes); a.w1n_bytes = sq_desc_extent(w1n_bytes); a.wd_bytes = sq_desc_extent(wd_bytes);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
         SQ_HIP_CHECK(hipFuncSetAttribute((const void*)btl_tail_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
@@ -464,13 +444,13 @@ int sq_launch_bottleneck_tail_c64(const bf16_t* t1, const bf16_t* res, bf16_t* y
         SQ_HIP_CHECK(hipFuncSetAttribute((const void*)btl_tail_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         attr.done();
     }
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "btl_tail_c64_cn%d%s_P%lld", cn, ds ? "_ds" : "", P);
         const double flops = 2.0 * P * (576.0 * 64 + 64.0 * 256 + 256.0 * cn + (ds ? 64.0 * 256 : 0.0));
         const double bytes = (double)P * 2.0 * (64 + (ds ? 64 : 256) + 256 + cn) + 2.0 * (64 * 576 + 256 * 64 * (ds ? 2 : 1) + cn * 256);
-        prof = sq_prof_begin(name, flops, bytes, stream);
+        prof.begin(name, flops, bytes);
     }
     const dim3 grid(a.tiles), block(256);
     if (cn == 64 && !ds) hipLaunchKernelGGL((btl_tail_kernel<64, false>), grid, block, LDS_BYTES, stream, a);
@@ -478,6 +458,5 @@ int sq_launch_bottleneck_tail_c64(const bf16_t* t1, const bf16_t* res, bf16_t* y
     else if (cn == 64) hipLaunchKernelGGL((btl_tail_kernel<64, true>), grid, block, LDS_BYTES, stream, a);
     else hipLaunchKernelGGL((btl_tail_kernel<128, true>), grid, block, LDS_BYTES, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

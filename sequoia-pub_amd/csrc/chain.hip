@@ -15,26 +15,12 @@
 //   * outputs leave through buffer descriptors: rows past P are dropped by the range check, no branch per store.
 // Bit-identical to the two GEMM launches it replaces (same bf16 rounding of y, same ascending-K accumulation).
 #include "gemm.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-__device__ __forceinline__ u32x2 lds64(const char* p) { return *reinterpret_cast<const u32x2*>(p); }
-__device__ __forceinline__ void st_lds64(char* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
-__device__ __forceinline__ f32x16 mma(const u32x4& w, const u32x4& x, f32x16 acc) {
-    union { u32x4 u; bf16x8 h; } a, b;
-    a.u = w; b.u = x;
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-}
 
 struct ChainArgs {
     const bf16_t* t2;      // [P, 128]
@@ -67,18 +53,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void btl_chain_kernel(con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
     int t;
-    {
+    {   // sq_xcd_tile (tile_walk.h) written out: through the call hipcc allocates this kernel's scalar registers differently
         const int b = blockIdx.x, q = p.tiles >> 3, r = p.tiles & 7, xcd = b & 7, idx = b >> 3;
         t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
     const int p0 = t * TP;
-    const auto rsT2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, p.P * C * 2, 0x00020000);
-    const auto rsRes = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, p.P * C4 * 2, 0x00020000);
-    const auto rsW3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, (int)p.w3_bytes, 0x00020000);
-    const auto rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1n, 0, (int)p.w1n_bytes, 0x00020000);
+    const auto rsT2 = sq_rsrc(p.t2, p.P * C * 2);
+    const auto rsRes = sq_rsrc(p.res, p.P * C4 * 2);
+    const auto rsW3 = sq_rsrc(p.w3, (int)p.w3_bytes);
+    const auto rsW1 = sq_rsrc(p.w1n, (int)p.w1n_bytes);
     // stores go through descriptors as well: rows past P are dropped by the range check, no branch per piece
-    const auto rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.P * C4 * 2, 0x00020000);
-    const auto rsT1n = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1n, 0, p.P * CN * 2, 0x00020000);
+    const auto rsY = sq_rsrc(p.y, p.P * C4 * 2);
+    const auto rsT1n = sq_rsrc(p.t1n, p.P * CN * 2);
 
     // chunk stream: per 64-channel slice s of y:  B_s = w3 rows [64 s, 64 s + 64) as [64 n][256 B];
     //                                             C_s,h = w1' rows [128 h, 128 h + 128), columns [64 s, 64 s + 64) as [128 n][128 B]
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void btl_chain_kernel(con
         const int q = u * 64 + lane;
         const int row = wave * 32 + (q >> 4), c = (q & 15) ^ (row & 15);
         const int pr = p0 + row;
-        glds16(rsT2, A1 + (wave * 32 + u * 4) * 256, pr < p.P ? (uint32_t)(pr * C + c * 8) * 2u : OOB);
+        glds16(rsT2, A1 + (wave * 32 + u * 4) * 256, pr < p.P ? (uint32_t)(pr * C + c * 8) * 2u : SQ_OOB);
     }
     issue_chunk(0, 0);
 
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void btl_chain_kernel(con
             const int q = u * 64 + lane;
             const int row = wave * 32 + (q >> 3), c = (q & 7) ^ ((row >> 1) & 7);
             const int pr = p0 + row;
-            glds16(rsRes, XY + (wave * 32 + u * 8) * 128, pr < p.P ? (uint32_t)(pr * C4 + s * 64 + c * 8) * 2u : OOB);
+            glds16(rsRes, XY + (wave * 32 + u * 8) * 128, pr < p.P ? (uint32_t)(pr * C4 + s * 64 + c * 8) * 2u : SQ_OOB);
         }
         f32x16 accy[2];
 #pragma unroll
@@ -146,7 +132,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void btl_chain_kernel(con
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const int n = nt * 32 + l31;
-                    accy[nt] = mma(lds128(wb + n * 256 + (((2 * ks + lh) ^ (n & 15)) << 4)), x, accy[nt]);
+                    accy[nt] = mfma_bf16(lds128(wb + n * 256 + (((2 * ks + lh) ^ (n & 15)) << 4)), x, accy[nt]);
                 }
             }
         }
@@ -195,7 +181,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void btl_chain_kernel(con
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
                     const int n = nt * 32 + l31;
-                    acc1n[h * 4 + nt] = mma(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, acc1n[h * 4 + nt]);
+                    acc1n[h * 4 + nt] = mfma_bf16(lds128(wb + n * 128 + (((2 * ks + lh) ^ ((n >> 1) & 7)) << 4)), x, acc1n[h * 4 + nt]);
                 }
             }
         }
@@ -242,8 +228,7 @@ int sq_launch_bottleneck_chain_c128(const bf16_t* t2, const bf16_t* res, bf16_t*
     const int nw = cn == 256 ? 8 : 4;               // measured against the other count: 304 vs 321 us / 249 vs 257 us
     const int tp = 32 * nw;
     a.P = (int)P; a.tiles = (int)((P + tp - 1) / tp);
-    auto clamp = [](size_t b) { return (uint32_t)(b < 0x7fffffffu ? b : 0x7fffffffu); };
-    a.w3_bytes = clamp(w3_bytes); a.w1n_bytes = clamp(w1n_bytes);
+    a.w3_bytes = sq_desc_extent(w3_bytes); a.w1n_bytes = sq_desc_extent(w1n_bytes);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
         SQ_HIP_CHECK(hipFuncSetAttribute((const void*)btl_chain_kernel<128, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(4)));
@@ -252,11 +237,11 @@ int sq_launch_bottleneck_chain_c128(const bf16_t* t2, const bf16_t* res, bf16_t*
         SQ_HIP_CHECK(hipFuncSetAttribute((const void*)btl_chain_kernel<256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(8)));
         attr.done();
     }
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "btl_chain_c128_cn%d_P%lld", cn, P);
-        prof = sq_prof_begin(name, 2.0 * P * (128.0 * 512 + 512.0 * cn), (double)P * 2.0 * (128 + 512 + 512 + cn) + 2.0 * (512 * 128 + cn * 512), stream);
+        prof.begin(name, 2.0 * P * (128.0 * 512 + 512.0 * cn), (double)P * 2.0 * (128 + 512 + 512 + cn) + 2.0 * (512 * 128 + cn * 512));
     }
     if (nw == 4) {
         if (cn == 128) hipLaunchKernelGGL((btl_chain_kernel<128, 4>), dim3(a.tiles), dim3(256), lds_bytes(4), stream, a);
@@ -266,6 +251,5 @@ int sq_launch_bottleneck_chain_c128(const bf16_t* t2, const bf16_t* res, bf16_t*
         else hipLaunchKernelGGL((btl_chain_kernel<256, 8>), dim3(a.tiles), dim3(512), lds_bytes(8), stream, a);
     }
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

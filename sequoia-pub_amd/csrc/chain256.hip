@@ -18,25 +18,11 @@
 //     133 KiB of LDS, one block of 8 waves per CU.
 // Bit-identical to the two GEMM launches it replaces (same bf16 rounding of y, same ascending-K accumulation).
 #include "gemm.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-__device__ __forceinline__ u32x2 lds64(const char* p) { return *reinterpret_cast<const u32x2*>(p); }
-__device__ __forceinline__ void st_lds64(char* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
-__device__ __forceinline__ f32x16 mma(const u32x4& w, const u32x4& x, f32x16 acc) {
-    union { u32x4 u; bf16x8 h; } a, b;
-    a.u = w; b.u = x;
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-}
 
 struct Chain256Args {
     const bf16_t* t2;      // [P, 256]
@@ -69,17 +55,13 @@ __global__ __launch_bounds__(512, 1) void btl_chain256_kernel(const Chain256Args
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pg = wave >> 1, h = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
-    int t;
-    {
-        const int b = blockIdx.x, q = p.tiles >> 3, r = p.tiles & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, p.tiles);
     const int p0 = t * 128;
-    const auto rsRes = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, p.P * C4 * 2, 0x00020000);
-    const auto rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.P * C4 * 2, 0x00020000);      // rows past P: stores dropped
-    const auto rsT1n = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1n, 0, p.P * CN * 2, 0x00020000);
-    const auto rsW3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, (int)p.w3_bytes, 0x00020000);
-    const auto rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1n, 0, (int)p.w1n_bytes, 0x00020000);
+    const auto rsRes = sq_rsrc(p.res, p.P * C4 * 2);
+    const auto rsY = sq_rsrc(p.y, p.P * C4 * 2);      // rows past P: stores dropped
+    const auto rsT1n = sq_rsrc(p.t1n, p.P * CN * 2);
+    const auto rsW3 = sq_rsrc(p.w3, (int)p.w3_bytes);
+    const auto rsW1 = sq_rsrc(p.w1n, (int)p.w1n_bytes);
 
     auto issue_chunk = [&](int id) {
         char* dst = WB + (id % NBUF) * WB_BYTES + wave * 1024;
@@ -121,7 +103,7 @@ __global__ __launch_bounds__(512, 1) void btl_chain256_kernel(const Chain256Args
         for (int u = 0; u < 2; ++u) {
             const int row = u * 16 + (lane >> 2), c = (lane & 3) ^ ((row >> 2) & 3);
             const int pr = p0 + pg * 32 + row;
-            glds16(rsRes, myXY + (s & 1) * XY1_BYTES + u * 1024, pr < p.P ? (uint32_t)(pr * C4 + s * 64 + h * 32 + c * 8) * 2u : OOB);
+            glds16(rsRes, myXY + (s & 1) * XY1_BYTES + u * 1024, pr < p.P ? (uint32_t)(pr * C4 + s * 64 + h * 32 + c * 8) * 2u : SQ_OOB);
         }
     };
     issue_identity(0);
@@ -153,7 +135,7 @@ __global__ __launch_bounds__(512, 1) void btl_chain256_kernel(const Chain256Args
             const char* wrow = WB + (j % NBUF) * WB_BYTES + n * 512;
             const int sw = n & 15;
 #pragma unroll
-            for (int ks = 0; ks < 16; ++ks) accy = mma(lds128(wrow + (((2 * ks + lh) ^ sw) << 4)), xr[ks], accy);
+            for (int ks = 0; ks < 16; ++ks) accy = mfma_bf16(lds128(wrow + (((2 * ks + lh) ^ sw) << 4)), xr[ks], accy);
         }
         {
             char* row = xy + (pg * 2 + h) * 2048 + l31 * 64;
@@ -193,7 +175,7 @@ __global__ __launch_bounds__(512, 1) void btl_chain256_kernel(const Chain256Args
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
                     const int n = 128 * h + 32 * nt + l31;
-                    acc1n[nt] = mma(lds128(wb + n * 128 + ((kc ^ ((n >> 1) & 7)) << 4)), x, acc1n[nt]);
+                    acc1n[nt] = mfma_bf16(lds128(wb + n * 128 + ((kc ^ ((n >> 1) & 7)) << 4)), x, acc1n[nt]);
                 }
             }
         }
@@ -236,21 +218,19 @@ int sq_launch_bottleneck_chain_c256(const bf16_t* t2, const bf16_t* res, bf16_t*
     Chain256Args a;
     a.t2 = t2; a.res = res; a.y = y; a.t1n = t1n; a.w3 = w3; a.w1n = w1n; a.b3 = b3; a.b1n = b1n;
     a.P = (int)P; a.tiles = (int)((P + 127) / 128);
-    auto clamp = [](size_t b) { return (uint32_t)(b < 0x7fffffffu ? b : 0x7fffffffu); };
-    a.w3_bytes = clamp(w3_bytes); a.w1n_bytes = clamp(w1n_bytes);
+    a.w3_bytes = sq_desc_extent(w3_bytes); a.w1n_bytes = sq_desc_extent(w1n_bytes);
     static SqDevOnce attr;       // hipFuncSetAttribute is per device
     if (attr.needed()) {
         SQ_HIP_CHECK(hipFuncSetAttribute((const void*)btl_chain256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         attr.done();
     }
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "btl_chain_c256_cn256_P%lld", P);
-        prof = sq_prof_begin(name, 2.0 * P * (256.0 * 1024 + 1024.0 * 256), (double)P * 2.0 * (256 + 1024 + 1024 + 256) + 2.0 * (1024 * 256 + 256 * 1024), stream);
+        prof.begin(name, 2.0 * P * (256.0 * 1024 + 1024.0 * 256), (double)P * 2.0 * (256 + 1024 + 1024 + 256) + 2.0 * (1024 * 256 + 256 * 1024));
     }
     hipLaunchKernelGGL(btl_chain256_kernel, dim3(a.tiles), dim3(512), LDS_BYTES, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

@@ -31,6 +31,7 @@
 // launches it replaces: bit-identical results (tests/test_gpu_x3.py).
 #include "gemm.h"
 #include "x3_fmt.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -40,14 +41,6 @@ extern int g_dbg;                // sq_dbg_set key 1 (gemm.hip)
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // n is a constant after unrolling: the switch folds to one s_waitcnt
 __device__ __forceinline__ void wait_vm_n(int n) {
     switch (n) {
@@ -104,10 +97,10 @@ __global__ __launch_bounds__(256, 2) void chain_x3_kernel(const ChainX3Args p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const auto rsTh = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, (int)p.t2_bytes, 0x00020000);
-    const auto rsTl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.t2 + p.plT2), 0, (int)p.t2_bytes, 0x00020000);
-    const auto rsXh = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.xin : p.t2), 0, (int)p.t2_bytes, 0x00020000);
-    const auto rsXl = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.xin + p.plX : p.t2 + p.plT2), 0, (int)p.t2_bytes, 0x00020000);
+    const auto rsTh = __builtin_amdgcn_make_buffer_rsrc((void*)p.t2, 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
+    const auto rsTl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.t2 + p.plT2), 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
+    const auto rsXh = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.xin : p.t2), 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
+    const auto rsXl = __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? p.xin + p.plX : p.t2 + p.plT2), 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
 
     // B fragments of the second product come straight from L2 into registers (w1' is 64 / 128 KiB: no room in LDS beside the
     // y image), four k-steps per group, the next group requested while the current one is multiplied, the first one before
@@ -134,6 +127,7 @@ __global__ __launch_bounds__(256, 2) void chain_x3_kernel(const ChainX3Args p) {
     // memory-side cache, never by DRAM; the launch is bound inside the CU).
     int tile_id = blockIdx.x;
     if (p.xcd_walk == 1) {
+        // sq_xcd_tile (tile_walk.h) written out: through the call hipcc schedules this kernel differently
         const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = blockIdx.x & 7, i = blockIdx.x >> 3;
         tile_id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
     } else if (p.xcd_walk > 1) {
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void chain_x3_kernel(const ChainX3Args p) {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             char* buf = smem + kt * KT_BYTES + a_off + wave * 1024;
-            const uint32_t oa = m < p.P ? ((uint32_t)m * K1 + (uint32_t)(kt * 32 + gc * 8)) * 2u : OOB;
+            const uint32_t oa = m < p.P ? ((uint32_t)m * K1 + (uint32_t)(kt * 32 + gc * 8)) * 2u : SQ_OOB;
             glds16(ah_, buf, oa);
             glds16(al_, buf + A_PLANE, oa);
         }
@@ -202,10 +196,10 @@ __global__ __launch_bounds__(256, 2) void chain_x3_kernel(const ChainX3Args p) {
         char* const HB = smem;
         char* const WR = smem + 2 * HCB;
         const int W = p.W;
-        const auto rs1h = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, (int)p.t2_bytes, 0x00020000);
-        const auto rs1l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.t1 + p.plT1), 0, (int)p.t2_bytes, 0x00020000);
-        const auto rs2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, (int)p.w2_bytes, 0x00020000);
-        const auto rs2l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w2 + p.plW), 0, (int)p.w2_bytes, 0x00020000);
+        const auto rs1h = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1, 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
+        const auto rs1l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.t1 + p.plT1), 0, (int)p.t2_bytes, SQ_RSRC_FLAGS);
+        const auto rs2h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, (int)p.w2_bytes, SQ_RSRC_FLAGS);
+        const auto rs2l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w2 + p.plW), 0, (int)p.w2_bytes, SQ_RSRC_FLAGS);
         {
             const int halo0 = p0 - W - 1, halo_slots = (PX + 2 * W + 2) * 4;
 #pragma unroll
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void chain_x3_kernel(const ChainX3Args p) {
                     const int row = sl >> 2, c = (sl & 3) ^ ((row >> 2) & 3);
                     const int px = halo0 + row;
                     const bool ok = sl < halo_slots && px >= 0 && px < p.P;
-                    const uint32_t off = ok ? ((uint32_t)px * 64u + (uint32_t)(cb * 32 + c * 8)) * 2u : OOB;
+                    const uint32_t off = ok ? ((uint32_t)px * 64u + (uint32_t)(cb * 32 + c * 8)) * 2u : SQ_OOB;
                     char* dst = HB + cb * HCB + u * 4096 + wave * 1024;
                     glds16(rs1h, dst, off);
                     glds16(rs1l, dst + HPL, off);
@@ -574,9 +568,8 @@ int sq_launch_chain_x3_c64(int f16, const uint16_t* t2, long long plT2, const ui
     a.t2 = t2; a.plT2 = plT2; a.w3 = frag; a.w1n = frag + FRAG_W1; a.plW = FRAG; a.b3 = b3; a.cs3 = cs3; a.b1n = b1n; a.cs1n = cs1n;
     a.res = res; a.plRes = plRes; a.y = y; a.plY = plY; a.t1n = t1n; a.plT1n = plT1n; a.P = (int)P;
     a.t2_bytes = (uint32_t)(P * K1 * 2);
-    auto clamp = [](size_t b) { return (uint32_t)(b < 0x7fffffffu ? b : 0x7fffffffu); };
-    a.w3_bytes = clamp(w3_bytes);
-    a.xin = xin; a.plX = plX; a.wd = frag + FRAG_WD; a.bd = bd; a.csd = csd; a.wd_bytes = clamp(wd_bytes);
+    a.w3_bytes = sq_desc_extent(w3_bytes);
+    a.xin = xin; a.plX = plX; a.wd = frag + FRAG_WD; a.bd = bd; a.csd = csd; a.wd_bytes = sq_desc_extent(wd_bytes);
     a.t1 = t1; a.plT1 = plT1; a.w2 = frag + FRAG_W2; a.b2 = b2; a.cs2 = cs2; a.w2_bytes = (uint32_t)((FRAG - FRAG_W2) * 2); a.W = W; a.HW = HW; a.dbg = g_dbg;
     { const char* e = getenv("SQ_X3_TAIL_XCD_WALK"); a.xcd_walk = tail ? (e ? atoi(e) : 64) : 0; }      // (read per launch: the tests flip it inside one process)
     using I64 = std::integral_constant<int, 64>; using I128 = std::integral_constant<int, 128>;
@@ -590,16 +583,15 @@ int sq_launch_chain_x3_c64(int f16, const uint16_t* t2, long long plT2, const ui
     auto pick_f16 = [&](auto n2c) { return f16 ? pick_ds(n2c, T{}) : pick_ds(n2c, F{}); };
     const void* fn = n2 == 64 ? pick_f16(I64{}) : pick_f16(I128{});
     SQ_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "%s_%s_c64_cn%d%s_P%lld", tail ? "tail" : "chain", f16 ? "f16x3" : "bf16x3", n2, ds ? "_ds" : "", P);
-        prof = sq_prof_begin(name, 2.0 * P * ((tail ? 576.0 * 64 : 0.0) + 64.0 * 256 * (ds ? 2 : 1) + 256.0 * n2), (double)P * 4.0 * (64 + (ds ? 64 : 256) + 256 + n2), stream);
+        prof.begin(name, 2.0 * P * ((tail ? 576.0 * 64 : 0.0) + 64.0 * 256 * (ds ? 2 : 1) + 256.0 * n2), (double)P * 4.0 * (64 + (ds ? 64 : 256) + 256 + n2));
     }
     const dim3 grid((unsigned)((P + PX - 1) / PX)), block(256);
     void* kargs[] = {(void*)&a};
     SQ_HIP_CHECK(hipLaunchKernel(fn, grid, block, kargs, LDS_BYTES, stream));
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }
 

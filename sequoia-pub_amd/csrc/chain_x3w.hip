@@ -29,6 +29,7 @@
 // same epilogue arithmetic as the two gemm_x3.hip launches it replaces: bit-identical results (tests/test_gpu_x3.py).
 #include "gemm.h"
 #include "x3_fmt.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -38,19 +39,6 @@ extern int g_dbg;                // sq_dbg_set key 1 (gemm.hip)
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ void glds16_nt(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {      // streaming (read-once) data
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 2);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-__device__ __forceinline__ u32x2 lds64(const char* p) { return *reinterpret_cast<const u32x2*>(p); }
-__device__ __forceinline__ void st_lds64(char* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // n (wave-uniform, even, <= 16): waits until at most n vector-memory operations are outstanding
 __device__ __forceinline__ void wait_vm_n(int n) {
     switch (n >> 1) {
@@ -119,11 +107,7 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
     const int pg = wave & 3;                      // pixel group; waves 0-3: role A, waves 4-7: role B
     const int l31 = lane & 31, lh = lane >> 5;
     const int swz = (l31 >> 2) & 3;
-    int t;
-    {   // each XCD (block id % 8) walks a contiguous run of tiles
-        const int b = blockIdx.x, q = p.tiles >> 3, r = p.tiles & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, p.tiles);
     const int p0 = t * Cfg::PX + pg * 32;         // this pixel group's first pixel
     char* const myXY = XYB + pg * 3 * XYW;
 
@@ -146,12 +130,12 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
         // =========================================== role A ===========================================
         const int ta = tid;                       // 0 .. 255
         const uint32_t act_bytes = (uint32_t)p.P * N1 * 2u;
-        const auto rsRh = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, (int)act_bytes, 0x00020000);
-        const auto rsRl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res + p.plRes), 0, (int)act_bytes, 0x00020000);
-        const auto rsW3h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3, 0, (int)p.w3_bytes, 0x00020000);
-        const auto rsW3l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w3 + p.plW), 0, (int)p.w3_bytes, 0x00020000);
-        const auto rsW1h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1n, 0, (int)p.w1n_bytes, 0x00020000);
-        const auto rsW1l = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w1n + p.plW), 0, (int)p.w1n_bytes, 0x00020000);
+        const auto rsRh = sq_rsrc(p.res, (int)act_bytes);
+        const auto rsRl = sq_rsrc(p.res + p.plRes, (int)act_bytes);
+        const auto rsW3h = sq_rsrc(p.w3, (int)p.w3_bytes);
+        const auto rsW3l = sq_rsrc(p.w3 + p.plW, (int)p.w3_bytes);
+        const auto rsW1h = sq_rsrc(p.w1n, (int)p.w1n_bytes);
+        const auto rsW1l = sq_rsrc(p.w1n + p.plW, (int)p.w1n_bytes);
 
         // ---- the two units of step i -> ring slots 2 (i % 3) and 2 (i % 3) + 1, one LDS-DMA request (piece) at a time so that the
         // requests can be dealt between the MFMAs of a step (an LDS-DMA request costs the issuing wave ~100 cycles of issue time).
@@ -196,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
             const int u = r >> 1;
             const int e = u * 64 + lane, row = e >> 2, cl = (e & 3) ^ ((row >> 2) & 3);
             const int pr = p0 + row;
-            const uint32_t off = (pr < p.P && !(dbg & 2)) ? ((uint32_t)pr * N1 + (uint32_t)(s * 32 + cl * 8)) * 2u : OOB;
+            const uint32_t off = (pr < p.P && !(dbg & 2)) ? ((uint32_t)pr * N1 + (uint32_t)(s * 32 + cl * 8)) * 2u : SQ_OOB;
             if (nt) { if (r & 1) glds16_nt(rsRl, dst + 2048 + u * 1024, off); else glds16_nt(rsRh, dst + u * 1024, off); }
             else { if (r & 1) glds16(rsRl, dst + 2048 + u * 1024, off); else glds16(rsRh, dst + u * 1024, off); }
         };
@@ -312,10 +296,10 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
     } else {
         // =========================================== role B ===========================================
         const uint32_t act_bytes = (uint32_t)p.P * N1 * 2u;
-        const auto rsYh = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)act_bytes, 0x00020000);
-        const auto rsYl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + p.plY), 0, (int)act_bytes, 0x00020000);
-        const auto rsTh = __builtin_amdgcn_make_buffer_rsrc((void*)p.t1n, 0, (int)((uint32_t)p.P * N2 * 2u), 0x00020000);
-        const auto rsTl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.t1n + p.plT1n), 0, (int)((uint32_t)p.P * N2 * 2u), 0x00020000);
+        const auto rsYh = sq_rsrc(p.y, (int)act_bytes);
+        const auto rsYl = sq_rsrc(p.y + p.plY, (int)act_bytes);
+        const auto rsTh = sq_rsrc(p.t1n, (int)((uint32_t)p.P * N2 * 2u));
+        const auto rsTl = sq_rsrc(p.t1n + p.plT1n, (int)((uint32_t)p.P * N2 * 2u));
         f32x16 acc2[NT2];
 #pragma unroll
         for (int i = 0; i < NT2; ++i)
@@ -340,11 +324,11 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
                     if constexpr (H == 1) {
                         const int e = (r >> 1) * 64 + lane, row = e >> 2, cl = (e & 3) ^ ((row >> 2) & 3);
                         const int pr = p0 + row;
-                        return pr < p.P ? ((uint32_t)pr * N1 + (uint32_t)(s * 32 + cl * 8)) * 2u : OOB;
+                        return pr < p.P ? ((uint32_t)pr * N1 + (uint32_t)(s * 32 + cl * 8)) * 2u : SQ_OOB;
                     } else {
                         const int row = (r & 3) * 8 + (lane >> 3), c8 = lane & 7;
                         const int pr = p0 + row;
-                        return pr < p.P ? ((uint32_t)pr * N1 + (uint32_t)((s - 1) * 32 + c8 * 8)) * 2u : OOB;
+                        return pr < p.P ? ((uint32_t)pr * N1 + (uint32_t)((s - 1) * 32 + c8 * 8)) * 2u : SQ_OOB;
                     }
                 };
                 auto store_read = [&](int r) {            // piece r -> sv[r & 3]
@@ -456,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void chain_x3w_kernel(const ChainWArgs p) {
                 for (int u = 0; u < (32 * ROWB) / 1024; ++u) {
                     const int e = u * 64 + lane, row = e / NCH, cl = (e % NCH) ^ (row & (NCH - 1));
                     const int pr = p0 + row;
-                    const uint32_t off = pr < p.P ? ((uint32_t)pr * N2 + (uint32_t)(cl * 8)) * 2u : OOB;
+                    const uint32_t off = pr < p.P ? ((uint32_t)pr * N2 + (uint32_t)(cl * 8)) * 2u : SQ_OOB;
                     const u32x4 v = lds128(mine + e * 16);
                     if (nt && (dbg & 256)) {      // (experiment: t1' with the streaming policy too)
                         if (pl == 0) __builtin_amdgcn_raw_buffer_store_b128(v, rsTh, off, 0, 2);
@@ -510,21 +494,17 @@ int sq_launch_chain_x3w(int f16, int c, const uint16_t* t2, long long plT2, cons
     a.t2 = t2; a.plT2 = plT2; a.res = res; a.plRes = plRes; a.y = y; a.plY = plY; a.t1n = t1n; a.plT1n = plT1n;
     a.w3 = w3; a.w1n = w1n; a.plW = plW; a.b3 = b3; a.cs3 = cs3; a.b1n = b1n; a.cs1n = cs1n;
     a.P = (int)P; a.tiled = w_tiled; a.dbg = g_dbg;
-    auto clamp = [](size_t b) { return (uint32_t)(b < 0x7fffffffu ? b : 0x7fffffffu); };
-    a.w3_bytes = clamp(w3_bytes); a.w1n_bytes = clamp(w1n_bytes);
+    a.w3_bytes = sq_desc_extent(w3_bytes); a.w1n_bytes = sq_desc_extent(w1n_bytes);
     a.tiles = (int)((P + 127) / 128);
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "chainw_%s_c%d_cn%d_P%lld", f16 ? "f16x3" : "bf16x3", c, n2, P);
-        prof = sq_prof_begin(name, 2.0 * P * (4.0 * c * c + 4.0 * c * n2), (double)P * 4.0 * (c + 4 * c + 4 * c + n2), stream);
+        prof.begin(name, 2.0 * P * (4.0 * c * c + 4.0 * c * n2), (double)P * 4.0 * (c + 4 * c + 4 * c + n2));
     }
-    int rc;
-    if (c == 256) rc = f16 ? launch_chainw<256, 256, true>(a, stream) : launch_chainw<256, 256, false>(a, stream);
-    else if (n2 == 256) rc = f16 ? launch_chainw<128, 256, true>(a, stream) : launch_chainw<128, 256, false>(a, stream);
-    else rc = f16 ? launch_chainw<128, 128, true>(a, stream) : launch_chainw<128, 128, false>(a, stream);
-    if (prof >= 0) sq_prof_end(prof, stream);
-    return rc;
+    if (c == 256) return f16 ? launch_chainw<256, 256, true>(a, stream) : launch_chainw<256, 256, false>(a, stream);
+    if (n2 == 256) return f16 ? launch_chainw<128, 256, true>(a, stream) : launch_chainw<128, 256, false>(a, stream);
+    return f16 ? launch_chainw<128, 128, true>(a, stream) : launch_chainw<128, 128, false>(a, stream);
 }
 
 // Probe / test entry (tests/test_gpu_x3.py, tools/chainw_probe.py): one launch on caller-provided planes (row-major or K-tile-major weights)

@@ -246,13 +246,12 @@ int sq_launch_conv1_pool_bf16(const uint8_t* u8, const float* f32_nchw, const bf
         attr.done();
     }
     const int grid = (int)(tiles < 512 ? tiles : 512);      // persistent: 2 blocks per CU keep their weights in registers
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         const double px_out = (double)n * ((H + 1) / 2) * ((W + 1) / 2);
-        prof = sq_prof_begin("conv1_pool_bf16", 2.0 * px_out * 64 * 147, (double)n * H * W * 3 + (double)n * PH * PW * 64 * 2, stream);
+        prof.begin("conv1_pool_bf16", 2.0 * px_out * 64 * 147, (double)n * H * W * 3 + (double)n * PH * PW * 64 * 2);
     }
     hipLaunchKernelGGL(conv1_pool_kernel, dim3(grid), dim3(256), lds, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

@@ -357,16 +357,15 @@ int sq_launch_conv1_pool_x3(int f16, const uint8_t* u8, const float* f32_nchw, c
         attr.done();
     }
     const int grid = (int)(tiles < 256 ? tiles : 256);      // persistent: one block per CU keeps its weight planes in registers
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         const double px_out = (double)n * ((H + 1) / 2) * ((W + 1) / 2);
-        prof = sq_prof_begin(f16 ? (t1_hi ? "conv1_pool_reduce_f16x3" : "conv1_pool_f16x3") : (t1_hi ? "conv1_pool_reduce_bf16x3" : "conv1_pool_bf16x3"),
-                             2.0 * px_out * 64 * 147 + (t1_hi ? 2.0 * n * PH * PW * 64.0 * 64.0 : 0.0),
-                             (double)n * H * W * 3 + (double)n * PH * PW * 64 * 4 * (t1_hi ? 2 : 1), stream);
+        prof.begin(f16 ? (t1_hi ? "conv1_pool_reduce_f16x3" : "conv1_pool_f16x3") : (t1_hi ? "conv1_pool_reduce_bf16x3" : "conv1_pool_bf16x3"),
+                   2.0 * px_out * 64 * 147 + (t1_hi ? 2.0 * n * PH * PW * 64.0 * 64.0 : 0.0),
+                   (double)n * H * W * 3 + (double)n * PH * PW * 64 * 4 * (t1_hi ? 2 : 1));
     }
     if (f16) hipLaunchKernelGGL(conv1_pool_x3_kernel<true>, dim3(grid), dim3(NT), LDS_BYTES, stream, a);
     else hipLaunchKernelGGL(conv1_pool_x3_kernel<false>, dim3(grid), dim3(NT), LDS_BYTES, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

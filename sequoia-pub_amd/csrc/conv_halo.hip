@@ -11,19 +11,12 @@
 // gemm_ring.hip) = 144 KiB, one block per CU.  K is walked channel-block-major (all nine taps of a block, then the next
 // block): the fp32 accumulation order differs from the tap-major implicit GEMM, results agree to fp32 rounding.
 #include "gemm.h"
+#include "cdna_prims.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 constexpr int BM = 256, BN = 128;
 constexpr int HALO_BYTES = 40960;                 // <= 320 rows of 128 B: 256 + 2 W + 2 rows, W <= 31
@@ -49,19 +42,15 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmArgs p) {
 
     const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int t;
-    {
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, nwg);
     const int p0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
     const int W = p.W, HWp = p.H * p.W, C = p.Cin;
     const int ncb = C / 64;
     const int halo0 = p0 - W - 1;
     const int halo_slots = (BM + 2 * W + 2) * 8;
 
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
+    const auto rsA = sq_rsrc(p.A, (int)p.a_bytes);
+    const auto rsB = sq_rsrc(p.B, (int)p.b_bytes);
 
     auto issue_halo = [&](int cb, int buf) {      // rows [halo0, halo0 + HR) x channels [64 cb, 64 cb + 64)
 #pragma unroll
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmArgs p) {
             const int row = q >> 3, c = (q & 7) ^ ((row >> 1) & 7);
             const int px = halo0 + row;
             const bool ok = q < halo_slots && px >= 0 && px < p.M;
-            glds16(rsA, HB + buf * HALO_BYTES + u * 8192 + wave * 1024, ok ? ((uint32_t)px * (uint32_t)C + (uint32_t)(cb * 64 + c * 8)) * 2u : OOB);
+            glds16(rsA, HB + buf * HALO_BYTES + u * 8192 + wave * 1024, ok ? ((uint32_t)px * (uint32_t)C + (uint32_t)(cb * 64 + c * 8)) * 2u : SQ_OOB);
         }
     };
     const int br0 = tid >> 3, bc = (tid & 7) ^ ((br0 >> 1) & 7);
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(const GemmArgs p) {
             if (cb + 1 < ncb) issue_halo(cb + 1, (cb + 1) & 1);       // in FRONT of this iteration's weight tile
             else {                                                     // keep the per-iteration load count uniform
 #pragma unroll
-                for (int u = 0; u < HL; ++u) glds16(rsA, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, OOB);
+                for (int u = 0; u < HL; ++u) glds16(rsA, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, SQ_OOB);
             }
         }
         {

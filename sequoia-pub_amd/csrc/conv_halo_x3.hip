@@ -17,19 +17,12 @@
 // K is walked channel-block-major: the fp32 accumulation order differs from the tap-major implicit GEMM (fp32 rounding).
 #include "gemm.h"
 #include "x3_fmt.h"
+#include "cdna_prims.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 constexpr int BM = 256, ROWB = 64, CB = 32;
 constexpr int NB = 4;                             // weight ring stages
@@ -50,8 +43,6 @@ template <int WTN, int HROWS> struct HxCfg {
     static constexpr int WL = WTN;                         // LDS-DMA instructions per thread and weight tile (BN = 64: both planes in one)
 };
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <int WTN, int HROWS, bool F16, bool PP>
 __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
     using Fmt = X3Fmt<F16>;
@@ -68,11 +59,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
 
     const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int t;
-    {
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, nwg);
     const int p0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
     const int W = p.W, HWp = p.H * p.W, C = p.Cin;
     const int ncb = (p.dbg & 4) ? 0 : (C / CB);        // dbg 4 (x3_probe.py halo): no K loop -- what a tile costs around it
@@ -81,10 +68,10 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
 
     const uint16_t* Ah = reinterpret_cast<const uint16_t*>(p.A);
     const uint16_t* Bh = reinterpret_cast<const uint16_t*>(p.B);
-    const auto rsAh = __builtin_amdgcn_make_buffer_rsrc((void*)Ah, 0, (int)p.a_bytes, 0x00020000);
-    const auto rsAl = __builtin_amdgcn_make_buffer_rsrc((void*)(Ah + p.plA), 0, (int)p.a_bytes, 0x00020000);
-    const auto rsBh = __builtin_amdgcn_make_buffer_rsrc((void*)Bh, 0, (int)p.b_bytes, 0x00020000);
-    const auto rsBl = __builtin_amdgcn_make_buffer_rsrc((void*)(Bh + p.plB), 0, (int)p.b_bytes, 0x00020000);
+    const auto rsAh = sq_rsrc(Ah, (int)p.a_bytes);
+    const auto rsAl = sq_rsrc(Ah + p.plA, (int)p.a_bytes);
+    const auto rsBh = sq_rsrc(Bh, (int)p.b_bytes);
+    const auto rsBl = sq_rsrc(Bh + p.plB, (int)p.b_bytes);
 
     // input block: rows [halo0, halo0 + HROWS) x channels [32 cb, 32 cb + 32), hi plane then lo plane.  Instruction u of a wave
     // covers slots [u*512 + wave*64, +64); a plane is a whole number of wave instructions, so the plane is wave-uniform
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
             const int row = s >> 2, c = (s & 3) ^ ((row >> 2) & 3);
             const int px = halo0 + row;
             const bool ok = s < halo_slots && px >= 0 && px < p.M;
-            const uint32_t off = ok ? ((uint32_t)px * (uint32_t)C + (uint32_t)(cb * CB + c * 8)) * 2u : OOB;
+            const uint32_t off = ok ? ((uint32_t)px * (uint32_t)C + (uint32_t)(cb * CB + c * 8)) * 2u : SQ_OOB;
             char* dst = HB + buf * HALO_BYTES + u * 8192 + wave * 1024;
             if (lo) glds16(rsAl, dst, off); else glds16(rsAh, dst, off);
         }
@@ -215,7 +202,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
             if (cb + 1 < ncb) issue_halo(cb + 1, (cb + 1) & 1);       // in FRONT of this step's weight tile
             else {                                                     // keep the per-step load count uniform
 #pragma unroll
-                for (int u = 0; u < HL; ++u) glds16(rsAh, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, OOB);
+                for (int u = 0; u < HL; ++u) glds16(rsAh, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, SQ_OOB);
             }
         }
         {
@@ -272,7 +259,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(const GemmArgs p) {
                 if (cb + 1 < ncb) issue_halo(cb + 1, (cb + 1) & 1);
                 else {
 #pragma unroll
-                    for (int u = 0; u < HL; ++u) glds16(rsAh, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, OOB);
+                    for (int u = 0; u < HL; ++u) glds16(rsAh, HB + ((cb + 1) & 1) * HALO_BYTES + u * 8192 + wave * 1024, SQ_OOB);
                 }
             }
             {

@@ -18,6 +18,7 @@
 // bf16 path: v_mfma_f32_32x32x16_bf16, fp32 accumulate -- the perf mode.
 #include "gemm.h"
 #include "gemm_epi.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -31,18 +32,6 @@ bool sq_gemm_ring_eligible(const GemmArgs& a, int dtype);
 int sq_launch_gemm_ring(const GemmArgs& a, hipStream_t stream);
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ u32x4 lds_read128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
-
-// 16 B per lane, HBM/L2 -> LDS without a VGPR round trip.  LDS destination = lds_base + lane*16
-// (lane-linear); the source offset is per lane.  Kept in a non-template helper: the host pass of a
-// kernel TEMPLATE that names this builtin directly silently drops the kernel's launch stub.
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, soffset, 0, 0);
-}
 
 template <typename T> struct Mma;
 
@@ -83,11 +72,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
     const int tiles_n = (p.N + BN - 1) / BN;
     const int tiles_m = (p.M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int t;
-    {
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, nwg);
     const int m0 = (t / tiles_n) * BM;
     const int n0 = (t % tiles_n) * BN;
     const int z = blockIdx.z;
@@ -96,8 +81,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
     const T* Bb = reinterpret_cast<const T*>(p.B) + (long long)z * p.sB;
     const size_t a_rem = p.a_bytes - (size_t)z * p.sA * sizeof(T);
     const size_t b_rem = p.b_bytes - (size_t)z * p.sB * sizeof(T);
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)a_rem, 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)b_rem, 0x00020000);
+    const auto rsA = sq_rsrc(Ab, (int)a_rem);
+    const auto rsB = sq_rsrc(Bb, (int)b_rem);
 
     const int r0 = tid >> 3;                       // row inside a 32-row group (LDS image: lane-linear)
     const int gc = (tid & 7) ^ ((r0 >> 1) & 7);    // 16-B chunk of the SOURCE row this lane fetches
@@ -123,13 +108,13 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
         } else {
             a_ih0[j] = a_iw0[j] = 0;
             a_pix[j] = 0;
-            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * EPC)) * (uint32_t)sizeof(T) : OOB;
+            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * EPC)) * (uint32_t)sizeof(T) : SQ_OOB;
         }
     }
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
         const int n = n0 + r0 + 32 * j;
-        b_off[j] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * EPC)) * (uint32_t)sizeof(T) : OOB;
+        b_off[j] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * EPC)) * (uint32_t)sizeof(T) : SQ_OOB;
     }
 
     // Epilogue operands that do not depend on the accumulators are requested NOW, so their HBM latency
@@ -185,17 +170,17 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
                 const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
                 const bool ok = a_ok[j] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
                 const uint32_t off = ((a_pix[j] + (uint32_t)(ih * p.W + iw)) * (uint32_t)p.Cin + (uint32_t)cin0) * (uint32_t)sizeof(T);
-                oa[j] = ok ? off : OOB;
+                oa[j] = ok ? off : SQ_OOB;
             }
             soff = 0;
 #pragma unroll
-            for (int j = 0; j < RB; ++j) ob[j] = k_ok ? b_off[j] + (uint32_t)(k0 * (int)sizeof(T)) : OOB;
+            for (int j = 0; j < RB; ++j) ob[j] = k_ok ? b_off[j] + (uint32_t)(k0 * (int)sizeof(T)) : SQ_OOB;
         } else {
             soff = k0 * (int)sizeof(T);
 #pragma unroll
-            for (int j = 0; j < RA; ++j) oa[j] = k_ok ? a_off[j] : OOB;
+            for (int j = 0; j < RA; ++j) oa[j] = k_ok ? a_off[j] : SQ_OOB;
 #pragma unroll
-            for (int j = 0; j < RB; ++j) ob[j] = k_ok ? b_off[j] : OOB;
+            for (int j = 0; j < RB; ++j) ob[j] = k_ok ? b_off[j] : SQ_OOB;
         }
 #pragma unroll
         for (int j = 0; j < RA; ++j)
@@ -237,16 +222,16 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
         const char* st = smem + buf * TILE_BYTES;
         u32x4 fa[2][WTM], fb[2][WTN];
 #pragma unroll
-        for (int i = 0; i < WTM; ++i) fa[0][i] = lds_read128(st + fa_off[i][0]);
+        for (int i = 0; i < WTM; ++i) fa[0][i] = lds128(st + fa_off[i][0]);
 #pragma unroll
-        for (int j = 0; j < WTN; ++j) fb[0][j] = lds_read128(st + fb_off[j][0]);
+        for (int j = 0; j < WTN; ++j) fb[0][j] = lds128(st + fb_off[j][0]);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if (s < 3) {
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) fa[(s + 1) & 1][i] = lds_read128(st + fa_off[i][s + 1]);
+                for (int i = 0; i < WTM; ++i) fa[(s + 1) & 1][i] = lds128(st + fa_off[i][s + 1]);
 #pragma unroll
-                for (int j = 0; j < WTN; ++j) fb[(s + 1) & 1][j] = lds_read128(st + fb_off[j][s + 1]);
+                for (int j = 0; j < WTN; ++j) fb[(s + 1) & 1][j] = lds128(st + fb_off[j][s + 1]);
             }
             __builtin_amdgcn_sched_barrier(0);      // keep the prefetch ahead of this k-step's MFMAs
 #pragma unroll
@@ -636,8 +621,8 @@ int sq_launch_gemm(const GemmArgs& a, int dtype, hipStream_t stream) {
     }
     GemmArgs av = a;
     av.vec_epi = sq_gemm_vec_epi(a);
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         // algorithmic work of this launch: 2*M*N*K flops; operands read once + output written once
         const double es = dtype == SQ_BF16 ? 2.0 : 4.0;
         const double flops = 2.0 * a.M * (double)a.N * a.K * a.batch;
@@ -652,7 +637,7 @@ int sq_launch_gemm(const GemmArgs& a, int dtype, hipStream_t stream) {
         char name[96];
         snprintf(name, sizeof(name), "%s_%s_M%d_N%d_K%d_b%d", a.conv ? "conv" : "gemm", dtype == SQ_BF16 ? "bf16" : "f32",
                  a.M, a.N, a.K, a.batch);
-        prof = sq_prof_begin(name, flops, bytes, stream);
+        prof.begin(name, flops, bytes);
     }
     if (av.ln64_g) {
         SQ_REQUIRE(av.ln64_b && !av.conv && av.N % 64 == 0 && av.vec_epi && !av.gelu_grad_of && ((uintptr_t)av.ln64_g & 15) == 0 &&
@@ -668,6 +653,5 @@ int sq_launch_gemm(const GemmArgs& a, int dtype, hipStream_t stream) {
     } else {
         rc = dtype == SQ_BF16 ? launch_t<bf16_t>(av, stream) : launch_t<float>(av, stream);
     }
-    if (prof >= 0) sq_prof_end(prof, stream);
     return rc;
 }

@@ -47,20 +47,14 @@
 // 1024: 418 -> 417; K = 4096: 396 -> 401): the counted wait of every K-tile then has stores in front of it.  Removed.
 #include "gemm.h"
 #include "gemm_epi.h"
+#include "cdna_prims.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds_read128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 constexpr int BM = 256, BK = 64, NT = 512;
 constexpr int HALF_A = 128 * BK * 2;             // 16 KiB: 128 rows x 64 k
@@ -123,8 +117,8 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
 
     const bf16_t* Ab = reinterpret_cast<const bf16_t*>(p.A) + (long long)z * p.sA;
     const bf16_t* Bb = reinterpret_cast<const bf16_t*>(p.B) + (long long)z * p.sB;
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)(p.a_bytes - (size_t)z * p.sA * 2), 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)(p.b_bytes - (size_t)z * p.sB * 2), 0x00020000);
+    const auto rsA = sq_rsrc(Ab, (int)(p.a_bytes - (size_t)z * p.sA * 2));
+    const auto rsB = sq_rsrc(Bb, (int)(p.b_bytes - (size_t)z * p.sB * 2));
 
     // ---- staging geometry.  A half-tile (128 LDS rows): wave w stages row group w (16 rows), both 32-deep halves -- two
     // instructions that together request the whole 128-byte line of each row.  B half-tile: the same for 128 rows (BNT = 256);
@@ -143,8 +137,8 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
         for (int h = 0; h < 2; ++h) {
             const int m = m0_ + (s_RA / SA) * (2 * SA) + h * SA + (s_RA % SA);
             const int n = n0_ + (s_RB >> 5) * 64 + h * 32 + (s_RB & 31);
-            a_src[h] = m < p.M ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(s_ck * 8)) * 2u : OOB;
-            b_src[h] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(s_ck * 8)) * 2u : OOB;
+            a_src[h] = m < p.M ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(s_ck * 8)) * 2u : SQ_OOB;
+            b_src[h] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(s_ck * 8)) * 2u : SQ_OOB;
         }
     };
     set_src(m0, n0);
@@ -160,19 +154,19 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
                 const bool ok = kt < nk && k0 + kh * 32 + s_ck * 8 < p.K;
-                glds16(rsA, dst + kh * 1024, ok ? a_src[slot] : OOB, (k0 + kh * 32) * 2);
+                glds16(rsA, dst + kh * 1024, ok ? a_src[slot] : SQ_OOB, (k0 + kh * 32) * 2);
             }
         } else if constexpr (LB == 2) {
             char* dst = smem + buf * BUF_BYTES + 2 * HALF_A + (slot - 2) * HALF_B + wave * 2048;
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
                 const bool ok = kt < nk && k0 + kh * 32 + s_ck * 8 < p.K;
-                glds16(rsB, dst + kh * 1024, ok ? b_src[slot - 2] : OOB, (k0 + kh * 32) * 2);
+                glds16(rsB, dst + kh * 1024, ok ? b_src[slot - 2] : SQ_OOB, (k0 + kh * 32) * 2);
             }
         } else {
             char* dst = smem + buf * BUF_BYTES + 2 * HALF_A + (slot - 2) * HALF_B + wave * 1024;
             const bool ok = kt < nk && k0 + s_khB * 32 + s_ck * 8 < p.K;
-            glds16(rsB, dst, ok ? b_src[slot - 2] : OOB, (k0 + s_khB * 32) * 2);
+            glds16(rsB, dst, ok ? b_src[slot - 2] : SQ_OOB, (k0 + s_khB * 32) * 2);
         }
     };
     // first operands of a tile: K-tile 0 complete, then what the steady state would have issued during "K-tile -1"
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
 #pragma unroll
         for (int ii = 0; ii < MA; ++ii)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fa[ii][ks] = lds_read128(s + ii * 2048 + ks * 1024);
+            for (int ks = 0; ks < 2; ++ks) fa[ii][ks] = lds128(s + ii * 2048 + ks * 1024);
     };
     auto read_b = [&](int buf, int b) {
         if (dbg & 8) return;
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fb[jj][ks] = lds_read128(s + jj * 2048 + ks * 1024);
+            for (int ks = 0; ks < 2; ++ks) fb[jj][ks] = lds128(s + jj * 2048 + ks * 1024);
     };
     auto mma = [&](auto ac, auto bc) {
         constexpr int a = decltype(ac)::value, b = decltype(bc)::value;
@@ -453,7 +447,7 @@ __global__ __launch_bounds__(NT) void gemm_p8_kernel(const GemmArgs p) {
                 const u32x4 packed = {pack_bf16x2(v[u][0], v[u][1]), pack_bf16x2(v[u][2], v[u][3]), pack_bf16x2(v[u][4], v[u][5]), pack_bf16x2(v[u][6], v[u][7])};
                 *reinterpret_cast<u32x4*>(sb + (e_c8 >> 2) * 1024 + ((row * 64 + (e_c8 & 3) * 16) ^ ((row >> 3) << 5))) = packed;
             }
-            const u32x4 af0 = lds_read128(sb + f_byte), af1 = lds_read128(sb + 1024 + f_byte);
+            const u32x4 af0 = lds128(sb + f_byte), af1 = lds128(sb + 1024 + f_byte);
             f32x4v o[4];
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {

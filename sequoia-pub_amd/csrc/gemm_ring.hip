@@ -20,18 +20,11 @@
 // bias / residual / ReLU / bf16-or-fp32 output take a prefetching fast path, everything else goes through epi_apply.
 #include "gemm.h"
 #include "gemm_epi.h"
+#include "cdna_prims.h"
 
 #include <cstdlib>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds_read128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 constexpr int BM = 256, BN = 128, BK = 64;
 constexpr int WTM = 2, WTN = 2;                 // 32 x 32 MFMA tiles per wave
@@ -50,18 +43,14 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(const GemmArgs p) {
 
     const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int t;
-    {   // each XCD (block id % 8) walks a contiguous run of tiles
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, nwg);
     const int m0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
     const int z = blockIdx.z;
 
     const bf16_t* Ab = reinterpret_cast<const bf16_t*>(p.A) + (long long)z * p.sA;
     const bf16_t* Bb = reinterpret_cast<const bf16_t*>(p.B) + (long long)z * p.sB;
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)(p.a_bytes - (size_t)z * p.sA * 2), 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)(p.b_bytes - (size_t)z * p.sB * 2), 0x00020000);
+    const auto rsA = sq_rsrc(Ab, (int)(p.a_bytes - (size_t)z * p.sA * 2));
+    const auto rsB = sq_rsrc(Bb, (int)(p.b_bytes - (size_t)z * p.sB * 2));
 
     const int r0 = tid >> 3;                        // row inside a 64-row round
     const int gc = (tid & 7) ^ ((r0 >> 1) & 7);     // 16-byte chunk of the SOURCE row this lane fetches
@@ -85,13 +74,13 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(const GemmArgs p) {
         } else {
             a_ih0[j] = a_iw0[j] = 0;
             a_pix[j] = 0;
-            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * 8)) * 2u : OOB;
+            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * 8)) * 2u : SQ_OOB;
         }
     }
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
         const int n = n0 + r0 + 64 * j;
-        b_off[j] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * 8)) * 2u : OOB;
+        b_off[j] = n < p.N ? ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * 8)) * 2u : SQ_OOB;
     }
     auto issue_loads = [&](int kt, int buf) {
         const int k0 = kt * BK;
@@ -107,16 +96,16 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(const GemmArgs p) {
                 const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
                 const bool ok = a_ok[j] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
                 const uint32_t off = ((a_pix[j] + (uint32_t)(ih * p.W + iw)) * (uint32_t)p.Cin + (uint32_t)cin0) * 2u;
-                glds16(rsA, sa + j * (64 * 128), ok ? off : OOB, 0);
+                glds16(rsA, sa + j * (64 * 128), ok ? off : SQ_OOB, 0);
             }
 #pragma unroll
-            for (int j = 0; j < RB; ++j) glds16(rsB, sb + j * (64 * 128), k_ok ? b_off[j] + (uint32_t)(k0 * 2) : OOB, 0);
+            for (int j = 0; j < RB; ++j) glds16(rsB, sb + j * (64 * 128), k_ok ? b_off[j] + (uint32_t)(k0 * 2) : SQ_OOB, 0);
         } else {
             const int soff = k0 * 2;
 #pragma unroll
-            for (int j = 0; j < RA; ++j) glds16(rsA, sa + j * (64 * 128), k_ok ? a_off[j] : OOB, soff);
+            for (int j = 0; j < RA; ++j) glds16(rsA, sa + j * (64 * 128), k_ok ? a_off[j] : SQ_OOB, soff);
 #pragma unroll
-            for (int j = 0; j < RB; ++j) glds16(rsB, sb + j * (64 * 128), k_ok ? b_off[j] : OOB, soff);
+            for (int j = 0; j < RB; ++j) glds16(rsB, sb + j * (64 * 128), k_ok ? b_off[j] : SQ_OOB, soff);
         }
     };
 
@@ -167,16 +156,16 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(const GemmArgs p) {
         const char* st = smem + buf * STAGE_BYTES;
         u32x4 fa[2][WTM], fb[2][WTN];
 #pragma unroll
-        for (int i = 0; i < WTM; ++i) fa[0][i] = lds_read128(st + fa_off[i][0]);
+        for (int i = 0; i < WTM; ++i) fa[0][i] = lds128(st + fa_off[i][0]);
 #pragma unroll
-        for (int j = 0; j < WTN; ++j) fb[0][j] = lds_read128(st + fb_off[j][0]);
+        for (int j = 0; j < WTN; ++j) fb[0][j] = lds128(st + fb_off[j][0]);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if (s < 3) {
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) fa[(s + 1) & 1][i] = lds_read128(st + fa_off[i][s + 1]);
+                for (int i = 0; i < WTM; ++i) fa[(s + 1) & 1][i] = lds128(st + fa_off[i][s + 1]);
 #pragma unroll
-                for (int j = 0; j < WTN; ++j) fb[(s + 1) & 1][j] = lds_read128(st + fb_off[j][s + 1]);
+                for (int j = 0; j < WTN; ++j) fb[(s + 1) & 1][j] = lds128(st + fb_off[j][s + 1]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

@@ -14,18 +14,12 @@
 // per step with two LDS buffers; grid.y slices the contraction (split-K, deterministic reduction).
 #include "gemm.h"
 #include "gemm_epi.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, soffset, 0, 0);
-}
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 lds_bf16x4;
@@ -91,8 +85,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmArgs p) {
     const T* Ab = reinterpret_cast<const T*>(grouped ? sq_group_pick(p.gA, z) : p.A) + (long long)zs * p.sA;
     const T* Bb = reinterpret_cast<const T*>(grouped ? sq_group_pick(p.gB, z) : p.B) + (long long)zs * p.sB;
     float* const colsum_dst = grouped ? sq_group_pick(p.gcs, z) : p.colsum_a;
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)(p.a_bytes - (size_t)zs * p.sA * sizeof(T)), 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)(p.b_bytes - (size_t)zs * p.sB * sizeof(T)), 0x00020000);
+    const auto rsA = sq_rsrc(Ab, (int)(p.a_bytes - (size_t)zs * p.sA * sizeof(T)));
+    const auto rsB = sq_rsrc(Bb, (int)(p.b_bytes - (size_t)zs * p.sB * sizeof(T)));
 
     // DMA lane mapping: instruction j of wave w fills rows (j*4 + w) * ROWS_PER_INSTR + lane / CHUNKS
     const int lrow = lane / CHUNKS, lchunk = lane % CHUNKS;
@@ -112,8 +106,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmArgs p) {
             const int k = kt * KR + row;                        // contraction index
             const int gchunk = lchunk ^ key(row);               // source chunk landing at LDS chunk lchunk
             const int ca = m0 + gchunk * (16 / (int)sizeof(T)), cb = n0 + gchunk * (16 / (int)sizeof(T));
-            const uint32_t oa = (k < p.K && ca < p.M) ? (uint32_t)(((long long)k * p.lda + ca) * (long long)sizeof(T)) : OOB;
-            const uint32_t ob = (k < p.K && cb < p.N) ? (uint32_t)(((long long)k * p.ldb + cb) * (long long)sizeof(T)) : OOB;
+            const uint32_t oa = (k < p.K && ca < p.M) ? (uint32_t)(((long long)k * p.lda + ca) * (long long)sizeof(T)) : SQ_OOB;
+            const uint32_t ob = (k < p.K && cb < p.N) ? (uint32_t)(((long long)k * p.ldb + cb) * (long long)sizeof(T)) : SQ_OOB;
             glds16(rsA, sa + rbase * ROWB, oa, 0);
             glds16(rsB, sb + rbase * ROWB, ob, 0);
         }
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmArgs p) {
                 const int rbase = (j * 4 + wave) * ROWS_PER_INSTR;
                 const int row = rbase + lrow, k = kt * KR + row;
                 const int ca = m0 + (lchunk ^ key(row)) * (16 / (int)sizeof(T));
-                const uint32_t oa = (k < p.K && ca < p.M) ? (uint32_t)(((long long)k * p.lda + ca) * (long long)sizeof(T)) : OOB;
+                const uint32_t oa = (k < p.K && ca < p.M) ? (uint32_t)(((long long)k * p.lda + ca) * (long long)sizeof(T)) : SQ_OOB;
                 glds16(rsA, sa + rbase * ROWB, oa, 0);
             }
         };
@@ -349,8 +343,8 @@ __global__ __launch_bounds__(512) void gemm_tn_ring_kernel(const GemmArgs p, con
     const bf16_t* Ab = reinterpret_cast<const bf16_t*>(grouped ? sq_group_pick(p.gA, z) : p.A);
     const bf16_t* Bb = reinterpret_cast<const bf16_t*>(grouped ? sq_group_pick(p.gB, z) : p.B);
     float* const colsum_dst = grouped ? sq_group_pick(p.gcs, z) : p.colsum_a;
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)p.a_bytes, 0x00020000);
-    const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)p.b_bytes, 0x00020000);
+    const auto rsA = sq_rsrc(Ab, (int)p.a_bytes);
+    const auto rsB = sq_rsrc(Bb, (int)p.b_bytes);
 
     const int nk_all = (p.K + RG_KR - 1) / RG_KR;
     const int per_k = (nk_all + p.splitk - 1) / p.splitk;
@@ -377,8 +371,8 @@ __global__ __launch_bounds__(512) void gemm_tn_ring_kernel(const GemmArgs p, con
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const bool ok = kt < kt_hi && kt * RG_KR + row_j[j] < p.K;
-            const uint32_t oa = ok ? src_a[j] + (uint32_t)kt * step_a : OOB;
-            const uint32_t ob = ok ? src_b[j] + (uint32_t)kt * step_b : OOB;
+            const uint32_t oa = ok ? src_a[j] + (uint32_t)kt * step_a : SQ_OOB;
+            const uint32_t ob = ok ? src_b[j] + (uint32_t)kt * step_b : SQ_OOB;
             glds16(rsA, sa + (j * 8 + wave) * 4 * RG_ROWB, oa, 0);
             glds16(rsB, sb + (j * 8 + wave) * 4 * RG_ROWB, ob, 0);
         }
@@ -623,21 +617,18 @@ int sq_launch_gemm_tn(const GemmArgs& a_in, int dtype, hipStream_t stream) {
             SQ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS));
             attr.done();
         }
-        int prof = -1;
-        if (sq_prof_on()) {
+        SqProf prof(stream);        // brackets the product and its split-K reduction
+        if (prof.on()) {
             char name[96];
             snprintf(name, sizeof(name), "gemmtn_bf16_M%d_N%d_K%d_b%d", a.M, a.N, a.K, a.batch);
-            prof = sq_prof_begin(name, 2.0 * a.M * (double)a.N * a.K * a.batch, ((double)a.K * (a.M + a.N) * 2.0 + (double)a.M * a.N * 4.0) * a.batch, stream);
+            prof.begin(name, 2.0 * a.M * (double)a.N * a.K * a.batch, ((double)a.K * (a.M + a.N) * 2.0 + (double)a.M * a.N * 4.0) * a.batch);
         }
         const int total = (int)(work * a.splitk);
         a.dbg |= g_dbg;
         const dim3 grid((unsigned)((total + 7) / 8 * 8)), block(512);
         hipLaunchKernelGGL(gemm_tn_ring_kernel, grid, block, RG_LDS, stream, a, a.M / 128, a.N / 128, total);
         SQ_LAUNCH_CHECK();
-        int rc = SQ_OK;
-        if (a.splitk > 1) rc = sq_launch_splitk_reduce(a, stream);
-        if (prof >= 0) sq_prof_end(prof, stream);
-        return rc;
+        return a.splitk > 1 ? sq_launch_splitk_reduce(a, stream) : SQ_OK;
     }
     const long long cs_blocks = a.colsum_a ? ((a.M + 127) / 128 + 7) / 8 * 8 : 0;
     if (a.splitk_ws && tiles * a.batch < 256 && nk >= 4) {
@@ -650,21 +641,17 @@ int sq_launch_gemm_tn(const GemmArgs& a_in, int dtype, hipStream_t stream) {
         if (s > 1) a.splitk = (int)s;
     }
     if (g_tn_force_split > 0 && a.splitk_ws && (size_t)g_tn_force_split * ((size_t)a.M * a.N * a.batch + (size_t)a.M * a.batch) * 4 <= a.splitk_ws_bytes) a.splitk = g_tn_force_split;
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         const double es = dtype == SQ_BF16 ? 2.0 : 4.0;
         char name[96];
         snprintf(name, sizeof(name), "gemmtn_%s_M%d_N%d_K%d_b%d", dtype == SQ_BF16 ? "bf16" : "f32", a.M, a.N, a.K, a.batch);
-        prof = sq_prof_begin(name, 2.0 * a.M * (double)a.N * a.K * a.batch,
-                             ((double)a.K * (a.M + a.N) * es + (double)a.M * a.N * 4.0) * a.batch, stream);
+        prof.begin(name, 2.0 * a.M * (double)a.N * a.K * a.batch, ((double)a.K * (a.M + a.N) * es + (double)a.M * a.N * 4.0) * a.batch);
     }
     const long long grid_x = tiles + cs_blocks;
     dim3 grid((unsigned)grid_x, a.splitk, a.batch), block(256);
     if (dtype == SQ_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, block, 65536, stream, a);
     else hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, block, 65536, stream, a);
     SQ_LAUNCH_CHECK();
-    int rc = SQ_OK;
-    if (a.splitk > 1) rc = sq_launch_splitk_reduce(a, stream);
-    if (prof >= 0) sq_prof_end(prof, stream);
-    return rc;
+    return a.splitk > 1 ? sq_launch_splitk_reduce(a, stream) : SQ_OK;
 }

@@ -20,6 +20,7 @@
 // (the transformer's residual stream never travels as planes) and the exact-erf GELU of the fp32 mode.
 #include "gemm.h"
 #include "x3_fmt.h"
+#include "cdna_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -32,13 +33,6 @@ extern int g_dbg;                // sq_dbg_set key 1: ablation switches (tools/x
 
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, char* lds_base, uint32_t voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_base, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds_read128(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 // 16-byte global accesses.  (A streaming (nt) policy on the residual reads and plane stores -- activations written once and read once
 // by the next launch -- was an experiment switch until round 5: pipeline 34.1 / 34.4 slides/s without, 34.1 / 34.1 with; only
 // chain_x3w.hip's 256-channel form gains from it and carries it unconditionally.)
@@ -85,21 +79,17 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
 
     const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int t;
-    {   // each XCD (block id % 8) walks a contiguous run of tiles
-        const int b = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = sq_xcd_tile(blockIdx.x, nwg);
     // (round 6: co-resident tiles of the dual form as 8 x 8 squares instead of 4 x 16 strips was measured -- 424 -> 418 us on the
     // N = 2048 launch, nothing on the others, profiles/r06_dual_walk_ab.txt -- and not kept)
     const int m0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
 
     const bf16_t* Ah = reinterpret_cast<const bf16_t*>(p.A);
     const bf16_t* Bh = reinterpret_cast<const bf16_t*>(p.B);
-    const auto rsAh = __builtin_amdgcn_make_buffer_rsrc((void*)Ah, 0, (int)p.a_bytes, 0x00020000);
-    const auto rsAl = __builtin_amdgcn_make_buffer_rsrc((void*)(Ah + p.plA), 0, (int)p.a_bytes, 0x00020000);
-    const auto rsBh = __builtin_amdgcn_make_buffer_rsrc((void*)Bh, 0, (int)p.b_bytes, 0x00020000);
-    const auto rsBl = __builtin_amdgcn_make_buffer_rsrc((void*)(Bh + p.plB), 0, (int)p.b_bytes, 0x00020000);
+    const auto rsAh = sq_rsrc(Ah, (int)p.a_bytes);
+    const auto rsAl = sq_rsrc(Ah + p.plA, (int)p.a_bytes);
+    const auto rsBh = sq_rsrc(Bh, (int)p.b_bytes);
+    const auto rsBl = sq_rsrc(Bh + p.plB, (int)p.b_bytes);
 
     // loader geometry: a wave instruction fills 16 consecutive 64-byte LDS rows; NT threads = one round of NT / 4 rows
     const int r0 = tid >> 2;                            // row inside a round
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
         } else {
             a_ih0[j] = a_iw0[j] = 0;
             a_pix[j] = 0;
-            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * 8)) * 2u : OOB;
+            a_off[j] = a_ok[j] ? ((uint32_t)m * (uint32_t)p.lda + (uint32_t)(gc * 8)) * 2u : SQ_OOB;
         }
     }
     // B rows: BN / ROUND rounds per plane; SPLIT_B (8 waves, BN = 64): rows 0-63 of the single round are the hi plane, 64-127 the lo plane
@@ -134,7 +124,7 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
 #pragma unroll
     for (int j = 0; j < RBP; ++j) {
         const int n = n0 + (Cfg::SPLIT_B ? (r0 & 63) : r0 + ROUND * j);
-        b_off[j] = n >= p.N ? OOB : p.b_tiled ? ((uint32_t)n * 32u + (uint32_t)(gc * 8)) * 2u : ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * 8)) * 2u;
+        b_off[j] = n >= p.N ? SQ_OOB : p.b_tiled ? ((uint32_t)n * 32u + (uint32_t)(gc * 8)) * 2u : ((uint32_t)n * (uint32_t)p.ldb + (uint32_t)(gc * 8)) * 2u;
     }
     auto issue_loads = [&](int kt, int buf) {
         const int k0 = kt * BK;
@@ -149,13 +139,13 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
             for (int j = 0; j < 2; ++j) {
                 const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
                 const bool ok = a_ok[j] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-                const uint32_t off = ok ? ((a_pix[j] + (uint32_t)(ih * p.W + iw)) * (uint32_t)p.Cin + (uint32_t)cin0) * 2u : OOB;
+                const uint32_t off = ok ? ((a_pix[j] + (uint32_t)(ih * p.W + iw)) * (uint32_t)p.Cin + (uint32_t)cin0) * 2u : SQ_OOB;
                 glds16(rsAh, sa + j * (ROUND * ROWB), off, 0);
                 glds16(rsAl, sa + A_BYTES + j * (ROUND * ROWB), off, 0);
             }
 #pragma unroll
             for (int j = 0; j < RBP; ++j) {
-                const uint32_t ob = k_ok ? b_off[j] + (p.b_tiled ? (uint32_t)kt * (uint32_t)p.N * 64u : (uint32_t)(k0 * 2)) : OOB;
+                const uint32_t ob = k_ok ? b_off[j] + (p.b_tiled ? (uint32_t)kt * (uint32_t)p.N * 64u : (uint32_t)(k0 * 2)) : SQ_OOB;
                 if constexpr (Cfg::SPLIT_B) {
                     if (b_lo_half) glds16(rsBl, sb, ob, 0); else glds16(rsBh, sb, ob, 0);
                 } else {
@@ -168,13 +158,13 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
             const int soffb = p.b_tiled ? kt * p.N * 64 : soff;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const uint32_t off = k_ok ? a_off[j] : OOB;
+                const uint32_t off = k_ok ? a_off[j] : SQ_OOB;
                 glds16(rsAh, sa + j * (ROUND * ROWB), off, soff);
                 glds16(rsAl, sa + A_BYTES + j * (ROUND * ROWB), off, soff);
             }
 #pragma unroll
             for (int j = 0; j < RBP; ++j) {
-                const uint32_t ob = k_ok ? b_off[j] : OOB;
+                const uint32_t ob = k_ok ? b_off[j] : SQ_OOB;
                 if constexpr (Cfg::SPLIT_B) {
                     if (b_lo_half) glds16(rsBl, sb, ob, soffb); else glds16(rsBh, sb, ob, soffb);
                 } else {
@@ -253,16 +243,16 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
         const char* st = smem + buf * STAGE_BYTES;
         u32x4 ah[2][WTM], al[2][WTM], bh[2][WTN], bl[2][WTN];
 #pragma unroll
-        for (int i = 0; i < WTM; ++i) { ah[0][i] = lds_read128(st + fa_off[i][0]); al[0][i] = lds_read128(st + fa_off[i][0] + A_BYTES); }
+        for (int i = 0; i < WTM; ++i) { ah[0][i] = lds128(st + fa_off[i][0]); al[0][i] = lds128(st + fa_off[i][0] + A_BYTES); }
 #pragma unroll
-        for (int j = 0; j < WTN; ++j) { bh[0][j] = lds_read128(st + fb_off[j][0]); bl[0][j] = lds_read128(st + fb_off[j][0] + B_BYTES); }
+        for (int j = 0; j < WTN; ++j) { bh[0][j] = lds128(st + fb_off[j][0]); bl[0][j] = lds128(st + fb_off[j][0] + B_BYTES); }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             if (s == 0) {
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) { ah[1][i] = lds_read128(st + fa_off[i][1]); al[1][i] = lds_read128(st + fa_off[i][1] + A_BYTES); }
+                for (int i = 0; i < WTM; ++i) { ah[1][i] = lds128(st + fa_off[i][1]); al[1][i] = lds128(st + fa_off[i][1] + A_BYTES); }
 #pragma unroll
-                for (int j = 0; j < WTN; ++j) { bh[1][j] = lds_read128(st + fb_off[j][1]); bl[1][j] = lds_read128(st + fb_off[j][1] + B_BYTES); }
+                for (int j = 0; j < WTN; ++j) { bh[1][j] = lds128(st + fb_off[j][1]); bl[1][j] = lds128(st + fb_off[j][1] + B_BYTES); }
             }
             __builtin_amdgcn_sched_barrier(0);
             // the two correction terms first, the leading term last; consecutive MFMAs touch different accumulators
@@ -301,9 +291,9 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
 #pragma unroll
-                for (int i = 0; i < WTM; ++i) { ah[s][i] = lds_read128(st + fa_off[i][s]); al[s][i] = lds_read128(st + fa_off[i][s] + A_BYTES); }
+                for (int i = 0; i < WTM; ++i) { ah[s][i] = lds128(st + fa_off[i][s]); al[s][i] = lds128(st + fa_off[i][s] + A_BYTES); }
 #pragma unroll
-                for (int j = 0; j < WTN; ++j) { bh[s][j] = lds_read128(st + fb_off[j][s]); bl[s][j] = lds_read128(st + fb_off[j][s] + B_BYTES); }
+                for (int j = 0; j < WTN; ++j) { bh[s][j] = lds128(st + fb_off[j][s]); bl[s][j] = lds128(st + fb_off[j][s] + B_BYTES); }
             }
         };
         auto mma_all = [&]() {
@@ -396,10 +386,10 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
             __syncthreads();                            // every wave has read the first product's last tile
             const bf16_t* A2h = reinterpret_cast<const bf16_t*>(p.A2);
             const bf16_t* B2h = reinterpret_cast<const bf16_t*>(p.B2);
-            const auto rsXh = __builtin_amdgcn_make_buffer_rsrc((void*)A2h, 0, (int)p.a2_bytes, 0x00020000);
-            const auto rsXl = __builtin_amdgcn_make_buffer_rsrc((void*)(A2h + p.plA2), 0, (int)p.a2_bytes, 0x00020000);
-            const auto rsDh = __builtin_amdgcn_make_buffer_rsrc((void*)B2h, 0, (int)p.b2_bytes, 0x00020000);
-            const auto rsDl = __builtin_amdgcn_make_buffer_rsrc((void*)(B2h + p.plB), 0, (int)p.b2_bytes, 0x00020000);
+            const auto rsXh = sq_rsrc(A2h, (int)p.a2_bytes);
+            const auto rsXl = sq_rsrc(A2h + p.plA2, (int)p.a2_bytes);
+            const auto rsDh = sq_rsrc(B2h, (int)p.b2_bytes);
+            const auto rsDl = sq_rsrc(B2h + p.plB, (int)p.b2_bytes);
             uint32_t x_off[2], d_off[RBP];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -407,12 +397,12 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void gemm_x3_kernel(co
                 const int ohw = p.dOH * p.dOW;
                 const int img = m / ohw, rem = m - img * ohw, oh = rem / p.dOW, ow = rem - oh * p.dOW;
                 const uint32_t pix = (uint32_t)((img * p.dH + oh * p.dstride) * p.dW + ow * p.dstride);
-                x_off[j] = m < p.M ? (pix * (uint32_t)p.lda2 + (uint32_t)(gc * 8)) * 2u : OOB;
+                x_off[j] = m < p.M ? (pix * (uint32_t)p.lda2 + (uint32_t)(gc * 8)) * 2u : SQ_OOB;
             }
 #pragma unroll
             for (int j = 0; j < RBP; ++j) {
                 const int n = n0 + (Cfg::SPLIT_B ? (r0 & 63) : r0 + ROUND * j);
-                d_off[j] = n >= p.N ? OOB : p.b_tiled ? ((uint32_t)n * 32u + (uint32_t)(gc * 8)) * 2u : ((uint32_t)n * (uint32_t)p.ldb2 + (uint32_t)(gc * 8)) * 2u;
+                d_off[j] = n >= p.N ? SQ_OOB : p.b_tiled ? ((uint32_t)n * 32u + (uint32_t)(gc * 8)) * 2u : ((uint32_t)n * (uint32_t)p.ldb2 + (uint32_t)(gc * 8)) * 2u;
             }
             auto issue2 = [&](int kt, int buf) {
                 char* sa = smem + buf * STAGE_BYTES + wave * 1024;
@@ -659,29 +649,27 @@ int sq_launch_gemm_x3(const GemmArgs& a_in, hipStream_t stream) {
         SQ_REQUIRE(a.dOH > 0 && a.dOW > 0 && a.M % (a.dOH * a.dOW) == 0 && a.dstride >= 1 && (a.dOH - 1) * a.dstride < a.dH && (a.dOW - 1) * a.dstride < a.dW,
                    "gemm_x3 dual: gather geometry %dx%d -> %dx%d stride %d", a.dH, a.dW, a.dOH, a.dOW, a.dstride);
     }
-    int prof = -1;
-    if (sq_prof_on() && dual) {
+    SqProf prof(stream);
+    if (prof.on() && dual) {
         char name[96];
         snprintf(name, sizeof(name), "dual_%s_M%d_N%d_K%d_K%d", a.x3_f16 ? "f16x3" : "bf16x3", a.M, a.N, a.K, a.K2);
-        prof = sq_prof_begin(name, 2.0 * a.M * (double)a.N * (a.K + a.K2), ((double)a.M * (a.K + a.K2) + (double)a.N * (a.K + a.K2)) * 4.0 + (double)a.M * a.N * 4.0, stream);
-    } else if (sq_prof_on()) {
+        prof.begin(name, 2.0 * a.M * (double)a.N * (a.K + a.K2), ((double)a.M * (a.K + a.K2) + (double)a.N * (a.K + a.K2)) * 4.0 + (double)a.M * a.N * 4.0);
+    } else if (prof.on()) {
         const double flops = 2.0 * a.M * (double)a.N * a.K;      // algorithmic (fp32-equivalent) work; the kernel issues 3x that in bf16 MFMAs
         const double a_elems = a.conv ? (double)a.M / (a.OH * a.OW) * a.H * a.W * a.Cin : (double)a.M * a.K;
         const double bytes = (a_elems + (double)a.N * a.K) * 4.0 + (double)a.M * a.N * (4.0 + (a.res ? 4.0 : 0.0));
         char name[96];
         snprintf(name, sizeof(name), "%s_%s_M%d_N%d_K%d", a.conv ? "conv" : "gemm", a.x3_f16 ? "f16x3" : "bf16x3", a.M, a.N, a.K);
-        prof = sq_prof_begin(name, flops, bytes, stream);
+        prof.begin(name, flops, bytes);
     }
     // products with K up to this take the 128-row, two-blocks-per-CU shape (sq_dbg_set key 7 overrides: probes; 512 ... 2048 measured level in the pipeline)
     const int small_max_k = g_x3_small_max_k >= 0 ? g_x3_small_max_k : 256;
     const bool small = a.K <= small_max_k || (a.N <= 64 && small_max_k > 0);
-    const int rc = uni ? (small ? launch_x3_uni_fmt<128, false>(a, stream) : launch_x3_uni_fmt<256, true>(a, stream))
-                 : dual ? (a.x3_f16 ? launch_x3_dual<true>(a, stream) : launch_x3_dual<false>(a, stream))
-                 : (g_x3_halo != 0 && sq_conv_halo_x3_eligible(a)) ? sq_launch_conv_halo_x3(a, stream)
-                 : (a.K <= small_max_k || (a.N <= 64 && small_max_k > 0)) ? launch_x3_fmt<128, false>(a, stream)
-                 : launch_x3_fmt<256, true>(a, stream);
-    if (prof >= 0) sq_prof_end(prof, stream);
-    return rc;
+    return uni ? (small ? launch_x3_uni_fmt<128, false>(a, stream) : launch_x3_uni_fmt<256, true>(a, stream))
+         : dual ? (a.x3_f16 ? launch_x3_dual<true>(a, stream) : launch_x3_dual<false>(a, stream))
+         : (g_x3_halo != 0 && sq_conv_halo_x3_eligible(a)) ? sq_launch_conv_halo_x3(a, stream)
+         : (a.K <= small_max_k || (a.N <= 64 && small_max_k > 0)) ? launch_x3_fmt<128, false>(a, stream)
+         : launch_x3_fmt<256, true>(a, stream);
 }
 
 // C-ABI entry (include/sequoia_hip.h): one split-bf16 linear layer / convolution on caller-owned hi / lo planes

@@ -211,24 +211,24 @@ extern "C" int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, co
     const long long blocks = (long long)n_tiles * a.g.blocks;
     a.lanes = 1;
     while (a.lanes < ENT_THREADS && (n_tiles + a.lanes - 1) / a.lanes > ENT_MAX_WAVES) a.lanes *= 2;
-    const bool prof_on = sq_prof_on();
     char name[96];
-    int prof = -1;
     SQ_HIP_CHECK(hipMemsetAsync(a.coefs, 0, coef_bytes, stream));        // the entropy lanes write non-zero coefficients only
-    if (prof_on) { snprintf(name, sizeof(name), "jpeg_tables_s%d", n_table_sets); prof = sq_prof_begin(name, 0.0, (double)n_table_sets * 8000.0, stream); }
-    hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)((n_table_sets * 4 + 63) / 64)), dim3(64), 0, stream, a);
-    SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
-    prof = -1;
-    if (prof_on) { snprintf(name, sizeof(name), "jpeg_entropy_n%d_%dx%d", n_tiles, tile_w, tile_h); prof = sq_prof_begin(name, 0.0, (double)scans_bytes + (double)coef_bytes, stream); }
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((n_tiles + a.lanes - 1) / a.lanes)), dim3(ENT_THREADS), 0, stream, a);
-    SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
-    prof = -1;
-    if (prof_on) { snprintf(name, sizeof(name), "jpeg_idct_n%d_%dx%d", n_tiles, tile_w, tile_h); prof = sq_prof_begin(name, 0.0, (double)coef_bytes + (double)n_tiles * a.g.plane_bytes, stream); }
+    {   // one profiling bracket per launch
+        SqProf prof(stream);
+        if (prof.on()) { snprintf(name, sizeof(name), "jpeg_tables_s%d", n_table_sets); prof.begin(name, 0.0, (double)n_table_sets * 8000.0); }
+        hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)((n_table_sets * 4 + 63) / 64)), dim3(64), 0, stream, a);
+        SQ_LAUNCH_CHECK();
+    }
+    {
+        SqProf prof(stream);
+        if (prof.on()) { snprintf(name, sizeof(name), "jpeg_entropy_n%d_%dx%d", n_tiles, tile_w, tile_h); prof.begin(name, 0.0, (double)scans_bytes + (double)coef_bytes); }
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((n_tiles + a.lanes - 1) / a.lanes)), dim3(ENT_THREADS), 0, stream, a);
+        SQ_LAUNCH_CHECK();
+    }
+    SqProf prof(stream);
+    if (prof.on()) { snprintf(name, sizeof(name), "jpeg_idct_n%d_%dx%d", n_tiles, tile_w, tile_h); prof.begin(name, 0.0, (double)coef_bytes + (double)n_tiles * a.g.plane_bytes); }
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(IDCT_THREADS), 0, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }
 
@@ -256,14 +256,13 @@ extern "C" int sq_jpeg_compose_regions(const uint8_t* planes, int n_slots, int t
     const long long total = (long long)k * h * a.groups;
     const long long want = (total + CMP_THREADS - 1) / CMP_THREADS;
     const unsigned grid = (unsigned)(want < 65536 ? want : 65536);
-    int prof = -1;
-    if (sq_prof_on()) {
+    SqProf prof(stream);
+    if (prof.on()) {
         char name[96];
         snprintf(name, sizeof(name), "jpeg_compose_k%d_%dx%d", k, w, h);
-        prof = sq_prof_begin(name, 0.0, (double)k * h * w * 6.0, stream);
+        prof.begin(name, 0.0, (double)k * h * w * 6.0);
     }
     hipLaunchKernelGGL(jpeg_compose_kernel, dim3(grid), dim3(CMP_THREADS), 0, stream, a);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

@@ -21,6 +21,23 @@ bool sq_env_flag(const char* name);                           // set and not "0"
 int sq_prof_begin(const char* name, double flops, double bytes, hipStream_t st);
 void sq_prof_end(int idx, hipStream_t st);
 
+// Profiling bracket of a launcher:   SqProf prof(stream);  if (prof.on()) prof.begin(name, flops, bytes);   Begun only while
+// profiling is on, so the name's snprintf and the flops / bytes arithmetic cost nothing otherwise; ended where the scope is
+// left, on every return path (SQ_LAUNCH_CHECK and SQ_HIP_CHECK return early).
+struct SqProf {
+    hipStream_t st;
+    int idx = -1;
+    explicit SqProf(hipStream_t s) : st(s) {}
+    SqProf(const SqProf&) = delete;
+    SqProf& operator=(const SqProf&) = delete;
+    ~SqProf() { if (idx >= 0) sq_prof_end(idx, st); }
+    static bool on() { return sq_prof_on(); }
+    void begin(const char* name, double flops, double bytes) { idx = sq_prof_begin(name, flops, bytes, st); }
+};
+
+// Byte extent of a buffer descriptor: at most 0x7fffffff, so that an offset with bit 31 set (SQ_OOB, cdna_prims.h) is out of range.
+static inline uint32_t sq_desc_extent(size_t bytes) { return (uint32_t)(bytes < 0x7fffffffu ? bytes : 0x7fffffffu); }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE setting: a launcher's attribute block has to run once for
 // every device the process drives, not once per process.  Setting it twice from two threads is harmless.
 struct SqDevOnce {

@@ -136,11 +136,10 @@ __global__ __launch_bounds__(256) void summary_fwd_kernel(const bf16_t* __restri
 int sq_launch_summary_fwd(const void* Xbar, const void* Ws, const float* bs, const float* lng, const float* lnb, const void* Wc,
                           const float* bc, float* Sm, void* Ts, float* Cs, int B, int D, int H, hipStream_t stream) {
     SQ_REQUIRE(D % 64 == 0 && B >= 1 && H >= 1, "summary_fwd: D=%d must be a multiple of 64", D);
-    int prof = -1;
-    if (sq_prof_on()) prof = sq_prof_begin("summary_fwd_bf16", 2.0 * B * (double)H * 64 * (D + 64), ((double)B * D + (double)H * 64 * D) * 2.0, stream);
+    SqProf prof(stream);
+    if (prof.on()) prof.begin("summary_fwd_bf16", 2.0 * B * (double)H * 64 * (D + 64), ((double)B * D + (double)H * 64 * D) * 2.0);
     hipLaunchKernelGGL(summary_fwd_kernel, dim3(H, (B + 63) / 64), dim3(256), 0, stream, (const bf16_t*)Xbar, (const bf16_t*)Ws, bs, lng, lnb,
                        (const bf16_t*)Wc, bc, Sm, (bf16_t*)Ts, Cs, B, D, H * 64);
     SQ_LAUNCH_CHECK();
-    if (prof >= 0) sq_prof_end(prof, stream);
     return SQ_OK;
 }

@@ -9,7 +9,7 @@
 //                 units, an eighth of the 2^-25 above.  Pinned by tests/test_gpu_x3.py::test_f16x3_subnormal_planes_*.
 // Both feed 16-bit MFMAs at the same rate; a product is a_hi.b_hi + a_hi.b_lo + a_lo.b_hi with fp32 accumulation.
 #pragma once
-#include "sq_common.h"
+#include "cdna_prims.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -24,11 +24,7 @@ template <> struct X3Fmt<false> {
     static __device__ __forceinline__ float sum_lo(uint32_t h, uint32_t l) { return lo_f(h) + lo_f(l); }     // element 0 of hi + lo
     static __device__ __forceinline__ float sum_hi(uint32_t h, uint32_t l) { return hi_f(h) + hi_f(l); }
     static __device__ __forceinline__ uint32_t rest2(float a, float b, uint32_t h) { return pack2(a - lo_f(h), b - hi_f(h)); }   // the lo plane of (a, b) given their hi plane
-    static __device__ __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x16& acc) {
-        union { u32x4 u; bf16x8 h; } ua, ub;
-        ua.u = a; ub.u = b;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.h, ub.h, acc, 0, 0, 0);
-    }
+    static __device__ __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x16& acc) { acc = mfma_bf16(a, b, acc); }
 };
 
 template <> struct X3Fmt<true> {
