@@ -7,6 +7,7 @@ streams are shared.  There is no fallback: a missing library or GPU raises.
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from . import _abi
@@ -86,6 +87,53 @@ def stream_ptr(device=None):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def need(fn, *args):
+    """The byte count an entry's ``*_workspace_bytes`` (or ``*_bytes``) function asks for.  It is 0 exactly for the shapes the entry
+    refuses (include/sequoia_hip.h): that raises the library's own sentence (sq_last_error) as a ``SequoiaHipArgError``."""
+    n = fn(*args)
+    if n == 0:
+        check(SQ_ERR_ARG)
+    return n
+
+
+def marshal(fn, args, workspace=None):
+    """(fn, args) of ``call`` as ctypes takes them, the stream left out; touches no device.  ``fn``: a ctypes function or an
+    entry's name.  A tensor goes as its address (a slice as the address of its first element, an empty one as 0), a numpy
+    array -- C-contiguous, or ValueError -- as the address of its data; None (the null pointer), numbers, ``ctypes.byref``, ctypes
+    arrays and ``c_void_p`` pass as they are.  ``workspace``: a uint8 tensor whose address and size in bytes come last."""
+    if isinstance(fn, str):
+        fn = getattr(lib(), fn)
+    out = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            a = a.data_ptr()
+        elif isinstance(a, np.ndarray):
+            if not a.flags.c_contiguous:
+                raise ValueError(f"{fn.__name__}: a numpy argument of shape {a.shape} is not C-contiguous; the library reads packed arrays")
+            a = a.ctypes.data
+        out.append(a)
+    if workspace is not None:
+        out += [workspace.data_ptr(), workspace.numel()]
+    return fn, out
+
+
+def call(fn, device, *args, workspace=None, after=()):
+    """One library launch on ``device`` and its current stream: the arguments as ``marshal`` turns them, then the workspace pair, then
+    the stream, read under the device guard at call time (so a call inside ``torch.cuda.stream(s)`` lands on ``s``), then ``after`` as
+    it is (sq_vis_backward_buckets takes its events behind the stream).  The library keys per-device state (its once-flags, side
+    streams and profiler slots) on the current device: the guard is here so that no launch can be made without it.
+    workspace: a uint8 tensor the caller keeps, or a byte count -- the entry's ``*_workspace_bytes`` -- for scratch of that size.
+    The count is 0 exactly for the shapes the entry refuses, so nothing is tested here: the one real call is made, the library's
+    own first check refuses it and ``check`` raises its message (a ``SequoiaHipArgError``).
+    ``args`` holds every tensor and array, temporaries made in the argument list too, until the entry has returned."""
+    if workspace is not None and not isinstance(workspace, torch.Tensor):
+        args += (torch.empty(max(workspace, 8), dtype=torch.uint8, device=device), workspace)
+        workspace = None
+    fn, argv = marshal(fn, args, workspace)
+    with torch.cuda.device(device):
+        check(fn(*argv, stream_ptr(device), *after))
 
 
 def prof_enable(on, markers=False):

@@ -1,11 +1,12 @@
-"""What the wrappers of the slide analytics (mapstats.py, gtalign.py, spotnorm.py) share: a device table, column list or vector turned
-into the arguments of the C ABI, and the one way a call is made and a shape is refused."""
+"""What the wrappers of the slide analytics (mapstats.py, gtalign.py, spotnorm.py, emd.py) share: a device table, column list or vector
+turned into the arguments of the C ABI.  The one way a call is made and a shape is refused is the whole package's: ``_lib.call``."""
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import call  # noqa: F401  (the analytics wrappers import it from here)
 
 
 def _on_device(t, what):
@@ -76,18 +77,3 @@ def empty(dtype, device, *shape):
     if 0 not in shape:
         return torch.empty(shape, dtype=dtype, device=device)
     return torch.empty([max(s, 1) for s in shape], dtype=dtype, device=device)[tuple(slice(0, s) for s in shape)]
-
-
-def call(fn, device, *args, workspace=None):
-    """One library call on ``device`` and its current stream: tensors go as their addresses (None is the null pointer
-    of a ``c_void_p`` parameter as it is), the stream comes last.
-    workspace: the entry's ``*_workspace_bytes`` -- scratch of that size goes in front of the stream.  It is 0 exactly
-    for the shapes the entry refuses (include/sequoia_hip.h), so nothing is tested here: the one real call is made, the
-    library's own first check refuses it and ``_lib.check`` raises its message (a ``SequoiaHipArgError``)."""
-    tensor = torch.Tensor
-    args = [a.data_ptr() if isinstance(a, tensor) else a for a in args]
-    with torch.cuda.device(device):
-        if workspace is not None:
-            ws = torch.empty(max(workspace, 8), dtype=torch.uint8, device=device)
-            args += [ws.data_ptr(), workspace]
-        _lib.check(fn(*args, _lib.stream_ptr(device)))

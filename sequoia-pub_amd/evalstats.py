@@ -41,11 +41,8 @@ def device_stats(real, pred, random, device="cuda:0"):
     need = _lib.lib().sq_gene_eval_workspace_bytes(n, G)
     if need == 0:
         raise ValueError(f"unsupported test-set size n={n} (2..8192 samples)")
-    ws = torch.empty(need, dtype=torch.uint8, device=t[0].device)
     out = torch.empty(9, G, dtype=torch.float64, device=t[0].device)
-    with torch.cuda.device(t[0].device):
-        _lib.check(_lib.lib().sq_gene_eval_stats(_lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]), n, G, _lib.ptr(out),
-                                                 _lib.ptr(ws), need, _lib.stream_ptr(t[0].device)))
+    _lib.call("sq_gene_eval_stats", t[0].device, *t, n, G, out, workspace=need)
     return out.cpu().numpy(), n
 
 

@@ -55,28 +55,25 @@ def _layer_stack(xt, m, p_drop=0.0, dst=None):
     rows, and the reference's default layers=[1] has a hidden width of ONE.  `dst`: where the last layer writes (f32 [M, ld >= G]
     rows, e.g. a slice of a score table) instead of a new tensor.  Returns (acts -- the padded input and every layer's output --,
     dropout masks or None per layer): what the backward pass needs; acts[-1][:, :G] are the scores."""
-    lib, dev, flat = _lib.lib(), xt.device, m.flat.detach()
+    dev, flat = xt.device, m.flat.detach()
     if not xt.is_cuda or flat.device != dev:
         raise _lib.SequoiaHipError(f"HE2RNA: parameters on {flat.device}, input on {dev}: both must be on the same GPU (no CPU fallback)")
     (M, C), ws = xt.shape, m._workspace(dev)
-    with torch.cuda.device(dev):                      # the library keys per-device state on the current device
-        st = _lib.stream_ptr(dev)
-        a = torch.zeros(M, _up(m.input_dim, 8), dtype=torch.float32, device=dev)
-        a[:, :m.input_dim] = xt[:, C - m.input_dim:]
-        acts, drops = [a], []
-        for i in range(m.n_layers):
-            n_out, k_pad = int(m.dims[i + 1]), acts[-1].shape[1]
-            last = i + 1 == m.n_layers
-            out = dst if last and dst is not None else torch.zeros(M, _up(n_out, 8), dtype=torch.float32, device=dev)
-            _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(acts[-1]), k_pad, _lib.ptr(flat[m.w_off[i]:]), k_pad, _lib.ptr(flat[m.b_off[i]:]),
-                                     None, 0, _lib.SQ_F32, 0 if last else 2, _lib.ptr(out), _lib.SQ_F32, out.shape[1], M, n_out, k_pad,
-                                     _lib.ptr(ws), ws.numel(), st))
-            dm = None
-            if not last and p_drop > 0.0:
-                dm = (torch.rand(M, out.shape[1], device=dev) >= p_drop).to(torch.float32) / (1.0 - p_drop)
-                out.mul_(dm)
-            drops.append(dm)
-            acts.append(out)
+    a = torch.zeros(M, _up(m.input_dim, 8), dtype=torch.float32, device=dev)
+    a[:, :m.input_dim] = xt[:, C - m.input_dim:]
+    acts, drops = [a], []
+    for i in range(m.n_layers):
+        n_out, k_pad = int(m.dims[i + 1]), acts[-1].shape[1]
+        last = i + 1 == m.n_layers
+        out = dst if last and dst is not None else torch.zeros(M, _up(n_out, 8), dtype=torch.float32, device=dev)
+        _lib.call("sq_linear", dev, _lib.SQ_F32, acts[-1], k_pad, flat[m.w_off[i]:], k_pad, flat[m.b_off[i]:], None, 0, _lib.SQ_F32,
+                  0 if last else 2, out, _lib.SQ_F32, out.shape[1], M, n_out, k_pad, workspace=ws)
+        dm = None
+        if not last and p_drop > 0.0:
+            dm = (torch.rand(M, out.shape[1], device=dev) >= p_drop).to(torch.float32) / (1.0 - p_drop)
+            out.mul_(dm)
+        drops.append(dm)
+        acts.append(out)
     return acts, drops
 
 
@@ -87,54 +84,49 @@ class _He2rnaFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, x, m, ks, scale, p_drop):
-        lib, dev, (B, C, N) = _lib.lib(), x.device, x.shape
+        dev, (B, C, N) = x.device, x.shape
         M = B * N
         xt = x.detach().to(torch.float32).transpose(1, 2).contiguous().view(M, C)        # free when x came from 'b c f -> b f c'
         ks_arr = np.asarray(ks, dtype=np.int32)
         mask = torch.empty(M, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.sq_he2rna_tile_mask(_lib.ptr(xt), M, C, _lib.ptr(mask), st))
-            acts, drops = _layer_stack(xt, m, p_drop)
-            pred = torch.empty(B, m.output_dim, dtype=torch.float32, device=dev)
-            _lib.check(lib.sq_he2rna_topk_mean(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), float(scale),
-                                               _lib.ptr(pred), B, N, m.output_dim, st))
+        _lib.call("sq_he2rna_tile_mask", dev, xt, M, C, mask)
+        acts, drops = _layer_stack(xt, m, p_drop)
+        pred = torch.empty(B, m.output_dim, dtype=torch.float32, device=dev)
+        _lib.call("sq_he2rna_topk_mean", dev, acts[-1], acts[-1].shape[1], mask, ks_arr, len(ks_arr), float(scale), pred, B, N, m.output_dim)
         ctx.save_for_backward(flat)                    # autograd refuses the backward pass if the buffer was written in between
         ctx.saved = (acts, drops, mask, ks_arr, float(scale), (B, C, N), (m.dims, m.w_off, m.b_off), m._workspace(dev))
         return pred
 
     @staticmethod
     def backward(ctx, gout):
-        lib, dev, (flat,) = _lib.lib(), gout.device, ctx.saved_tensors
+        dev, (flat,) = gout.device, ctx.saved_tensors
         acts, drops, mask, ks_arr, scale, (B, C, N), (dims, w_off, b_off), ws = ctx.saved
         M, input_dim, G = B * N, int(dims[0]), int(dims[-1])
         gflat = torch.zeros_like(flat)
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            dy = torch.zeros_like(acts[-1])
-            _lib.check(lib.sq_he2rna_topk_mean_bwd(_lib.ptr(acts[-1]), acts[-1].shape[1], _lib.ptr(mask), ks_arr.ctypes.data, len(ks_arr), scale,
-                                                   _lib.ptr(gout.detach().float().contiguous()), _lib.ptr(dy), dy.shape[1], B, N, G, st))
-            for i in range(len(w_off) - 1, -1, -1):
-                a_in, n_out = acts[i], int(dims[i + 1])
-                k_pad = a_in.shape[1]
-                _lib.check(lib.sq_linear_weight_grad(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(a_in), k_pad, _lib.ptr(gflat[w_off[i]:]), k_pad,
-                                                     _lib.ptr(gflat[b_off[i]:]), n_out, k_pad, M, _lib.ptr(ws), ws.numel(), st))
-                if i > 0 or ctx.needs_input_grad[1]:
-                    wt = torch.zeros(k_pad, dy.shape[1], dtype=torch.float32, device=dev)      # W^T, contraction over the padded outputs
-                    wt[:, :n_out] = flat[w_off[i]:w_off[i] + n_out * k_pad].view(n_out, k_pad).t()
-                    dx = torch.empty(M, k_pad, dtype=torch.float32, device=dev)
-                    _lib.check(lib.sq_linear(_lib.SQ_F32, _lib.ptr(dy), dy.shape[1], _lib.ptr(wt), wt.shape[1], None, None, 0, _lib.SQ_F32, 0,
-                                             _lib.ptr(dx), _lib.SQ_F32, k_pad, M, k_pad, dy.shape[1], _lib.ptr(ws), ws.numel(), st))
-                    if i > 0:
-                        dx.mul_((a_in > 0).to(torch.float32))          # ReLU (a dropped unit is 0 here and gets no gradient either way)
-                        if drops[i - 1] is not None:
-                            dx.mul_(drops[i - 1])
-                    dy = dx
-            gx = None
-            if ctx.needs_input_grad[1]:
-                gx = torch.zeros(B, N, C, dtype=torch.float32, device=dev)
-                gx[:, :, C - input_dim:] = dy[:, :input_dim].view(B, N, input_dim)
-                gx = gx.transpose(1, 2)
+        dy = torch.zeros_like(acts[-1])
+        _lib.call("sq_he2rna_topk_mean_bwd", dev, acts[-1], acts[-1].shape[1], mask, ks_arr, len(ks_arr), scale,
+                  gout.detach().float().contiguous(), dy, dy.shape[1], B, N, G)
+        for i in range(len(w_off) - 1, -1, -1):
+            a_in, n_out = acts[i], int(dims[i + 1])
+            k_pad = a_in.shape[1]
+            _lib.call("sq_linear_weight_grad", dev, _lib.SQ_F32, dy, dy.shape[1], a_in, k_pad, gflat[w_off[i]:], k_pad, gflat[b_off[i]:],
+                      n_out, k_pad, M, workspace=ws)
+            if i > 0 or ctx.needs_input_grad[1]:
+                wt = torch.zeros(k_pad, dy.shape[1], dtype=torch.float32, device=dev)      # W^T, contraction over the padded outputs
+                wt[:, :n_out] = flat[w_off[i]:w_off[i] + n_out * k_pad].view(n_out, k_pad).t()
+                dx = torch.empty(M, k_pad, dtype=torch.float32, device=dev)
+                _lib.call("sq_linear", dev, _lib.SQ_F32, dy, dy.shape[1], wt, wt.shape[1], None, None, 0, _lib.SQ_F32, 0,
+                          dx, _lib.SQ_F32, k_pad, M, k_pad, dy.shape[1], workspace=ws)
+                if i > 0:
+                    dx.mul_((a_in > 0).to(torch.float32))          # ReLU (a dropped unit is 0 here and gets no gradient either way)
+                    if drops[i - 1] is not None:
+                        dx.mul_(drops[i - 1])
+                dy = dx
+        gx = None
+        if ctx.needs_input_grad[1]:
+            gx = torch.zeros(B, N, C, dtype=torch.float32, device=dev)
+            gx[:, :, C - input_dim:] = dy[:, :input_dim].view(B, N, input_dim)
+            gx = gx.transpose(1, 2)
         return gflat, gx, None, None, None, None
 
 
@@ -243,8 +235,7 @@ class HE2RNA(nn.Module, FlatParams, PyTorchModelHubMixin):
         scores = torch.empty(n, _up(self.output_dim, 8), dtype=torch.float32, device=dev)
         if n == 0:
             return scores, mask
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sq_he2rna_tile_mask(_lib.ptr(x), n, C, _lib.ptr(mask), _lib.stream_ptr(dev)))
+        _lib.call("sq_he2rna_tile_mask", dev, x, n, C, mask)
         for r0 in range(0, n, self.TILE_ROWS):
             r1 = min(n, r0 + self.TILE_ROWS)
             _layer_stack(x[r0:r1], self, dst=scores[r0:r1])
@@ -261,10 +252,8 @@ class HE2RNA(nn.Module, FlatParams, PyTorchModelHubMixin):
         out = torch.empty(W, G, dtype=torch.float32, device=scores.device)
         if W == 0:
             return out
-        with torch.cuda.device(scores.device):
-            _lib.check(_lib.lib().sq_he2rna_window_topk_mean(_lib.ptr(scores), scores.shape[1], _lib.ptr(mask), scores.shape[0], _lib.ptr(members),
-                                                             ks.ctypes.data, len(ks), 1.0 / len(ks), _lib.ptr(out), W, N, G,
-                                                             _lib.stream_ptr(scores.device)))
+        _lib.call("sq_he2rna_window_topk_mean", scores.device, scores, scores.shape[1], mask, scores.shape[0], members, ks, len(ks),
+                  1.0 / len(ks), out, W, N, G)
         return out
 
     def conv(self, x):
@@ -331,9 +320,7 @@ class He2rnaTrainStep:
         if self._shape != (B, N):
             m = self.model
             off = np.zeros(m.n_layers + 1, dtype=np.int64)
-            need = _lib.lib().sq_he2rna_train_workspace_bytes(m.dims.ctypes.data, m.n_layers, B, N, off.ctypes.data)
-            if need == 0:
-                raise _lib.SequoiaHipArgError(f"libsequoia_hip: {_lib.lib().sq_last_error().decode()}")
+            need = _lib.need(_lib.lib().sq_he2rna_train_workspace_bytes, m.dims.ctypes.data, m.n_layers, B, N, off.ctypes.data)
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._shape, self._act_off = (B, N), [int(o) for o in off]
@@ -350,7 +337,7 @@ class He2rnaTrainStep:
     def forward_backward(self, x, y, k):
         """Loss (device scalar) and flat gradient of one batch at top-k `k`, without the update.  x [B, N, C] as the loader
         gives it (tiles x channels), y [B, G]."""
-        lib, dev, m, flat = _lib.lib(), self.device, self.model, self.flat
+        dev, m, flat = self.device, self.model, self.flat
         x = x.to(dev, torch.float32).contiguous()
         y = torch.as_tensor(y).to(dev, torch.float32).contiguous()
         G = m.output_dim
@@ -362,13 +349,9 @@ class He2rnaTrainStep:
         ks = np.asarray([int(k)], dtype=np.int32)
         self.pred = torch.empty(B, G, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.sq_he2rna_train_forward(_lib.ptr(x), B, N, C, m.dims.ctypes.data, m.n_layers, _lib.ptr(flat), ks.ctypes.data, 1,
-                                                   1.0, m.p_drop, self.seed, self.step_index, _lib.ptr(y), 2.0 / (B * G), _lib.ptr(self.pred),
-                                                   _lib.ptr(loss), _lib.ptr(ws), ws.numel(), st))
-            _lib.check(lib.sq_he2rna_train_backward(B, N, m.dims.ctypes.data, m.n_layers, _lib.ptr(flat), m.p_drop, _lib.ptr(self.grad),
-                                                    _lib.ptr(ws), ws.numel(), st))
+        _lib.call("sq_he2rna_train_forward", dev, x, B, N, C, m.dims, m.n_layers, flat, ks, 1, 1.0, m.p_drop, self.seed, self.step_index,
+                  y, 2.0 / (B * G), self.pred, loss, workspace=ws)
+        _lib.call("sq_he2rna_train_backward", dev, B, N, m.dims, m.n_layers, flat, m.p_drop, self.grad, workspace=ws)
         return loss
 
     def step(self, x, y):
@@ -378,10 +361,8 @@ class He2rnaTrainStep:
         loss = self.forward_backward(x, y, k)
         self.t += 1
         self.step_index += 1
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sq_adamw_step(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), None,
-                                                self.total, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, self.t, 1.0,
-                                                _lib.stream_ptr(self.device)))
+        _lib.call("sq_adamw_step", self.device, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, None, self.total, self.lr, self.betas[0],
+                  self.betas[1], self.eps, 0.0, self.t, 1.0)
         return loss
 
 
@@ -465,8 +446,7 @@ def device_validation_score(pred, labels):
     y = labels.to(dev, torch.float32).contiguous()
     out3 = torch.empty(3, dtype=torch.float32, device=dev)
     scratch = torch.empty(lib.sq_train_scratch_bytes(G), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sq_batch_metrics(_lib.ptr(p), _lib.ptr(y), n, G, _lib.ptr(out3), _lib.ptr(scratch), _lib.stream_ptr(dev)))
+    _lib.call("sq_batch_metrics", dev, p, y, n, G, out3, scratch)
     return out3[1]
 
 

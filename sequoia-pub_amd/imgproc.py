@@ -23,9 +23,7 @@ def resize_plan(h_in, w_in, h_out, w_out, resample="bilinear"):
     """The host plan of sq_resize_plan_init as an int32 array (layout: include/sequoia_hip.h).  Needs no GPU."""
     L = _lib.lib()
     flt = _filter_id(resample)
-    need = L.sq_resize_plan_bytes(h_in, w_in, h_out, w_out, flt)
-    if need == 0:
-        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    need = _lib.need(L.sq_resize_plan_bytes, h_in, w_in, h_out, w_out, flt)
     plan = np.empty(need // 4, dtype=np.int32)
     _lib.check(L.sq_resize_plan_init(h_in, w_in, h_out, w_out, flt, plan.ctypes.data_as(ctypes.c_void_p), need))
     return plan
@@ -89,9 +87,7 @@ def resize_u8_pil(patches_u8, size, resample="bilinear", index=None):
     out = torch.empty(m, h, w, 3, dtype=torch.uint8, device=dev)
     if m == 0:
         return out
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().sq_resize_u8_gather(_lib.ptr(x), n, C, _lib.ptr(idx), m, H, W, _lib.ptr(out), h, w, flt, _lib.ptr(plan),
-                                                  _lib.stream_ptr(dev)))
+    _lib.call("sq_resize_u8_gather", dev, x, n, C, idx, m, H, W, out, h, w, flt, plan)
     return out
 
 
@@ -104,8 +100,7 @@ def pack_rgb(tiles_u8, index=None):
     out = torch.empty(m, H, W, 3, dtype=torch.uint8, device=x.device)
     if m == 0:
         return out
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().sq_pack_rgb_gather(_lib.ptr(x), n, C, _lib.ptr(idx), m, H, W, _lib.ptr(out), _lib.stream_ptr(x.device)))
+    _lib.call("sq_pack_rgb_gather", x.device, x, n, C, idx, m, H, W, out)
     return out
 
 
@@ -125,6 +120,5 @@ def _resize_rgb(patches_u8, size, resample):
     out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
     if n == 0:
         return out
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().sq_resize_u8(_lib.ptr(x), n, H, W, _lib.ptr(out), h, w, flt, _lib.ptr(plan), _lib.stream_ptr(dev)))
+    _lib.call("sq_resize_u8", dev, x, n, H, W, out, h, w, flt, plan)
     return out

@@ -79,19 +79,17 @@ def _fit(route, X, counts, n_clusters, random_state, max_iter, tol, want_means):
         S, n = len(counts), counts[0]
         ns = np.ascontiguousarray(counts, dtype=np.int32)
         firsts = np.array([_first_center(c, k, random_state) for c in counts], dtype=np.int32)
-        shape, need = (S, ns.ctypes.data), int(L.sq_kmeans_ragged_workspace_bytes(S, ns.ctypes.data, D, k))
+        shape, need = (S, ns), int(L.sq_kmeans_ragged_workspace_bytes(S, ns.ctypes.data, D, k))
     X = X.to(torch.float32).contiguous()
     u_dev, trials = _uniforms(k, random_state, dev)
-    first = firsts.ctypes.data if route == "ragged" else _first_center(n, k, random_state)
+    first = firsts if route == "ragged" else _first_center(n, k, random_state)
     labels = torch.empty(X.shape[0], dtype=torch.int32, device=dev)
     means = torch.empty(S, k, D, dtype=torch.float32, device=dev) if want_means else None
     seeds = torch.empty(S, k, dtype=torch.int32, device=dev)
     n_iter = torch.empty(S, dtype=torch.int32, device=dev)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     entry = dict(batch=L.sq_kmeans_fit, large=L.sq_kmeans_fit_large, ragged=L.sq_kmeans_fit_ragged)[route]
-    with torch.cuda.device(dev):
-        _lib.check(entry(_lib.ptr(X), *shape, D, k, first, _lib.ptr(u_dev), trials, max_iter, float(tol), _lib.ptr(labels), _lib.ptr(means),
-                         _lib.ptr(seeds), _lib.ptr(n_iter), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+    _lib.call(entry, dev, X, *shape, D, k, first, u_dev, trials, max_iter, float(tol), labels, means, seeds, n_iter, workspace=ws)
     return dict(labels=labels, cluster_features=means, indices=seeds, n_iter=n_iter)
 
 

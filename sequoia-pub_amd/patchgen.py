@@ -156,20 +156,14 @@ def filter_patches(patches_u8, rgb_min=50, background_threshold=0.2, fraction_th
     x = patches_u8.contiguous()
     n, H, W, C = x.shape
     dev = x.device
-    L = _lib.lib()
-    need = L.sq_patch_filter_workspace_bytes(max(n, 1), H, W)       # refuses a bad size with the library's message
-    if need == 0:
-        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    need = _lib.need(_lib.lib().sq_patch_filter_workspace_bytes, max(n, 1), H, W)       # refuses a bad size with the library's message
     keep = torch.empty(n, dtype=torch.uint8, device=dev)
     stats = torch.empty(n, 8, dtype=torch.float64, device=dev) if return_stats else None
     raw = torch.empty(n, H, W, dtype=torch.uint8, device=dev) if return_masks else None
     dil = torch.empty(n, H, W, dtype=torch.uint8, device=dev) if return_masks else None
     if n:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.sq_patch_filter_px(_lib.ptr(x), n, H, W, C, int(rgb_min), float(background_threshold), float(fraction_threshold),
-                                            _lib.ptr(keep), _lib.ptr(stats), _lib.ptr(raw), _lib.ptr(dil), _lib.ptr(ws), need,
-                                            _lib.stream_ptr(dev)))
+        _lib.call("sq_patch_filter_px", dev, x, n, H, W, C, int(rgb_min), float(background_threshold), float(fraction_threshold),
+                  keep, stats, raw, dil, workspace=need)
     out = (keep.bool(),)
     if return_stats:
         out += (stats,)
@@ -195,18 +189,12 @@ def slide_mask(img_u8, rgb_min=50, iterations=3, transpose=False, return_raw=Fal
     x = img_u8.contiguous()
     H, W, C = x.shape
     dev = x.device
-    L = _lib.lib()
-    need = L.sq_slide_mask_workspace_bytes(H, W)                    # refuses a bad size with the library's message
-    if need == 0:
-        raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
+    need = _lib.need(_lib.lib().sq_slide_mask_workspace_bytes, H, W)                    # refuses a bad size with the library's message
     shape = (W, H) if transpose else (H, W)
     closed = torch.empty(shape, dtype=torch.uint8, device=dev)
     raw = torch.empty(shape, dtype=torch.uint8, device=dev) if return_raw else None
     stats = torch.empty(8, dtype=torch.float64, device=dev) if return_stats else None
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.sq_slide_mask_px(_lib.ptr(x), H, W, C, int(rgb_min), int(iterations), int(bool(transpose)), _lib.ptr(raw),
-                                      _lib.ptr(closed), _lib.ptr(stats), _lib.ptr(ws), need, _lib.stream_ptr(dev)))
+    _lib.call("sq_slide_mask_px", dev, x, H, W, C, int(rgb_min), int(iterations), int(bool(transpose)), raw, closed, stats, workspace=need)
     out = (closed.view(torch.bool),)
     if return_raw:
         out += (raw.view(torch.bool),)
@@ -262,10 +250,8 @@ def valid_tile_grid(mask, slide_dims, patch_size_resized, iterations=3, threshol
     counts = torch.empty((n_col, n_row), dtype=torch.int32, device=dev) if return_counts else None
     sizes = torch.empty((n_col, n_row), dtype=torch.int32, device=dev) if return_counts else None
     if n_col and n_row:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sq_tile_grid_valid(_lib.ptr(x), x.shape[0], x.shape[1], n_col, n_row, int(patch_size_resized), ds, pm,
-                                                     int(iterations), float(threshold), _lib.ptr(valid), _lib.ptr(counts), _lib.ptr(sizes),
-                                                     _lib.stream_ptr(dev)))
+        _lib.call("sq_tile_grid_valid", dev, x, x.shape[0], x.shape[1], n_col, n_row, int(patch_size_resized), ds, pm,
+                  int(iterations), float(threshold), valid, counts, sizes)
     return (valid.view(torch.bool), counts, sizes) if return_counts else valid.view(torch.bool)
 
 

@@ -222,16 +222,10 @@ class ResNet50(nn.Module):
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < need or ws.device != w.device:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            fl = _lib.ptr(flag) if flag is not None else None
-            if square:
-                _lib.check(_lib.lib().sq_resnet50_extract_checked(self.compute_dtype, _lib.ptr(w), _lib.ptr(b), _lib.ptr(patches_u8),
-                                                                  _lib.ptr(x_f32), n, H, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
-                                                                  fl, _lib.stream_ptr(w.device)))
-            else:
-                _lib.check(_lib.lib().sq_resnet50_extract_hw(self.compute_dtype, _lib.ptr(w), _lib.ptr(b), _lib.ptr(patches_u8),
-                                                             _lib.ptr(x_f32), n, H, W, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
-                                                             fl, _lib.stream_ptr(w.device)))
+        if square:
+            _lib.call("sq_resnet50_extract_checked", w.device, self.compute_dtype, w, b, patches_u8, x_f32, n, H, feats, ws, ws.numel(), flag)
+        else:
+            _lib.call("sq_resnet50_extract_hw", w.device, self.compute_dtype, w, b, patches_u8, x_f32, n, H, W, feats, ws, ws.numel(), flag)
         return feats
 
     @torch.no_grad()

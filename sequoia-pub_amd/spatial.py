@@ -149,10 +149,8 @@ def _slide_prologue(xtf, ytf, tile_features, stride, dev, G, shard):
 def _window_vote(win_vec, lists, stride, out):
     """sq_window_vote: out[t] = the vectors win_vec[lists[t, :]] (int32, -1 = none) of tile t's windows combined by the rule of
     visualize.py:87-100 -- stride 10: the last writer; stride < 10: the mean in visiting order; no window: NaN."""
-    dev = win_vec.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().sq_window_vote(_lib.ptr(win_vec), win_vec.shape[0], win_vec.shape[1], _lib.ptr(lists), lists.shape[0],
-                                             lists.shape[1], 1 if stride == WINDOW else 0, float("nan"), _lib.ptr(out), _lib.stream_ptr(dev)))
+    _lib.call("sq_window_vote", win_vec.device, win_vec, win_vec.shape[0], win_vec.shape[1], lists, lists.shape[0], lists.shape[1],
+              1 if stride == WINDOW else 0, float("nan"), out)
 
 
 @torch.no_grad()

@@ -56,26 +56,21 @@ def vis_backward(model, grad_out, batch, need_x_grad, bucket_events=None):
     bucket_events: torch.cuda.Event per grad_buckets() entry, recorded mid-pass as each bucket becomes final."""
     dev = model.flat.device
     grad_out = grad_out.to(dev, torch.float32).contiguous()
-    need = getattr(_lib.lib(), model._C_BWS)(ctypes.byref(model.cfg), model.compute_dtype, batch)
-    if need == 0:                # a shape the backward pass refuses (sq_last_error says why): nothing has been launched
-        _lib.check(-1)
+    need = _lib.need(getattr(_lib.lib(), model._C_BWS), ctypes.byref(model.cfg), model.compute_dtype, batch)    # raises before any launch
     if model._bws is None or model._bws.numel() < need or model._bws.device != dev:
         model._bws = torch.empty(need, dtype=torch.uint8, device=dev)
     gflat = _flat_grad(model)
     gx = torch.empty(batch, model.cfg.num_clusters, model._dim(), device=dev) if need_x_grad else None
     ws = model._ws
-    with torch.cuda.device(dev):
-        args = (ctypes.byref(model.cfg), model.compute_dtype, _lib.ptr(model.flat), _lib.ptr(model._params_lp()),
-                _lib.ptr(grad_out), _lib.ptr(gflat), _lib.ptr(gx), batch, _lib.ptr(ws), ws.numel(),
-                _lib.ptr(model._bws), model._bws.numel(), _lib.stream_ptr(dev))
-        if bucket_events is not None and model.has_grad_buckets:
-            handles = (ctypes.c_void_p * len(bucket_events))(*[e.cuda_event for e in bucket_events])
-            _lib.check(_lib.lib().sq_vis_backward_buckets(*args, handles, len(bucket_events)))
-        else:
-            _lib.check(getattr(_lib.lib(), model._C_BWD)(*args))
-            if bucket_events is not None:
-                for e in bucket_events:
-                    e.record(torch.cuda.current_stream(dev))
+    args = (ctypes.byref(model.cfg), model.compute_dtype, model.flat, model._params_lp(), grad_out, gflat, gx, batch, ws, ws.numel())
+    if bucket_events is not None and model.has_grad_buckets:
+        handles = (ctypes.c_void_p * len(bucket_events))(*[e.cuda_event for e in bucket_events])
+        _lib.call("sq_vis_backward_buckets", dev, *args, workspace=model._bws, after=(handles, len(bucket_events)))
+    else:
+        _lib.call(model._C_BWD, dev, *args, workspace=model._bws)
+        if bucket_events is not None:
+            for e in bucket_events:
+                e.record(torch.cuda.current_stream(dev))
     return gflat, gx
 
 
@@ -106,8 +101,7 @@ def mse_loss_grad(model, pred, target, grad_scale=None, want_grad=True):
     grad = torch.empty_like(pred) if want_grad else None
     loss = torch.empty(1, dtype=torch.float32, device=pred.device)
     scale = (2.0 / n) if grad_scale is None else grad_scale
-    _lib.check(_lib.lib().sq_mse_loss_grad(_lib.ptr(pred), _lib.ptr(target), n, scale, _lib.ptr(grad), _lib.ptr(loss),
-                                           _lib.ptr(_scratch(model)), _lib.stream_ptr(pred.device)))
+    _lib.call("sq_mse_loss_grad", pred.device, pred, target, n, scale, grad, loss, _scratch(model))
     return loss, grad
 
 
@@ -118,8 +112,7 @@ def batch_metrics(model, pred, target):
         raise ValueError(f"batch_metrics wants [B, G] predictions, got {tuple(pred.shape)}")
     out = torch.empty(3, dtype=torch.float32, device=pred.device)
     B, G = pred.shape
-    _lib.check(_lib.lib().sq_batch_metrics(_lib.ptr(pred), _lib.ptr(target), B, G, _lib.ptr(out),
-                                           _lib.ptr(_scratch(model)), _lib.stream_ptr(pred.device)))
+    _lib.call("sq_batch_metrics", pred.device, pred, target, B, G, out, _scratch(model))
     return out
 
 
@@ -232,18 +225,16 @@ class FusedTrainStep:
                         if self._wire is None:
                             dist.all_reduce(gflat[lo:hi], op=dist.ReduceOp.SUM)
                         else:                 # bf16 on the wire: pack -> sum over ranks in bf16 -> unpack into the fp32 gradient
-                            cs = _lib.stream_ptr(dev)                   # inside the block: the communication stream
-                            _lib.check(_lib.lib().sq_cast_f32_to_bf16(_lib.ptr(gflat[lo:hi]), _lib.ptr(self._wire[lo:hi]), hi - lo, cs))
+                            _lib.call("sq_cast_f32_to_bf16", dev, gflat[lo:hi], self._wire[lo:hi], hi - lo)     # on the communication stream
                             dist.all_reduce(self._wire[lo:hi], op=dist.ReduceOp.SUM)
-                            _lib.check(_lib.lib().sq_cast_bf16_to_f32(_lib.ptr(self._wire[lo:hi]), _lib.ptr(gflat[lo:hi]), hi - lo, cs))
+                            _lib.call("sq_cast_bf16_to_f32", dev, self._wire[lo:hi], gflat[lo:hi], hi - lo)
                 if not self.adamw_buckets:
                     continue
                 # the bucket's AdamW update (element-wise: identical to one pass over the flat buffer) behind its exchange
                 with torch.cuda.stream(self.comm_stream), torch.no_grad():
-                    _lib.check(_lib.lib().sq_adamw_step(_lib.ptr(m.flat[lo:hi]), _lib.ptr(gflat[lo:hi]), _lib.ptr(self.exp_avg[lo:hi]),
-                                                        _lib.ptr(self.exp_avg_sq[lo:hi]), _lib.ptr(lp[lo:hi]) if lp is not None else None,
-                                                        hi - lo, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0,
-                                                        _lib.stream_ptr(dev)))
+                    _lib.call("sq_adamw_step", dev, m.flat[lo:hi], gflat[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                              lp[lo:hi] if lp is not None else None, hi - lo, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                              self.step_count, 1.0)
             if not empty and sample:
                 tc1.record(self.comm_stream)
                 self._tm["pending"] = (tb0, tb1, tc0, tc1)
@@ -253,10 +244,8 @@ class FusedTrainStep:
         self.step_count += 1
         lp = m._params_lp()
         with torch.no_grad():
-            _lib.check(_lib.lib().sq_adamw_step(_lib.ptr(m.flat), _lib.ptr(gflat), _lib.ptr(self.exp_avg),
-                                                _lib.ptr(self.exp_avg_sq), _lib.ptr(lp), m.flat.numel(), self.lr,
-                                                self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0,
-                                                _lib.stream_ptr(dev)))
+            _lib.call("sq_adamw_step", dev, m.flat, gflat, self.exp_avg, self.exp_avg_sq, lp, m.flat.numel(), self.lr,
+                      self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0)
         # the kernel refreshed the bf16 shadow in the same pass (flat._version is unchanged by C-side writes)
         return None if empty else (loss, pred, mets)
 

@@ -199,10 +199,8 @@ class UniViT(nn.Module, FlatParams):
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < need or ws.device != dev:
             ws = self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sq_uni_forward_checked(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(wx),
-                                                         _lib.ptr(bx), _lib.ptr(patches_u8), _lib.ptr(x_f32), n, _lib.ptr(out), _lib.ptr(ws),
-                                                         ws.numel(), _lib.ptr(flag) if flag is not None else None, _lib.stream_ptr(dev)))
+        _lib.call("sq_uni_forward_checked", dev, ctypes.byref(self.cfg), self.compute_dtype, self.flat, wx, bx, patches_u8, x_f32, n, out,
+                  ws, ws.numel(), flag)
         return out
 
     @torch.no_grad()

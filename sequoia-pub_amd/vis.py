@@ -226,16 +226,13 @@ class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
             self._lp = torch.empty(self.flat.numel(), dtype=torch.bfloat16, device=self.flat.device)
             self._lp_version = -1
         if self._lp_version != self.flat._version:
-            _lib.check(_lib.lib().sq_cast_f32_to_bf16(_lib.ptr(self.flat), _lib.ptr(self._lp), self.flat.numel(),
-                                                      _lib.stream_ptr(self.flat.device)))
+            _lib.call("sq_cast_f32_to_bf16", self.flat.device, self.flat, self._lp, self.flat.numel())
             self._lp_version = self.flat._version
         return self._lp
 
     def _workspace(self, batch, save, slot=0):
         key = (batch, bool(save), self.compute_dtype, self.flat.device)
-        need = getattr(_lib.lib(), self._C_WS)(ctypes.byref(self.cfg), self.compute_dtype, batch, int(save))
-        if need == 0:
-            _lib.check(-1)
+        need = _lib.need(getattr(_lib.lib(), self._C_WS), ctypes.byref(self.cfg), self.compute_dtype, batch, int(save))
         if slot:                     # extra inference workspaces: forwards in flight on several streams
             ws, k = self._ws_extra.get(slot, (None, None))
             if ws is None or k != key or ws.numel() < need:
@@ -259,10 +256,7 @@ class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
         out = torch.empty(B, self.cfg.num_outputs, dtype=torch.float32, device=x.device)
         ws = self._workspace(B, save, slot)
         lp = self._params_lp()
-        with torch.cuda.device(x.device):
-            _lib.check(getattr(_lib.lib(), self._C_FWD)(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat),
-                                                         _lib.ptr(lp), _lib.ptr(x), _lib.ptr(out), B, int(save),
-                                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+        _lib.call(self._C_FWD, x.device, ctypes.byref(self.cfg), self.compute_dtype, self.flat, lp, x, out, B, int(save), workspace=ws)
         self._saved_x = x if save else None
         if slot == 0:           # slot-0 workspace rewritten (or re-allocated): earlier saved activations are gone
             self._saved_gen += 1
@@ -279,20 +273,17 @@ class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
         lay, dev = self.layout, cache.device
         D, HD, N = self._dim(), self.cfg.nheads * 64, self.cfg.num_clusters
         lp = self._params_lp()
-        L0 = lay.layer[0]
-        w_ptr = ctypes.c_void_p(lp.data_ptr() + 2 * L0.f_w)
+        L0, flat = lay.layer[0], self.flat.detach()
+        w = lp[L0.f_w:]
         a = cache.to(torch.bfloat16).contiguous()
-        pos = self.flat.detach()[lay.pos:lay.pos + N * D].view(N, D).to(torch.bfloat16).contiguous()
+        pos = flat[lay.pos:lay.pos + N * D].view(N, D).to(torch.bfloat16).contiguous()
         f_tile = torch.empty(a.shape[0], HD, dtype=torch.float32, device=dev)
         f_pos = torch.empty(N, HD, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            for r0 in range(0, a.shape[0], 32768):         # operand extents stay below the 2 GiB buffer-descriptor limit
-                r1 = min(a.shape[0], r0 + 32768)
-                _lib.check(_lib.lib().sq_linear(self.compute_dtype, _lib.ptr(a[r0:r1]), D, w_ptr, D, None, None, 0, 0, 0,
-                                                _lib.ptr(f_tile[r0:r1]), _lib.SQ_F32, HD, r1 - r0, HD, D, None, 0, _lib.stream_ptr(dev)))
-            b_ptr = ctypes.c_void_p(self.flat.data_ptr() + 4 * L0.f_b)
-            _lib.check(_lib.lib().sq_linear(self.compute_dtype, _lib.ptr(pos), D, w_ptr, D, b_ptr, None, 0, 0, 0,
-                                            _lib.ptr(f_pos), _lib.SQ_F32, HD, N, HD, D, None, 0, _lib.stream_ptr(dev)))
+        for r0 in range(0, a.shape[0], 32768):         # operand extents stay below the 2 GiB buffer-descriptor limit
+            r1 = min(a.shape[0], r0 + 32768)
+            _lib.call("sq_linear", dev, self.compute_dtype, a[r0:r1], D, w, D, None, None, 0, 0, 0,
+                      f_tile[r0:r1], _lib.SQ_F32, HD, r1 - r0, HD, D, None, 0)
+        _lib.call("sq_linear", dev, self.compute_dtype, pos, D, w, D, flat[L0.f_b:], None, 0, 0, 0, f_pos, _lib.SQ_F32, HD, N, HD, D, None, 0)
         return f_tile, f_pos
 
     def _run_head_inputs(self, cache, members, slot=0, tile_proj=None):
@@ -313,18 +304,15 @@ class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
         out = torch.empty(B, D, dtype=torch.float32, device=cache.device)
         ws = self._workspace(B, False, slot)
         lp = self._params_lp()
-        with torch.cuda.device(cache.device):
-            if tile_proj is not None:
-                f_tile, f_pos = tile_proj
-                if f_tile.shape != (cache.shape[0], self.cfg.nheads * 64) or f_pos.shape != (N, self.cfg.nheads * 64):
-                    raise ValueError("tile_proj does not belong to this cache / model")
-                _lib.check(_lib.lib().sq_vis_forward_tiles(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(lp),
-                                                           _lib.ptr(cache), _lib.ptr(members), cache.shape[0], _lib.ptr(f_tile), _lib.ptr(f_pos),
-                                                           _lib.ptr(out), B, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
-            else:
-                _lib.check(getattr(_lib.lib(), self._C_FWD_EX)(ctypes.byref(self.cfg), self.compute_dtype, _lib.ptr(self.flat), _lib.ptr(lp), None,
-                                                                _lib.ptr(cache), _lib.ptr(members), cache.shape[0], None, _lib.ptr(out), B, 0,
-                                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(cache.device)))
+        if tile_proj is not None:
+            f_tile, f_pos = tile_proj
+            if f_tile.shape != (cache.shape[0], self.cfg.nheads * 64) or f_pos.shape != (N, self.cfg.nheads * 64):
+                raise ValueError("tile_proj does not belong to this cache / model")
+            _lib.call("sq_vis_forward_tiles", cache.device, ctypes.byref(self.cfg), self.compute_dtype, self.flat, lp, cache, members,
+                      cache.shape[0], f_tile, f_pos, out, B, workspace=ws)
+        else:
+            _lib.call(self._C_FWD_EX, cache.device, ctypes.byref(self.cfg), self.compute_dtype, self.flat, lp, None, cache, members,
+                      cache.shape[0], None, out, B, 0, workspace=ws)
         return out
 
     def apply_head(self, head_in, chunk=32768):
@@ -334,21 +322,17 @@ class ViS(nn.Module, FlatParams, PyTorchModelHubMixin):
             raise ValueError("apply_head: chunk must be in 1..32768 (operand extents stay below the 2 GiB buffer-descriptor limit)")
         R, D = head_in.shape
         G = self.cfg.num_outputs
-        lay, dev = self.layout, head_in.device
+        lay, dev, flat = self.layout, head_in.device, self.flat.detach()
         lp = self._params_lp()
         out = torch.empty(R, G, dtype=torch.float32, device=dev)
         if lp is not None:
-            a = head_in.to(torch.bfloat16).contiguous()
-            w_ptr = ctypes.c_void_p(lp.data_ptr() + 2 * lay.head_w)
+            a, w = head_in.to(torch.bfloat16).contiguous(), lp[lay.head_w:]
         else:
-            a = head_in.contiguous()
-            w_ptr = ctypes.c_void_p(self.flat.data_ptr() + 4 * lay.head_w)
-        b_ptr = ctypes.c_void_p(self.flat.data_ptr() + 4 * lay.head_b)
-        with torch.cuda.device(dev):
-            for r0 in range(0, R, chunk):
-                r1 = min(R, r0 + chunk)
-                _lib.check(_lib.lib().sq_linear(self.compute_dtype, _lib.ptr(a[r0:r1]), D, w_ptr, D, b_ptr, None, 0, 0, 0,
-                                                _lib.ptr(out[r0:r1]), _lib.SQ_F32, G, r1 - r0, G, D, None, 0, _lib.stream_ptr(dev)))
+            a, w = head_in.contiguous(), flat[lay.head_w:]
+        for r0 in range(0, R, chunk):
+            r1 = min(R, r0 + chunk)
+            _lib.call("sq_linear", dev, self.compute_dtype, a[r0:r1], D, w, D, flat[lay.head_b:], None, 0, 0, 0,
+                      out[r0:r1], _lib.SQ_F32, G, r1 - r0, G, D, None, 0)
         return out
 
     def _run_backward(self, grad_out, batch, need_x_grad):

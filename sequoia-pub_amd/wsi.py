@@ -510,26 +510,16 @@ class TiffSlide:
         self._read_scans(lv, level, tiles, order, table, host[head:total])
         self.last_batch_tiles += [(t % lv.tiles_x, t // lv.tiles_x) for t in tiles]
         blob = self._pinned[:total].to(dev, non_blocking=True)
-        base = blob.data_ptr()
         o_sets = len(parts[0])
         o_slots = o_sets + len(parts[1])
         o_regions = o_slots + len(parts[2])
         geom = (lv.tile_w, lv.tile_h, lv.hs, lv.vs)
-        need = L.sq_jpeg_workspace_bytes(n, len(sets), *geom)
-        plane_bytes = L.sq_jpeg_planes_bytes(n, *geom)
-        if need == 0 or plane_bytes == 0:
-            raise _lib.SequoiaHipError(f"libsequoia_hip: {L.sq_last_error().decode()}")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        planes = torch.empty(plane_bytes, dtype=torch.uint8, device=dev)
+        need = _lib.need(L.sq_jpeg_workspace_bytes, n, len(sets), *geom)
+        planes = torch.empty(_lib.need(L.sq_jpeg_planes_bytes, n, *geom), dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        import ctypes
-        with torch.cuda.device(dev):
-            stream = _lib.stream_ptr(dev)
-            _lib.check(L.sq_jpeg_decode_tiles(ctypes.c_void_p(base + head), scans_bytes, ctypes.c_void_p(base), n, ctypes.c_void_p(base + o_sets),
-                                              len(sets), *geom, _lib.ptr(planes), _lib.ptr(status), _lib.ptr(ws), need, stream))
-            _lib.check(L.sq_jpeg_compose_regions(_lib.ptr(planes), n, *geom, lv.transform, ctypes.c_void_p(base + o_slots), lv.tiles_x,
-                                                 lv.tiles_y, lv.width, lv.height, ctypes.c_void_p(base + o_regions), k, h, w, _lib.ptr(out),
-                                                 stream))
+        _lib.call("sq_jpeg_decode_tiles", dev, blob[head:], scans_bytes, blob, n, blob[o_sets:], len(sets), *geom, planes, status, workspace=need)
+        _lib.call("sq_jpeg_compose_regions", dev, planes, n, *geom, lv.transform, blob[o_slots:], lv.tiles_x, lv.tiles_y, lv.width, lv.height,
+                  blob[o_regions:], k, h, w, out)
         st = status.cpu().numpy()            # waits for the chunk: the pinned buffer may be written again
         return [(level, tiles[order[s]] % lv.tiles_x, tiles[order[s]] // lv.tiles_x, int(st[s])) for s in np.flatnonzero(st)]
 
