@@ -1206,6 +1206,26 @@ int sq_j2k_decode_tiles(const uint8_t* streams, size_t streams_bytes, const int3
                         int n_param_sets, int tile_w, int tile_h, int max_blocks, int max_nodes, int max_bands, uint8_t* planes,
                         int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-resident cohort feed: one training or inference batch gathered from tables that stay on the device.
+ * It replaces, per batch, what the loader path does on the host: one store open and read per slide
+ * (/root/reference/src/read_data.py:38-56), the collate that stacks the readable items (/root/reference/src/utils.py:10-18)
+ * and the pinned copy and upload of the loaders of every fold (/root/reference/src/main.py:112-135).  The tables are loaded
+ * and uploaded once (sequoia-pub_amd/data.py: CohortTable); ResidentLoader makes the index of every batch.
+ *   sq_cohort_gather : x_table f32 [n_slides, row_x] (row_x = tokens * D) and y_table f32 [n_slides, row_y] (row_y = G) ->
+ *                      x_out f32 [m, row_x] and y_out f32 [m, row_y], row j of both = row index[j] of the tables, in ONE launch.
+ *                      index: int32 [m] in device memory, or null for the identity with m = n_slides.  An index outside
+ *                      [0, n_slides) gives all-zero rows (it is compared before it addresses anything).  m = 0 launches
+ *                      nothing.  y_table and y_out may both be null: a features-only gather (row_y is then ignored).
+ *                      A table whose rows and output rows all start 16-byte aligned (both base pointers on 16 bytes and the
+ *                      row a multiple of 4 floats -- decided per call and per table) moves as 16-byte loads and stores per
+ *                      lane and then has no tail; any other table moves by the dword.  Every offset is 64-bit; the grid is
+ *                      capped at 2048 blocks and strides over the rest.  Asynchronous on `stream`; arguments are checked
+ *                      before the launch; no workspace, no atomics, no LDS.
+ * ---------------------------------------------------------------------------------------------------------- */
+int sq_cohort_gather(const float* x_table, const float* y_table, int n_slides, long long row_x, long long row_y, const int32_t* index,
+                     int m, float* x_out, float* y_out, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

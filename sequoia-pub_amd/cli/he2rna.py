@@ -15,7 +15,7 @@ import pandas as pd
 import torch
 from torch.utils.data import DataLoader
 
-from ..data import SuperTileRNADataset, custom_collate_fn, filter_no_features, patient_kfold
+from ..data import CohortTable, ResidentLoader, SuperTileRNADataset, custom_collate_fn, filter_no_features, patient_kfold
 from .common import seed_everything
 
 LAYERS, KS = [256, 256], [1, 2, 5, 10, 20, 50, 100]
@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument('--patience', type=int, default=100, help='epochs without a better validation score before a fold stops')
     p.add_argument('--engine', choices=['fused', 'autograd'], default='fused', help='training step: fused C passes or the torch optimiser loop')
     p.add_argument('--dropout', type=float, default=0.5, help='dropout behind every hidden layer')
+    p.add_argument('--feed', default='loader', choices=['loader', 'resident'],
+                   help="'loader': a DataLoader opens every slide's store every epoch (the reference's feed); 'resident': the cohort is read "
+                        "once, kept on the device and every batch is one gather there (same batches, same order, same RNG draws)")
     return p
 
 
@@ -65,14 +68,20 @@ def main(argv=None):
     df = filter_no_features(df, args.feature_path, 'cluster_features')
 
     device = "cuda:0"
+    table = CohortTable(df, args.feature_path).to(device) if args.feed == 'resident' else None       # one table for every fold and role
     results = {}
     train_idxs, val_idxs, test_idxs = patient_kfold(df, n_splits=args.k)
     for i, (train_idx, val_idx, test_idx) in enumerate(zip(train_idxs, val_idxs, test_idxs)):
-        train_set, val_set, test_set = (SuperTileRNADataset(df.iloc[idx], args.feature_path) for idx in (train_idx, val_idx, test_idx))
-        # the dataset reads small per-slide files; worker processes would each need the library's device context
-        train_loader, valid_loader, test_loader = (
-            DataLoader(ds, batch_size=args.batch_size, shuffle=shuffle, num_workers=0, collate_fn=custom_collate_fn)
-            for ds, shuffle in ((train_set, True), (val_set, False), (test_set, False)))
+        if table is not None:
+            train_set = table                                  # feature_dim and num_genes are the cohort's
+            train_loader, valid_loader, test_loader = (ResidentLoader(table, idx, args.batch_size, shuffle=shuffle)
+                                                       for idx, shuffle in ((train_idx, True), (val_idx, False), (test_idx, False)))
+        else:
+            train_set, val_set, test_set = (SuperTileRNADataset(df.iloc[idx], args.feature_path) for idx in (train_idx, val_idx, test_idx))
+            # the dataset reads small per-slide files; worker processes would each need the library's device context
+            train_loader, valid_loader, test_loader = (
+                DataLoader(ds, batch_size=args.batch_size, shuffle=shuffle, num_workers=0, collate_fn=custom_collate_fn)
+                for ds, shuffle in ((train_set, True), (val_set, False), (test_set, False)))
         model = HE2RNA(input_dim=train_set.feature_dim, layers=LAYERS, ks=KS, dropout=args.dropout, device=device,
                        output_dim=args.num_genes if args.change_num_genes else train_set.num_genes)
         if args.checkpoint:

@@ -12,7 +12,7 @@ import torch
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
-from ..data import SuperTileRNADataset, custom_collate_fn, filter_no_features, patient_kfold
+from ..data import CohortTable, ResidentLoader, RowIndex, SuperTileRNADataset, custom_collate_fn, filter_no_features, patient_kfold
 from ..train import evaluate, train
 from ..vis import ViS
 from .common import init_distributed, seed_everything
@@ -58,6 +58,9 @@ def main(argv=None):
     p.add_argument('--compute_dtype', default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--grad_exchange', default='fp32', choices=['fp32', 'bf16'],
                    help='wire format of the gradient all-reduce under torchrun (bf16: half the bytes, gradients rounded to bf16 on the wire)')
+    p.add_argument('--feed', default='loader', choices=['loader', 'resident'],
+                   help="'loader': a DataLoader opens every slide's store every epoch (the reference's feed); 'resident': the cohort is read "
+                        "once, kept on the device and every batch is one gather there (same batches, same order, same RNG draws)")
     args = p.parse_args(argv)
 
     seed_everything(args.seed)
@@ -83,6 +86,8 @@ def main(argv=None):
     if args.filter_no_features:
         df = filter_no_features(df, feature_path=args.feature_path, feature_name='cluster_features')
 
+    # one table for every fold and role: the folds' datasets are row subsets of it
+    table = CohortTable(df, args.feature_path).to(device) if args.feed == 'resident' else None
     train_idxs, val_idxs, test_idxs = patient_kfold(df, n_splits=args.k)
     test_results_splits = {}
     for i, (train_idx, val_idx, test_idx) in enumerate(zip(train_idxs, val_idxs, test_idxs)):
@@ -91,17 +96,24 @@ def main(argv=None):
             np.save(save_dir + '/train_' + str(i) + '.npy', np.unique(train_df.patient_id))
             np.save(save_dir + '/val_' + str(i) + '.npy', np.unique(val_df.patient_id))
             np.save(save_dir + '/test_' + str(i) + '.npy', np.unique(test_df.patient_id))
-        train_dataset = SuperTileRNADataset(train_df, args.feature_path)
-        val_dataset = SuperTileRNADataset(val_df, args.feature_path)
-        test_dataset = SuperTileRNADataset(test_df, args.feature_path)
-        num_outputs, feature_dim = train_dataset.num_genes, train_dataset.feature_dim
-        sampler = DistributedSampler(train_dataset, world, rank, shuffle=True, seed=0) if world > 1 else None
-        train_dataloader = DataLoader(train_dataset, num_workers=0, pin_memory=True, shuffle=sampler is None, sampler=sampler,
-                                      batch_size=args.batch_size, collate_fn=custom_collate_fn, generator=g)
-        val_dataloader = DataLoader(val_dataset, num_workers=0, pin_memory=True, shuffle=True, batch_size=args.batch_size,
-                                    collate_fn=custom_collate_fn)
-        test_dataloader = DataLoader(test_dataset, num_workers=0, pin_memory=True, shuffle=False, batch_size=args.batch_size,
-                                     collate_fn=custom_collate_fn)
+        if table is not None:
+            num_outputs, feature_dim = table.num_genes, table.feature_dim
+            sampler = DistributedSampler(RowIndex(len(train_idx)), world, rank, shuffle=True, seed=0) if world > 1 else None
+            train_dataloader = ResidentLoader(table, train_idx, args.batch_size, shuffle=sampler is None, sampler=sampler, generator=g)
+            val_dataloader = ResidentLoader(table, val_idx, args.batch_size, shuffle=True)
+            test_dataloader = ResidentLoader(table, test_idx, args.batch_size, shuffle=False)
+        else:
+            train_dataset = SuperTileRNADataset(train_df, args.feature_path)
+            val_dataset = SuperTileRNADataset(val_df, args.feature_path)
+            test_dataset = SuperTileRNADataset(test_df, args.feature_path)
+            num_outputs, feature_dim = train_dataset.num_genes, train_dataset.feature_dim
+            sampler = DistributedSampler(train_dataset, world, rank, shuffle=True, seed=0) if world > 1 else None
+            train_dataloader = DataLoader(train_dataset, num_workers=0, pin_memory=True, shuffle=sampler is None, sampler=sampler,
+                                          batch_size=args.batch_size, collate_fn=custom_collate_fn, generator=g)
+            val_dataloader = DataLoader(val_dataset, num_workers=0, pin_memory=True, shuffle=True, batch_size=args.batch_size,
+                                        collate_fn=custom_collate_fn)
+            test_dataloader = DataLoader(test_dataset, num_workers=0, pin_memory=True, shuffle=False, batch_size=args.batch_size,
+                                         collate_fn=custom_collate_fn)
 
         if args.checkpoint and args.change_num_genes:                        # fine-tune from another gene set (:138-157)
             model = build_model(args, args.change_num_genes, feature_dim, device)

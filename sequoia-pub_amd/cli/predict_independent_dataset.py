@@ -12,7 +12,7 @@ import pandas as pd
 import torch
 from torch.utils.data import DataLoader
 
-from ..data import SuperTileRNADataset, custom_collate_fn, filter_no_features, shard_rows
+from ..data import CohortTable, ResidentLoader, SuperTileRNADataset, custom_collate_fn, filter_no_features, shard_rows
 from ..train import predict
 from ..vis import ViS
 from .common import init_distributed, seed_everything
@@ -33,6 +33,9 @@ def main(argv=None):
     p.add_argument('--exp_name', type=str, default='exp')
     p.add_argument('--model_dir', type=str, default=None)
     p.add_argument('--compute_dtype', default='fp32', choices=['fp32', 'bf16'])
+    p.add_argument('--feed', default='loader', choices=['loader', 'resident'],
+                   help="'loader': a DataLoader opens every slide's store every epoch (the reference's feed); 'resident': the cohort is read "
+                        "once, kept on the device and every batch is one gather there (same batches, same order, same RNG draws)")
     args = p.parse_args(argv)
     seed_everything(args.seed)
     rank, world, device = init_distributed()
@@ -45,9 +48,13 @@ def main(argv=None):
     if 'tcga_project' in df.columns and args.tcga_project:
         df = df[df['tcga_project'].isin([args.tcga_project])].reset_index(drop=True)
     lo, hi = shard_rows(df.shape[0], rank, world)
-    test_dataset = SuperTileRNADataset(df.iloc[lo:hi].reset_index(drop=True), args.feature_path, args.feature_use)
-    loader = DataLoader(test_dataset, num_workers=0, pin_memory=True, shuffle=False, batch_size=args.batch_size,
-                        collate_fn=custom_collate_fn)
+    if args.feed == 'resident':                                # this rank's slides, read once for every fold's two passes
+        test_dataset = CohortTable(df.iloc[lo:hi].reset_index(drop=True), args.feature_path, args.feature_use).to(device)
+        loader = ResidentLoader(test_dataset, np.arange(len(test_dataset)), args.batch_size, shuffle=False)
+    else:
+        test_dataset = SuperTileRNADataset(df.iloc[lo:hi].reset_index(drop=True), args.feature_path, args.feature_use)
+        loader = DataLoader(test_dataset, num_workers=0, pin_memory=True, shuffle=False, batch_size=args.batch_size,
+                            collate_fn=custom_collate_fn)
     cancer = args.tcga_project.split('-')[-1].lower()
     res_preds, res_random = [], []
     for fold in range(args.folds):

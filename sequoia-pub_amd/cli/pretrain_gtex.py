@@ -11,7 +11,7 @@ import pandas as pd
 import torch
 from torch.utils.data import DataLoader
 
-from ..data import SuperTileRNADataset, custom_collate_fn, filter_no_features
+from ..data import CohortTable, ResidentLoader, SuperTileRNADataset, custom_collate_fn, filter_no_features
 from ..train import train
 from ..vis import ViS
 from .common import seed_everything
@@ -32,6 +32,9 @@ def main(argv=None):
     p.add_argument('--checkpoint', type=str, default=None)
     p.add_argument('--quick', type=int, default=0, help='Whether to run a quick exp for debugging')
     p.add_argument('--compute_dtype', default='fp32', choices=['fp32', 'bf16'])
+    p.add_argument('--feed', default='loader', choices=['loader', 'resident'],
+                   help="'loader': a DataLoader opens every slide's store every epoch (the reference's feed); 'resident': the cohort is read "
+                        "once, kept on the device and every batch is one gather there (same batches, same order, same RNG draws)")
     args = p.parse_args(argv)
 
     seed_everything(args.seed)
@@ -53,10 +56,14 @@ def main(argv=None):
     if args.quick:
         df = df.iloc[0:20, :]
         args.num_epochs = 5
-    dataset = SuperTileRNADataset(df, args.feature_path)
-    # the dataset reads small per-slide files; worker processes would each need the library's device context
-    dataloader = DataLoader(dataset, num_workers=0, pin_memory=True, shuffle=True, batch_size=args.batch_size,
-                            collate_fn=custom_collate_fn)
+    if args.feed == 'resident':
+        dataset = CohortTable(df, args.feature_path).to(device)
+        dataloader = ResidentLoader(dataset, np.arange(len(dataset)), args.batch_size, shuffle=True)
+    else:
+        dataset = SuperTileRNADataset(df, args.feature_path)
+        # the dataset reads small per-slide files; worker processes would each need the library's device context
+        dataloader = DataLoader(dataset, num_workers=0, pin_memory=True, shuffle=True, batch_size=args.batch_size,
+                                collate_fn=custom_collate_fn)
     if args.model == 'vis':
         model = ViS(num_outputs=dataset.num_genes, input_dim=dataset.feature_dim, depth=6, nheads=16, dimensions_f=64,
                     dimensions_c=64, dimensions_s=64, device=str(device), compute_dtype=args.compute_dtype)

@@ -4,7 +4,11 @@ Pure host logic (pandas / numpy / sklearn splitters); the tensors it yields feed
 
 Same inputs, outputs and file rules as the reference; organised around whole-frame passes: store paths, names and
 targets are materialised once per dataset, the feature filter scans each project directory once into a
-name -> usable map, and the k-fold split is a patient -> role table expanded to row indices."""
+name -> usable map, and the k-fold split is a patient -> role table expanded to row indices.
+
+The opt-in device-resident feed (``CohortTable``, ``ResidentLoader``; ``--feed resident`` of the training and inference CLIs) reads
+the cohort once, keeps it on the device and gathers every batch there (csrc/cohort.hip: ``sq_cohort_gather``): the same batches in
+the same order as the loader path, which stays the default."""
 import os
 
 import numpy as np
@@ -70,6 +74,188 @@ def custom_collate_fn(batch):
     if not usable:
         return [], [], [], []
     return torch.utils.data.dataloader.default_collate(usable)
+
+
+# ---------------------------------------------------------------------------------------------
+# device-resident feed: the cohort read once, batches gathered on the device (csrc/cohort.hip)
+# ---------------------------------------------------------------------------------------------
+def cohort_gather(x_table, index=None, y_table=None, x_out=None, y_out=None):
+    """Rows ``index`` of f32 CUDA tables ``x_table [S, ...]`` and ``y_table [S, ...]`` (None: features only) in one launch
+    (``sq_cohort_gather``): returns ``(x [m, ...], y [m, ...] or None)``.  ``index``: int32 [m] on the tables' device, None for all
+    rows in order; an index outside [0, S) gives zero rows.  ``x_out`` / ``y_out``: contiguous f32 tensors of those shapes to write
+    into.  Asynchronous on the current stream; no CPU fallback."""
+    from . import _lib
+    _lib.require_gpu()
+    tables = [t for t in (x_table, y_table) if t is not None]
+    for t in tables:
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == x_table.device):
+            raise _lib.SequoiaHipError("cohort_gather needs CUDA tensors on one device (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != x_table.shape[0]:
+            raise ValueError(f"cohort_gather: a table must be contiguous float32 [{x_table.shape[0]}, ...], got {t.dtype} {tuple(t.shape)}")
+    dev, S = x_table.device, x_table.shape[0]
+    if index is None:
+        m = S
+    elif not (torch.is_tensor(index) and index.device == dev):
+        raise _lib.SequoiaHipError("cohort_gather: index must be a tensor on the device of the tables")
+    elif index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous():
+        raise ValueError(f"cohort_gather: index must be contiguous int32 [m], got {index.dtype} {tuple(index.shape)}")
+    else:
+        m = index.shape[0]
+    outs = []
+    for t, out in ((x_table, x_out), (y_table, y_out)):
+        if t is not None and out is None:
+            out = torch.empty((m,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        elif t is None and out is not None:
+            raise ValueError("cohort_gather: y_out without a y_table")
+        elif t is not None and not (out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
+                                    and tuple(out.shape) == (m,) + tuple(t.shape[1:])):
+            raise ValueError(f"cohort_gather: an output must be contiguous float32 {(m,) + tuple(t.shape[1:])} on {dev}")
+        outs.append(out)
+    row_x, row_y = (0 if t is None else int(np.prod(t.shape[1:])) for t in (x_table, y_table))
+    _lib.call("sq_cohort_gather", dev, x_table, y_table, S, row_x, row_y, index, m, outs[0], outs[1])
+    return outs[0], outs[1]
+
+
+class CohortTable:
+    """A cohort's features and targets read ONCE: what ``SuperTileRNADataset`` over the same arguments returns item by item and
+    epoch by epoch, as two host arrays ``x [S, tokens, D]`` and ``y [S, G]`` f32 with ``valid [S]``, ``names`` and ``projects``.
+    A slide whose store cannot be read or lacks ``feature_use`` is invalid (its row of x stays zero; the exception and the path are
+    printed here, once -- the loader path prints them every epoch) and is dropped from every batch of the run, as
+    ``custom_collate_fn`` drops it.  A slide whose dataset has another shape than the first readable one is refused by name (the
+    loader path fails in default_collate on the first batch that mixes two shapes).  Stores are read one after another on this
+    thread (h5lite drives the system's HDF5 C library, which need not be thread-safe).
+
+    ``to(device)`` uploads both arrays through one pinned buffer; datasets (folds, roles) are row subsets of the one table:
+    ``ResidentLoader(table, rows, ...)``."""
+
+    STAGING_BYTES = 256 << 20
+
+    def __init__(self, csv_path, features_path, feature_use="cluster_features"):
+        self.features_path, self.feature_use = features_path, feature_use
+        data = pd.read_csv(csv_path) if isinstance(csv_path, str) else csv_path
+        self.rna_cols = [c for c in data.columns if 'rna_' in c]
+        self.num_genes = len(self.rna_cols)
+        self.y = np.ascontiguousarray(data[self.rna_cols].to_numpy(dtype=np.float32))
+        self.names = data['wsi_file_name'].to_numpy()
+        self.projects = data['tcga_project'].to_numpy()
+        self.paths = [slide_store_path(features_path, p, w) for p, w in zip(self.projects, self.names)]
+        self.valid = np.zeros(len(self.paths), dtype=bool)
+        self.x = None
+        for i, path in enumerate(self.paths):
+            try:
+                with store.File(path, 'r') as f:
+                    item = torch.tensor(np.asarray(f[feature_use][:]), dtype=torch.float32).numpy()      # SuperTileRNADataset._load
+            except Exception as e:
+                print(e)
+                print(path)
+                continue
+            if self.x is None:
+                if item.ndim != 2:
+                    raise ValueError(f"CohortTable: {feature_use} of slide {self.names[i]} has shape {item.shape}, expected [tokens, D]")
+                self.x = np.zeros((len(self.paths),) + item.shape, dtype=np.float32)
+            elif item.shape != self.x.shape[1:]:
+                raise ValueError(f"CohortTable: {feature_use} of slide {self.names[i]} has shape {item.shape}, the cohort's first "
+                                 f"readable slide has {self.x.shape[1:]}: one table holds one shape")
+            self.x[i] = item
+            self.valid[i] = True
+        if self.x is None:
+            raise ValueError(f"CohortTable: none of the {len(self.paths)} slides has a readable {feature_use}")
+        self.tokens, self.feature_dim = self.x.shape[1:]
+        self.x_dev = self.y_dev = None
+
+    def __len__(self):
+        return len(self.paths)
+
+    @property
+    def nbytes(self):
+        return self.x.nbytes + self.y.nbytes
+
+    def to(self, device, max_bytes=None):
+        """Upload x and y to ``device`` (kept as ``x_dev``, ``y_dev``) through one pinned buffer of at most STAGING_BYTES.  Tables
+        larger than ``max_bytes`` (default: half of the device's free memory now) are refused before anything is allocated."""
+        device = torch.device(device)
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(device)[0] // 2
+        if self.nbytes > max_bytes:
+            raise ValueError(f"CohortTable: the tables take {self.nbytes} bytes ({self.x.nbytes} of features, {self.y.nbytes} of targets), "
+                             f"more than max_bytes = {int(max_bytes)}: keep the loader feed for this cohort or raise max_bytes")
+        staging = torch.empty(max(1, min(self.STAGING_BYTES, max(self.x.nbytes, self.y.nbytes)) // 4), dtype=torch.float32).pin_memory()
+        placed = []
+        for host in (self.x, self.y):
+            src = torch.from_numpy(host).reshape(-1)
+            dst = torch.empty(src.numel(), dtype=torch.float32, device=device)
+            for lo in range(0, src.numel(), staging.numel()):
+                n = min(staging.numel(), src.numel() - lo)
+                staging[:n].copy_(src[lo:lo + n])
+                dst[lo:lo + n].copy_(staging[:n], non_blocking=True)
+                torch.cuda.synchronize(device)                 # the one buffer is refilled next
+            placed.append(dst.view(host.shape))
+        self.x_dev, self.y_dev = placed
+        return self
+
+    def gather(self, index):
+        """``(x [m, tokens, D], y [m, G])`` on the device: rows ``index`` (int32 [m] on the device) of the uploaded tables."""
+        if self.x_dev is None:
+            raise RuntimeError("CohortTable: call to(device) before gathering batches")
+        return cohort_gather(self.x_dev, index, self.y_dev)
+
+
+class RowIndex(Dataset):
+    """The index-only dataset of n rows: item i is i.  What a sampler of the resident feed is built over."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i
+
+
+class ResidentLoader:
+    """Batches of rows ``rows`` of an uploaded CohortTable, in the place of ``DataLoader(SuperTileRNADataset(frame.iloc[rows]),
+    batch_size, shuffle, sampler, generator, collate_fn=custom_collate_fn)``: the same batches in the same order, with the same
+    draws from ``generator`` and from the global torch RNG.  The order is not restated: it is what a DataLoader of the same
+    arguments over ``RowIndex(len(rows))`` yields.  ``sampler`` (a DistributedSampler) is built over ``RowIndex(len(rows))``.
+    Yields ``(x, y, names, projects)`` with x and y on the table's device; invalid rows are dropped, an all-invalid batch is
+    ``([], [], [], [])``."""
+
+    def __init__(self, table, rows, batch_size=1, shuffle=False, generator=None, sampler=None):
+        self.table = table
+        self.rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        self._order = torch.utils.data.DataLoader(RowIndex(len(self.rows)), batch_size=batch_size, shuffle=shuffle, sampler=sampler,
+                                                  generator=generator, num_workers=0, collate_fn=list)
+
+    @property
+    def sampler(self):
+        return self._order.sampler
+
+    @property
+    def batch_size(self):
+        return self._order.batch_size
+
+    def __len__(self):
+        return len(self._order)
+
+    def index_batches(self):
+        """The host half: per batch the list of positions in ``rows``, as the DataLoader hands them to a dataset."""
+        return iter(self._order)
+
+    def __iter__(self):
+        collate = torch.utils.data.dataloader.default_collate
+        table = self.table
+        if table.x_dev is None:
+            raise RuntimeError("ResidentLoader: the table is not on a device: call table.to(device) first")
+        for positions in self.index_batches():
+            rows = self.rows[positions]
+            rows = rows[table.valid[rows]]                     # custom_collate_fn: items whose features failed to load are dropped
+            if rows.size == 0:
+                yield [], [], [], []
+                continue
+            x, y = table.gather(torch.from_numpy(rows.astype(np.int32)).to(table.x_dev.device))
+            names, projects = collate([(table.names[i], table.projects[i]) for i in rows])       # the containers default_collate makes
+            yield [x, y, names, projects]
 
 
 def _has_dataset(path, name):

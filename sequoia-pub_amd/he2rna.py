@@ -386,6 +386,12 @@ def _batches(model, loader):
         yield x, y, wsi, proj
 
 
+def _host_labels(y):
+    """A batch's labels as a host array: the loader feed hands them over on the host, the resident feed (data.ResidentLoader) on
+    the device."""
+    return np.asarray(y.cpu() if torch.is_tensor(y) else y)
+
+
 def training_epoch(model, dataloader, optimizer):
     """he2rna.py:108-127."""
     model.train()
@@ -409,7 +415,7 @@ def evaluate(model, dataloader):
     with torch.no_grad():
         for x, y, _, _ in _batches(model, dataloader):
             pred = model(x)
-            labels.append(np.asarray(y))
+            labels.append(_host_labels(y))
             losses.append(float(loss_fn(pred, torch.as_tensor(y).float().to(model.device))))
             preds.append(torch.relu(pred).cpu().numpy())
     preds, labels = np.concatenate(preds), np.concatenate(labels)
@@ -425,7 +431,7 @@ def he2rna_predict(model, dataloader):
             preds.append(torch.relu(model(x)).cpu().numpy())
             wsis.append(wsi)
             projs.append(proj)
-            labels.append(np.asarray(y))
+            labels.append(_host_labels(y))
     return np.concatenate(preds, 0), np.concatenate(labels, 0), np.concatenate(wsis, 0), np.concatenate(projs, 0)
 
 
