@@ -1122,7 +1122,38 @@ int sq_dbg_kmeans_lloyd(const float* X, int n_slides, int n_samples, int dim, in
  *                          on a tile without a slot (or with a slot outside 0..n_slots-1), is (0, 0, 0, 0); every other has
  *                          alpha 255.  Four adjacent pixels per thread, one 16-byte store where w is a multiple of 4.
  * Entries check scalars and sizes before launching (SQ_ERR_ARG / SQ_ERR_WORKSPACE); they allocate nothing and do not wait.
+ *
+ * JPEG tiles, split entropy decode (opt-in): sq_jpeg_decode_tiles_split is sq_jpeg_decode_tiles with the entropy launch
+ * replaced by one that puts the 64 lanes of a wave on ONE tile's scan (one wave per tile, grid = n_tiles).  Contract: planes
+ * and statuses are those of sq_jpeg_decode_tiles, byte for byte, for every input whatever it contains; the same device
+ * inputs, outputs, argument checks and error codes; nothing is read outside the buffers.
+ *   method      a baseline Huffman scan is self-synchronising (Klein & Wiseman; Weissenberger & Schmidt): a decoder started at
+ *               a wrong bit falls into step after a few symbols.  The scan is cut into subsequences of sub_bytes raw bytes
+ *               counted from its first byte (stuffed FF 00 pairs count as two), taken 64 at a time; lane 0 of such a round
+ *               starts from the confirmed state (the scan's start, or the round before), every other lane at its
+ *               subsequence's first bit as if an MCU began there.  Each lane decodes the symbols whose first bit lies in its
+ *               subsequence and records where the next one starts (byte, bit, block within the MCU, zigzag index), the block
+ *               ends it passed and the sums of the DC differences.  Then lane i + 1 takes lane i's end as its start and
+ *               decodes again until a wave vote finds no start changed: lane 0 is exact, so lanes <= r are exact after round r
+ *               and the loop ends after at most 63 rounds; every symbol consumes a bit and every lane stops at its
+ *               subsequence's end, so it cannot run on.  Exclusive wave scans give each lane the scan-order number of its
+ *               first block and its three DC predictors (sums kept in 32 bits: truncation to int16 commutes with addition),
+ *               and a last pass from the exact states stores the non-zero coefficients.
+ *   fallback    anything irregular -- a state that stays invalid after synchronisation in front of the scan's last block, an
+ *               error in the storing pass, a block count other than the frame's, a scan that ends short, a round of 64
+ *               subsequences that ends where it began (a marker in a scan without restart interval) -- and the wave
+ *               zeroes the tile's coefficients again and lane 0 runs the serial scan of sq_jpeg_decode_tiles on the tile,
+ *               which gives the tile's exact status and exact partial coefficients.
+ *   restart     tiles with a restart interval > 0 take that serial scan on lane 0 directly (a marker stops the bit reader;
+ *               Aperio tiles carry none).
+ *   sub_bytes   a multiple of 4 in SQ_JPEG_SPLIT_SUB_MIN..SQ_JPEG_SPLIT_SUB_MAX, or 0 for SQ_JPEG_SPLIT_SUB_DEFAULT; anything
+ *               else is SQ_ERR_ARG, the message naming the value.  Scans of any length work with any sub_bytes.
+ *   sq_jpeg_split_workspace_bytes : workspace of sq_jpeg_decode_tiles_split (that of sq_jpeg_decode_tiles; lane states live
+ *               in registers).  Table derivation, the memset and the IDCT launch are those of sq_jpeg_decode_tiles.
  * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_JPEG_SPLIT_SUB_MIN 16
+#define SQ_JPEG_SPLIT_SUB_MAX 256
+#define SQ_JPEG_SPLIT_SUB_DEFAULT 128
 #define SQ_JPEG_MAX_TILE 1024
 #define SQ_JPEG_TILE_WORDS 8
 #define SQ_JPEG_TABLE_SET_BYTES 1600
@@ -1140,6 +1171,10 @@ size_t sq_jpeg_planes_bytes(int n_tiles, int tile_w, int tile_h, int hs, int vs)
 int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles, const uint8_t* table_sets,
                          int n_table_sets, int tile_w, int tile_h, int hs, int vs, uint8_t* planes, int32_t* status,
                          void* workspace, size_t workspace_bytes, sq_stream_t stream);
+size_t sq_jpeg_split_workspace_bytes(int n_tiles, int n_table_sets, int tile_w, int tile_h, int hs, int vs);
+int sq_jpeg_decode_tiles_split(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles,
+                               const uint8_t* table_sets, int n_table_sets, int tile_w, int tile_h, int hs, int vs, uint8_t* planes,
+                               int32_t* status, void* workspace, size_t workspace_bytes, int sub_bytes, sq_stream_t stream);
 int sq_jpeg_compose_regions(const uint8_t* planes, int n_slots, int tile_w, int tile_h, int hs, int vs, int transform,
                             const int32_t* tile_slot, int tiles_x, int tiles_y, int level_w, int level_h, const int32_t* regions,
                             int k, int h, int w, uint8_t* rgba, sq_stream_t stream);

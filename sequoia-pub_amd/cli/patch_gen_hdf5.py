@@ -24,12 +24,13 @@ def get_slide_id(slide_name):
 def process(opts):
     slide_path, patch_size, patches_output_dir, mask_path, slide_id, max_patches_per_slide = opts[:6]
     device, batch, slide_mask = opts[6:9] if len(opts) > 6 else (None, 256, "host")
-    slide = open_slide(slide_path, opts[9] if len(opts) > 9 else "openslide", device or "cuda:0")
+    slide = open_slide(slide_path, opts[9] if len(opts) > 9 else "openslide", device or "cuda:0",
+                       entropy=opts[10] if len(opts) > 10 else "serial")
     extract_patches(slide, mask_path, patch_size, patches_output_dir, slide_id, max_patches_per_slide,
                     device=device, batch=batch, slide_mask=slide_mask)
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description='Generate patches from a given folder of images')
     p.add_argument('--ref_file', default="examples/ref_file.csv", required=False, metavar='ref_file', type=str)
     p.add_argument('--wsi_path', default="examples/HE", metavar='WSI_PATH', type=str)
@@ -51,6 +52,13 @@ def main(argv=None):
     p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
                    help="what opens a slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without "
                         "openslide; the tiles are decoded on the GPU, so it needs --filter device)")
+    p.add_argument('--jpeg_entropy', default='serial', choices=['serial', 'split'],
+                   help="JPEG tiles of --reader tiff: serial = one lane per tile (sq_jpeg_decode_tiles); split = the 64 lanes of a wave on one tile's scan (sq_jpeg_decode_tiles_split), the same bytes; JPEG 2000 levels and the openslide reader ignore it")
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     args = p.parse_args(argv)
     if args.slide_mask == 'device' and args.filter != 'device':
         p.error("--slide_mask device needs --filter device")
@@ -74,7 +82,7 @@ def main(argv=None):
         if args.parallel:
             print("--filter device: slides are processed one after another in this process (--parallel is not used)")
         for o in opts:
-            process(o + ("cuda:0", args.filter_batch, args.slide_mask, args.reader))
+            process(o + ("cuda:0", args.filter_batch, args.slide_mask, args.reader, args.jpeg_entropy))
     elif args.parallel:
         with Pool(processes=4) as pool:
             pool.map(process, opts)

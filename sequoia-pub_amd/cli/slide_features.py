@@ -28,7 +28,7 @@ from .common import init_distributed, ref_frame, seed_everything
 from .compute_features import build_extractor
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description='Slide regions to patch and cluster features without a patch store')
     p.add_argument('--ref_file', type=str, required=True, help='Path with reference csv file')
     p.add_argument('--wsi_path', default="examples/HE", metavar='WSI_PATH', type=str)
@@ -43,6 +43,8 @@ def main(argv=None):
     p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
                    help="what opens a slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without "
                         "openslide, the tiles decoded on the GPU)")
+    p.add_argument('--jpeg_entropy', default='serial', choices=['serial', 'split'],
+                   help="JPEG tiles of --reader tiff: serial = one lane per tile (sq_jpeg_decode_tiles); split = the 64 lanes of a wave on one tile's scan (sq_jpeg_decode_tiles_split), the same bytes; JPEG 2000 levels and the openslide reader ignore it")
     p.add_argument('--feat_type', default="resnet", type=str, required=True, help='"resnet" or "uni"')
     p.add_argument('--feature_path', type=str, default="/examples/features", help='Output directory to save features')
     p.add_argument('--max_patch_number', type=int, default=4000, help='Max number of patches to use per slide')
@@ -52,6 +54,11 @@ def main(argv=None):
     p.add_argument('--seed', type=int, default=99, help='Seed for random generation')
     p.add_argument("--tcga_projects", help="the tcga_projects we want to use", default=None, type=str, nargs='*')
     p.add_argument('--num_clusters', type=int, default=100)
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     args = p.parse_args(argv)
     if args.batch < 1:
         p.error("--batch must be at least 1")
@@ -85,7 +92,7 @@ def main(argv=None):
                 print(f'{WSI}: Cluster feature already available')
                 continue
         try:
-            r = embed_slide(open_slide(slide_path, args.reader, device), model, patch_size=(args.patch_size, args.patch_size),
+            r = embed_slide(open_slide(slide_path, args.reader, device, entropy=args.jpeg_entropy), model, patch_size=(args.patch_size, args.patch_size),
                             max_patches_per_slide=args.max_patches_per_slide, max_patch_number=args.max_patch_number,
                             n_clusters=args.num_clusters, random_state=0, feat_type=args.feat_type, resize=args.resize, device=device,
                             batch=args.batch, slide_mask=args.slide_mask, mask_path=args.mask_path, slide_id=WSI_slide)

@@ -150,13 +150,13 @@ def embed_tiles(slide, df, patch_size_resized, out_size, feat_model, device, chu
     return allf[gathered_row_of_window(torch.arange(len(df), device=device), chunk, world, slots)]
 
 
-def open_slide(path, reader="openslide", device="cuda:0"):
+def open_slide(path, reader="openslide", device="cuda:0", entropy="serial"):
     """``reader``: 'openslide' (openslide-python, when it is installed) or 'tiff' (``wsi.TiffSlide``: JPEG-tiled TIFF / SVS,
-    decoded on `device`); an ``.npy`` RGB array is an ``ArraySlide`` whatever the reader."""
+    decoded on `device`, its JPEG tiles by the `entropy` decode); an ``.npy`` RGB array is an ``ArraySlide`` whatever the reader."""
     if path.endswith('.npy'):
         return ArraySlide([np.load(path)])
     from .. import wsi
-    return wsi.open_slide(path, reader, device)
+    return wsi.open_slide(path, reader, device, entropy=entropy)
 
 
 def build_model(model_type, input_dim, n_genes, device, compute_dtype):
@@ -199,6 +199,8 @@ def build_parser():
     p.add_argument('--reader', default='openslide', choices=['openslide', 'tiff'],
                    help='what opens the slide: openslide = openslide-python; tiff = wsi.TiffSlide (JPEG-tiled TIFF / Aperio SVS without '
                         'openslide, the tiles decoded on the GPU)')
+    p.add_argument('--jpeg_entropy', default='serial', choices=['serial', 'split'],
+                   help="JPEG tiles of --reader tiff: serial = one lane per tile (sq_jpeg_decode_tiles); split = the 64 lanes of a wave on one tile's scan (sq_jpeg_decode_tiles_split), the same bytes; JPEG 2000 levels and the openslide reader ignore it")
     p.add_argument('--valid_tiles', default='host', choices=['host', 'device'],
                    help='where the grid of valid tiles is decided: host = the scipy loop over every grid tile (default); device = one kernel '
                         'launch on the rank\'s device (patchgen.valid_tile_grid), the same frame')
@@ -227,7 +229,7 @@ def main(argv=None):
     stem = args.wsi_file_name.replace('.svs', '').replace('.tif', '').replace('.npy', '')
     slide_dir = args.slide_path or f'./TCGA/{args.project}/'
     mask = np.load(args.mask_path or f'./TCGA/{args.project}_Masks/{stem}/mask.npy')
-    slide = open_slide(os.path.join(slide_dir, args.wsi_file_name), args.reader, device)
+    slide = open_slide(os.path.join(slide_dir, args.wsi_file_name), args.reader, device, entropy=args.jpeg_entropy)
     resize_factor = args.resize_factor if args.resize_factor is not None else float(slide.properties.get('aperio.AppMag', 20)) / 20.0
     patch_size_resized = int(resize_factor * patch_size)
     if args.valid_tiles == 'device':                    # under torchrun every rank computes it: deterministic, cheaper than a broadcast

@@ -239,6 +239,148 @@ SQJ_HD int sqj_scan(const SqjChunk* words, uint32_t pos, uint32_t end, const Sqj
     return SQ_JPEG_OK;
 }
 
+// ---- one scan split over the lanes of a wave (include/sequoia_hip.h, "JPEG tiles, split entropy decode") ----
+// The lane-level pieces of sq_jpeg_decode_tiles_split; the kernel (jpegdec.hip) and tools/jpegsplit_hostcheck.cpp drive them
+// the same way, the one with wave shuffles and votes, the other with loops over 64 lanes.  Restart intervals are not handled
+// here: a tile that has one takes sqj_scan.
+//
+// A state names a symbol boundary from which a FRESH reader reproduces the bits: `pos` is the byte the next bit lies in -- a
+// byte the serial reader fetches as data, never the 00 of an FF 00 pair -- and `bit` how many of its bits are already used.
+// The reader itself cannot give that position as pos * 8 - nbits: it looks up to 64 bits ahead and drops stuffed zeros as it
+// goes (sqj_state_at walks back over what it fetched).  blk: the block's index within the MCU (luma blocks row-major, Cb, Cr);
+// k: the next coefficient's zigzag index, 0 where the next symbol is a DC symbol.
+struct SqjState { uint32_t pos; int32_t bit, blk, k, valid; };
+struct SqjSubResult {
+    SqjState end;                        // the first symbol boundary at or behind the subsequence's end; invalid after an error
+    int32_t blocks;                      // block ends passed (before the error, if there was one)
+    uint32_t dc0, dc1, dc2;              // sums of the DC differences per component, wrapping as the serial predictor's low bits do
+    int32_t rc;                          // SQ_JPEG_OK or the error that stopped the lane
+};
+
+SQJ_HD bool sqj_state_same(const SqjState& a, const SqjState& b) {
+    return a.valid == b.valid && (!a.valid || (a.pos == b.pos && a.bit == b.bit && a.blk == b.blk && a.k == b.k));
+}
+
+// one byte of [0, end) through a chunk the caller keeps (at: its index, 0xFFFFFFFF before the first use)
+SQJ_HD uint32_t sqj_walk_byte(const SqjChunk* words, SqjChunk* c, uint32_t* at, uint32_t p) {
+    if ((p >> 4) != *at) { *at = p >> 4; *c = words[*at]; }
+    return sqj_chunk_byte(*c, p);
+}
+
+// Where a lane starts when nobody has told it better: the first bit of the subsequence that begins at byte `at` of the scan
+// [pos, end), as if an MCU began there.  A subsequence that begins on the 00 of an FF 00 pair holds no bit of that pair.
+SQJ_HD SqjState sqj_sub_guess(const SqjChunk* words, uint32_t pos, uint32_t end, uint32_t at) {
+    SqjState s;
+    s.pos = at < end ? at : end; s.bit = 0; s.blk = 0; s.k = 0; s.valid = 1;
+    if (s.pos > pos && s.pos < end) {
+        SqjChunk c; uint32_t cat = 0xFFFFFFFFu;
+        c.lo = 0; c.hi = 0;
+        if (sqj_walk_byte(words, &c, &cat, s.pos) == 0 && sqj_walk_byte(words, &c, &cat, s.pos - 1) == 0xFF) s.pos += 1;
+    }
+    return s;
+}
+
+// Stream bits from state `s` up to the subsequence's end: 8 for every byte in [s.pos, sub_end) that the reader takes as data
+// (FF 00 is one; a marker or the scan's end stops the count as it stops the reader), less the bits already used.
+SQJ_HD int sqj_sub_bits(const SqjChunk* words, const SqjState* s, uint32_t sub_end, uint32_t end) {
+    SqjChunk c; uint32_t cat = 0xFFFFFFFFu;
+    c.lo = 0; c.hi = 0;
+    int bits = 0;
+    uint32_t p = s->pos;
+    while (p < sub_end) {                // sub_end <= end
+        if (sqj_walk_byte(words, &c, &cat, p) == 0xFF) {
+            if ((p + 1 < end ? sqj_walk_byte(words, &c, &cat, p + 1) : 1u) != 0) break;
+            p += 2;
+        } else p += 1;
+        bits += 8;
+    }
+    return bits - s->bit;
+}
+
+// The state of reader `b`, which was started at byte `from`, after an error-free symbol: back from b->pos over as many
+// fetched bytes as hold unread stream bits.  A 00 behind an FF was dropped by the reader unless the FF lies in front of `from`.
+SQJ_HD void sqj_state_at(const SqjBits* b, uint32_t from, SqjState* s) {
+    const int n = b->nreal > 0 ? b->nreal : 0;
+    uint32_t p = b->pos;
+    for (int t = (n + 7) >> 3; t > 0 && p > from; t--) {
+        p -= 1;
+        if (p > from && sqj_byte(b, p) == 0 && sqj_byte(b, p - 1) == 0xFF) p -= 1;
+    }
+    s->pos = p; s->bit = (8 - (n & 7)) & 7;
+}
+
+// index in the coefficient array of block n of the scan (MCU order); n < g->blocks
+SQJ_HD int sqj_scan_block_index(const SqjGeom* g, int n) {
+    const int luma = g->hs * g->vs, per = luma + 2;
+    const int mcu = n / per, r = n - mcu * per;
+    const int mx = mcu % g->mcus_x, my = mcu / g->mcus_x;
+    if (r < luma) return sqj_block_index(g, 0, mx * g->hs + r % g->hs, my * g->vs + r / g->hs);
+    return sqj_block_index(g, r - luma + 1, mx, my);
+}
+
+// One subsequence from state *st (valid): symbols are decoded while their first bit lies in front of sub_end (<= end), the
+// last one may run over it.  write == false counts: block ends and DC sums into *o.  write == true also stores: block0 is the
+// scan-order number of the block *st lies in, p0..p2 the predictors in front of it, and non-zero coefficients go to `coefs`
+// (the tile's, zeroed) exactly as sqj_block writes them; it stops in front of block g->blocks, so nothing is stored outside
+// the tile.  The symbol layer is sqj_symbol's and the block rules are sqj_block's, here one symbol at a time because a
+// subsequence begins and ends inside blocks (sqj_block itself is kept as the serial kernel compiles it).
+SQJ_HD void sqj_sub_run(const SqjChunk* words, uint32_t end, const SqjGeom* g, const SqjHuff* huff, const uint8_t* zigzag, int sel,
+                        const SqjState* st, uint32_t sub_end, bool write, int block0, uint32_t p0, uint32_t p1, uint32_t p2,
+                        int16_t* coefs, SqjSubResult* o) {
+    o->end = *st; o->blocks = 0; o->dc0 = 0; o->dc1 = 0; o->dc2 = 0; o->rc = SQ_JPEG_OK;
+    int budget = sqj_sub_bits(words, st, sub_end, end);
+    if (budget <= 0) return;             // the symbol before ran over the whole of it, or there is no data here
+    SqjBits b;
+    sqj_bits_init(&b, words, st->pos, end);
+    sqj_fill(&b);
+    sqj_skip(&b, st->bit);
+    const int luma = g->hs * g->vs, per = luma + 2;
+    int blk = st->blk, k = st->k, n = block0, rc = SQ_JPEG_OK;
+    int16_t* out = (write && n < g->blocks) ? coefs + (size_t)sqj_scan_block_index(g, n) * 64 : coefs;
+    while (budget > 0 && !(write && n >= g->blocks)) {
+        sqj_fill(&b);
+        const int before = b.nbits;
+        const int c = blk < luma ? 0 : blk - luma + 1;
+        int s = 0;
+        if (k == 0) {
+            if ((rc = sqj_symbol(&b, huff + ((sel >> (4 * c + 2)) & 1), &s)) != SQ_JPEG_OK) break;
+            if (s > 15) { rc = SQ_JPEG_BAD_CODE; break; }
+            uint32_t diff = 0;
+            if (s) {
+                const int v = (int)sqj_peek(&b, s);
+                if (!sqj_skip(&b, s)) { rc = SQ_JPEG_TRUNCATED; break; }
+                diff = (uint32_t)sqj_extend(v, s);
+            }
+            if (c == 0) { o->dc0 += diff; p0 += diff; } else if (c == 1) { o->dc1 += diff; p1 += diff; } else { o->dc2 += diff; p2 += diff; }
+            if (write) out[0] = (int16_t)(uint16_t)(c == 0 ? p0 : c == 1 ? p1 : p2);
+            k = 1;
+        } else {
+            if ((rc = sqj_symbol(&b, huff + 2 + ((sel >> (4 * c + 3)) & 1), &s)) != SQ_JPEG_OK) break;
+            const int r = s >> 4;
+            s &= 15;
+            if (s == 0) k = r == 15 ? k + 16 : 64;
+            else {
+                k += r;
+                if (k > 63) { rc = SQ_JPEG_BAD_COEF; break; }
+                const int v = (int)sqj_peek(&b, s);
+                if (!sqj_skip(&b, s)) { rc = SQ_JPEG_TRUNCATED; break; }
+                if (write) out[zigzag[k]] = (int16_t)sqj_extend(v, s);
+                k += 1;
+            }
+        }
+        if (k >= 64) {
+            k = 0; n += 1; o->blocks += 1;
+            blk = blk + 1 == per ? 0 : blk + 1;
+            if (write && n < g->blocks) out = coefs + (size_t)sqj_scan_block_index(g, n) * 64;
+        }
+        budget -= before - b.nbits;
+    }
+    o->rc = rc;
+    if (rc != SQ_JPEG_OK) { o->end.valid = 0; return; }
+    sqj_state_at(&b, st->pos, &o->end);
+    o->end.blk = blk; o->end.k = k; o->end.valid = 1;
+}
+
 // What a lane checks of its tile-table row before it reads a byte of the scan: SQ_JPEG_OK or the tile's status.
 // huff: the derived tables of all n_sets table sets, four each.
 SQJ_HD int sqj_tile_check(const int32_t* row, int n_sets, unsigned long long scans_bytes, const SqjHuff* huff) {

@@ -1,8 +1,9 @@
 // JPEG tiles of a tiled TIFF / SVS level -> RGBA regions on the device (include/sequoia_hip.h, "JPEG tiles").
-// Four kernels: table derivation (one thread per Huffman table), entropy decode (one lane per tile; the scan is serial, so a
+// Five kernels: table derivation (one thread per Huffman table), entropy decode (one lane per tile; the scan is serial, so a
 // wave runs as long as its longest lane -- the caller orders the tiles by scan length -- and lanes are spread over waves), IDCT (column pass and row pass through
-// LDS, 32 blocks per workgroup) and composition (four RGBA pixels per thread).  The arithmetic is jpeg_core.h's, which the
-// host check program compiles too.
+// LDS, 32 blocks per workgroup) and composition (four RGBA pixels per thread); and, behind sq_jpeg_decode_tiles_split, the entropy decode
+// with one WAVE per tile, whose 64 lanes share the tile's scan (self-synchronising subsequences; what is irregular falls back to the
+// serial scan on lane 0, so the bytes are the serial kernel's).  The arithmetic is jpeg_core.h's, which the host check programs compile too.
 #include "sq_common.h"
 #include "jpeg_core.h"
 #include <stdio.h>
@@ -63,6 +64,111 @@ __global__ __launch_bounds__(ENT_THREADS) void jpeg_entropy_kernel(JpegArgs a) {
                       a.coefs + (size_t)tile * a.g.blocks * 64);
     }
     a.status[tile] = rc;
+}
+
+// ---- the split entropy decode: one wave per tile, its 64 lanes on the tile's scan (jpeg_core.h, "one scan split over the lanes") ----
+__device__ __forceinline__ SqjState shfl_up_state(const SqjState& s, int d) {
+    SqjState r;
+    r.pos = (uint32_t)__shfl_up((int)s.pos, d); r.bit = __shfl_up(s.bit, d); r.blk = __shfl_up(s.blk, d);
+    r.k = __shfl_up(s.k, d); r.valid = __shfl_up(s.valid, d);
+    return r;
+}
+__device__ __forceinline__ SqjState shfl_state(const SqjState& s, int lane) {
+    SqjState r;
+    r.pos = (uint32_t)__shfl((int)s.pos, lane); r.bit = __shfl(s.bit, lane); r.blk = __shfl(s.blk, lane);
+    r.k = __shfl(s.k, lane); r.valid = __shfl(s.valid, lane);
+    return r;
+}
+// inclusive sum over the wave's lanes
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < ENT_THREADS; d <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(ENT_THREADS) void jpeg_entropy_split_kernel(JpegArgs a, int sub) {
+    __shared__ SqjHuff lds_huff[4];
+    __shared__ uint8_t lds_zigzag[64];
+    const int tile = blockIdx.x, lane = threadIdx.x;                       // tile < n_tiles by the grid
+    const int32_t* row = a.tile_table + (size_t)tile * SQ_JPEG_TILE_WORDS;
+    const int checked = sqj_tile_check(row, a.n_sets, a.scans_bytes, a.huff);           // the same on every lane
+    lds_zigzag[lane] = ZIGZAG[lane];
+    if (checked == SQ_JPEG_OK) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.huff + (size_t)row[2] * 4);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(lds_huff);
+        for (int i = lane; i < (int)(4 * sizeof(SqjHuff) / 4); i += ENT_THREADS) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (checked != SQ_JPEG_OK) {
+        if (lane == 0) a.status[tile] = checked;
+        return;
+    }
+    // from here every branch but those inside sqj_sub_run is taken by the whole wave: the conditions come from votes and shuffles
+    const uint32_t pos = (uint32_t)row[0], end = pos + (uint32_t)row[1];
+    const int sel = row[4], restart = row[3];
+    const long long n_sub = ((long long)row[1] + sub - 1) / sub;
+    int16_t* coefs = a.coefs + (size_t)tile * a.g.blocks * 64;
+    const uint32_t want = (uint32_t)a.g.blocks;
+    bool done = false, bad = restart > 0;
+    SqjState carry;
+    carry.pos = pos; carry.bit = 0; carry.blk = 0; carry.k = 0; carry.valid = 1;
+    uint32_t base = 0, pred0 = 0, pred1 = 0, pred2 = 0;
+    for (long long first = 0; first < n_sub && !done && !bad; first += ENT_THREADS) {
+        const unsigned long long at = (unsigned long long)pos + (unsigned long long)(first + lane) * sub;
+        const uint32_t sub_end = (uint32_t)(at + sub < end ? at + sub : end);
+        const bool live = first + lane < n_sub;
+        const SqjState guess = lane == 0 ? carry : sqj_sub_guess(a.scans, pos, end, (uint32_t)(at < end ? at : end));
+        SqjState start = guess;
+        SqjSubResult res;
+        sqj_sub_run(a.scans, end, &a.g, lds_huff, lds_zigzag, sel, &start, sub_end, false, 0, 0, 0, 0, coefs, &res);
+        for (int r = 0; r < ENT_THREADS - 1; r++) {                        // lane r is exact after round r
+            const SqjState in = shfl_up_state(res.end, 1);
+            const SqjState next = (lane == 0 || !live) ? start : in.valid ? in : guess;      // a lane behind the scan's end has nothing to agree on
+            const bool changed = !sqj_state_same(next, start);
+            if (!__any(changed)) break;
+            if (changed) {
+                start = next;
+                sqj_sub_run(a.scans, end, &a.g, lds_huff, lds_zigzag, sel, &start, sub_end, false, 0, 0, 0, 0, coefs, &res);
+            }
+        }
+        const uint32_t blocks_in = wave_scan((uint32_t)res.blocks, lane), s0 = wave_scan(res.dc0, lane), s1 = wave_scan(res.dc1, lane),
+                       s2 = wave_scan(res.dc2, lane);
+        const bool reached = base + blocks_in >= want;                     // the scan's last block ends in this lane or before it
+        const unsigned long long reached_mask = __ballot(reached);
+        const int last = reached_mask ? __builtin_ctzll(reached_mask) : ENT_THREADS - 1;
+        if (__any(lane <= last && !reached && !res.end.valid)) bad = true;
+        if (reached_mask) {
+            done = true;
+            if (base + (uint32_t)__shfl((int)blocks_in, last) > want) bad = true;
+        }
+        if (bad) break;
+        SqjSubResult w;
+        w.rc = SQ_JPEG_OK;
+        if (lane <= last)
+            sqj_sub_run(a.scans, end, &a.g, lds_huff, lds_zigzag, sel, &start, sub_end, true, (int)(base + blocks_in - (uint32_t)res.blocks),
+                        pred0 + s0 - res.dc0, pred1 + s1 - res.dc1, pred2 + s2 - res.dc2, coefs, &w);
+        if (__any(w.rc != SQ_JPEG_OK)) bad = true;
+        const SqjState reached_state = shfl_state(res.end, ENT_THREADS - 1);
+        if (!done && sqj_state_same(reached_state, carry)) bad = true;      // a marker in the scan: no lane can pass it, the serial scan says why
+        carry = reached_state;
+        base += (uint32_t)__shfl((int)blocks_in, ENT_THREADS - 1);
+        pred0 += (uint32_t)__shfl((int)s0, ENT_THREADS - 1);
+        pred1 += (uint32_t)__shfl((int)s1, ENT_THREADS - 1);
+        pred2 += (uint32_t)__shfl((int)s2, ENT_THREADS - 1);
+    }
+    int rc = SQ_JPEG_OK;
+    if (!done || bad) {                  // anything irregular: the serial scan's status and coefficients
+        __syncthreads();                 // the lanes' stores are behind the zeros
+        u32x4* z = reinterpret_cast<u32x4*>(coefs);
+        const u32x4 zero = {0, 0, 0, 0};
+        for (int i = lane; i < a.g.blocks * 8; i += ENT_THREADS) z[i] = zero;
+        __syncthreads();                 // and the zeros behind lane 0's stores
+        if (lane == 0) rc = sqj_scan(a.scans, pos, end, &a.g, lds_huff, lds_zigzag, sel, restart, coefs);
+    }
+    if (lane == 0) a.status[tile] = rc;
 }
 
 __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(JpegArgs a) {
@@ -185,21 +291,22 @@ extern "C" size_t sq_jpeg_planes_bytes(int n_tiles, int tile_w, int tile_h, int 
     return (size_t)n_tiles * g.plane_bytes;
 }
 
-extern "C" int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles,
-                                    const uint8_t* table_sets, int n_table_sets, int tile_w, int tile_h, int hs, int vs,
-                                    uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
+// both decode entries; sub < 0: the serial entropy kernel, else the split one with subsequences of `sub` bytes
+static int decode_tiles(const char* entry, int sub, const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles,
+                        const uint8_t* table_sets, int n_table_sets, int tile_w, int tile_h, int hs, int vs,
+                        uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     JpegArgs a;
-    if (!frame_ok("sq_jpeg_decode_tiles", tile_w, tile_h, hs, vs, &a.g)) return SQ_ERR_ARG;
-    SQ_REQUIRE(n_tiles >= 1 && n_tiles <= (1 << 24), "sq_jpeg_decode_tiles: n_tiles = %d, must be in 1..%d", n_tiles, 1 << 24);
-    SQ_REQUIRE(n_table_sets >= 1 && n_table_sets <= (1 << 24), "sq_jpeg_decode_tiles: n_table_sets = %d, must be in 1..%d", n_table_sets, 1 << 24);
-    SQ_REQUIRE(scans && tile_table && table_sets && planes && status && workspace, "sq_jpeg_decode_tiles: a null pointer");
+    if (!frame_ok(entry, tile_w, tile_h, hs, vs, &a.g)) return SQ_ERR_ARG;
+    SQ_REQUIRE(n_tiles >= 1 && n_tiles <= (1 << 24), "%s: n_tiles = %d, must be in 1..%d", entry, n_tiles, 1 << 24);
+    SQ_REQUIRE(n_table_sets >= 1 && n_table_sets <= (1 << 24), "%s: n_table_sets = %d, must be in 1..%d", entry, n_table_sets, 1 << 24);
+    SQ_REQUIRE(scans && tile_table && table_sets && planes && status && workspace, "%s: a null pointer", entry);
     SQ_REQUIRE(scans_bytes >= 16 && scans_bytes % 16 == 0 && scans_bytes <= 0xFFFFFFF0ull && ((uintptr_t)scans & 15) == 0,
-               "sq_jpeg_decode_tiles: scans of %zu bytes at %p: the base must be 16-byte aligned and the size a multiple of 16 in 16..2^32-16",
-               scans_bytes, (const void*)scans);
+               "%s: scans of %zu bytes at %p: the base must be 16-byte aligned and the size a multiple of 16 in 16..2^32-16",
+               entry, scans_bytes, (const void*)scans);
     SQ_REQUIRE(((uintptr_t)planes & 7) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)tile_table & 3) == 0 && ((uintptr_t)status & 3) == 0,
-               "sq_jpeg_decode_tiles: planes must be 8-byte, the workspace 16-byte, tile_table and status 4-byte aligned");
-    SQ_REQUIRE_WORKSPACE("sq_jpeg_decode_tiles", workspace_bytes, sq_jpeg_workspace_bytes(n_tiles, n_table_sets, tile_w, tile_h, hs, vs));
+               "%s: planes must be 8-byte, the workspace 16-byte, tile_table and status 4-byte aligned", entry);
+    SQ_REQUIRE_WORKSPACE(entry, workspace_bytes, sq_jpeg_workspace_bytes(n_tiles, n_table_sets, tile_w, tile_h, hs, vs));
     a.scans = reinterpret_cast<const SqjChunk*>(scans); a.scans_bytes = scans_bytes;
     a.tile_table = tile_table; a.n_tiles = n_tiles; a.table_sets = table_sets; a.n_sets = n_table_sets;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
@@ -219,10 +326,15 @@ extern "C" int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, co
         hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)((n_table_sets * 4 + 63) / 64)), dim3(64), 0, stream, a);
         SQ_LAUNCH_CHECK();
     }
-    {
+    if (sub < 0) {
         SqProf prof(stream);
         if (prof.on()) { snprintf(name, sizeof(name), "jpeg_entropy_n%d_%dx%d", n_tiles, tile_w, tile_h); prof.begin(name, 0.0, (double)scans_bytes + (double)coef_bytes); }
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((n_tiles + a.lanes - 1) / a.lanes)), dim3(ENT_THREADS), 0, stream, a);
+        SQ_LAUNCH_CHECK();
+    } else {
+        SqProf prof(stream);
+        if (prof.on()) { snprintf(name, sizeof(name), "jpeg_entropy_split_n%d_%dx%d_b%d", n_tiles, tile_w, tile_h, sub); prof.begin(name, 0.0, (double)scans_bytes + (double)coef_bytes); }
+        hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)n_tiles), dim3(ENT_THREADS), 0, stream, a, sub);
         SQ_LAUNCH_CHECK();
     }
     SqProf prof(stream);
@@ -230,6 +342,28 @@ extern "C" int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, co
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(IDCT_THREADS), 0, stream, a);
     SQ_LAUNCH_CHECK();
     return SQ_OK;
+}
+
+extern "C" int sq_jpeg_decode_tiles(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles,
+                                    const uint8_t* table_sets, int n_table_sets, int tile_w, int tile_h, int hs, int vs,
+                                    uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream) {
+    return decode_tiles("sq_jpeg_decode_tiles", -1, scans, scans_bytes, tile_table, n_tiles, table_sets, n_table_sets, tile_w, tile_h, hs, vs,
+                        planes, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t sq_jpeg_split_workspace_bytes(int n_tiles, int n_table_sets, int tile_w, int tile_h, int hs, int vs) {
+    return sq_jpeg_workspace_bytes(n_tiles, n_table_sets, tile_w, tile_h, hs, vs);       // the lane states live in registers
+}
+
+extern "C" int sq_jpeg_decode_tiles_split(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles,
+                                          const uint8_t* table_sets, int n_table_sets, int tile_w, int tile_h, int hs, int vs,
+                                          uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, int sub_bytes,
+                                          sq_stream_t stream) {
+    SQ_REQUIRE(sub_bytes == 0 || (sub_bytes >= SQ_JPEG_SPLIT_SUB_MIN && sub_bytes <= SQ_JPEG_SPLIT_SUB_MAX && sub_bytes % 4 == 0),
+               "sq_jpeg_decode_tiles_split: sub_bytes = %d, must be a multiple of 4 in %d..%d, or 0 for the default (%d)", sub_bytes,
+               SQ_JPEG_SPLIT_SUB_MIN, SQ_JPEG_SPLIT_SUB_MAX, SQ_JPEG_SPLIT_SUB_DEFAULT);
+    return decode_tiles("sq_jpeg_decode_tiles_split", sub_bytes ? sub_bytes : SQ_JPEG_SPLIT_SUB_DEFAULT, scans, scans_bytes, tile_table, n_tiles,
+                        table_sets, n_table_sets, tile_w, tile_h, hs, vs, planes, status, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sq_jpeg_compose_regions(const uint8_t* planes, int n_slots, int tile_w, int tile_h, int hs, int vs, int transform,

@@ -468,10 +468,22 @@ class _Level:
 
 class TiffSlide:
     """``openslide.OpenSlide(path)`` for a JPEG-tiled TIFF / SVS file (module docstring).  ``read_region`` returns an RGBA
-    ``PIL.Image``; ``read_regions`` the same pixels for a batch as a device tensor.  Opening and the properties need no GPU."""
+    ``PIL.Image``; ``read_regions`` the same pixels for a batch as a device tensor.  Opening and the properties need no GPU.
+    ``entropy``: how the scans of JPEG tiles are decoded -- 'serial' (one lane per tile, ``sq_jpeg_decode_tiles``) or 'split'
+    (the 64 lanes of a wave on one tile's scan, ``sq_jpeg_decode_tiles_split``: the same bytes whatever the file holds; tiles
+    with restart intervals still decode on one lane).  ``sub_bytes``, an expert knob of 'split': the bytes of scan per lane and
+    round, a multiple of 4 in SQ_JPEG_SPLIT_SUB_MIN..SQ_JPEG_SPLIT_SUB_MAX, or 0 for the library's default.  JPEG 2000 levels
+    ignore both."""
 
-    def __init__(self, path, device="cuda:0", workspace_budget=DEFAULT_WORKSPACE_BUDGET):
+    def __init__(self, path, device="cuda:0", workspace_budget=DEFAULT_WORKSPACE_BUDGET, entropy="serial", *, sub_bytes=0):
+        if entropy not in ("serial", "split"):
+            raise ValueError(f"entropy={entropy!r}: 'serial' or 'split'")
+        sub_bytes = int(sub_bytes)
+        if sub_bytes and not (_C["SQ_JPEG_SPLIT_SUB_MIN"] <= sub_bytes <= _C["SQ_JPEG_SPLIT_SUB_MAX"] and sub_bytes % 4 == 0):
+            raise ValueError(f"sub_bytes={sub_bytes}: a multiple of 4 in {_C['SQ_JPEG_SPLIT_SUB_MIN']}..{_C['SQ_JPEG_SPLIT_SUB_MAX']}, or 0 "
+                             f"for the library's default")
         self.path, self.device, self.workspace_budget = path, device, int(workspace_budget)
+        self.entropy, self.sub_bytes = entropy, sub_bytes
         self._fd = os.open(path, os.O_RDONLY)
         self._pinned = None
         self.last_batch_tiles = []           # (tile_x, tile_y) of every tile decode of the last read_regions call, chunk by chunk
@@ -781,6 +793,11 @@ class TiffSlide:
             need = _lib.need(L.sq_j2k_workspace_bytes, n, lv.tile_w, lv.tile_h, *caps, scans_bytes)
             _lib.call("sq_j2k_decode_tiles", dev, blob[head:], scans_bytes, blob, n, blob[o_sets:], len(sets), lv.tile_w, lv.tile_h, *caps,
                       planes, status, workspace=need)
+        elif self.entropy == "split":
+            need = _lib.need(L.sq_jpeg_split_workspace_bytes, n, len(sets), *geom)
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)      # in the argument list: sub_bytes stands behind the workspace pair
+            _lib.call("sq_jpeg_decode_tiles_split", dev, blob[head:], scans_bytes, blob, n, blob[o_sets:], len(sets), *geom, planes, status,
+                      scratch, need, self.sub_bytes)
         else:
             need = _lib.need(L.sq_jpeg_workspace_bytes, n, len(sets), *geom)
             _lib.call("sq_jpeg_decode_tiles", dev, blob[head:], scans_bytes, blob, n, blob[o_sets:], len(sets), *geom, planes, status, workspace=need)
@@ -802,11 +819,14 @@ MISSING_OPENSLIDE = ("openslide-python is required to read whole-slide images (p
                      "JPEG-tiled TIFF and Aperio SVS files open without it: pass --reader tiff.")
 
 
-def open_slide(path, reader="openslide", device="cuda:0"):
+def open_slide(path, reader="openslide", device="cuda:0", entropy="serial"):
     """The slide object of the CLIs' ``--reader`` flag: 'tiff' is ``TiffSlide``, 'openslide' is ``openslide.OpenSlide`` (and a
-    SystemExit that points to ``--reader tiff`` when openslide-python is not installed)."""
+    SystemExit that points to ``--reader tiff`` when openslide-python is not installed).  ``entropy`` ('serial' or 'split', the
+    CLIs' ``--jpeg_entropy``) is ``TiffSlide``'s; the openslide reader has no use for it."""
+    if entropy not in ("serial", "split"):
+        raise ValueError(f"entropy={entropy!r}: 'serial' or 'split'")
     if reader == "tiff":
-        return TiffSlide(path, device=device)
+        return TiffSlide(path, device=device, entropy=entropy)
     if reader != "openslide":
         raise ValueError(f"reader={reader!r}: 'openslide' or 'tiff'")
     try:
