@@ -1261,6 +1261,47 @@ int sq_j2k_decode_tiles(const uint8_t* streams, size_t streams_bytes, const int3
 int sq_cohort_gather(const float* x_table, const float* y_table, int n_slides, long long row_x, long long row_y, const int32_t* index,
                      int m, float* x_out, float* y_out, sq_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * CSV text: the spatial prediction table of the reference's spatial_vis/visualize.py:286-304 -- per gene and fold a column,
+ * then per gene the fold mean, written with DataFrame.to_csv -- made on the device (sequoia-pub_amd/csvtext.py is the caller).
+ *   sq_fold_mean_f32 : out[r, c] = what DataFrame.mean(axis=1) gives for the float32 values x[f * fold_stride + r * ld + c],
+ *                      f = 0 .. n_folds - 1 (pandas' nanmean, bit for bit): sum = +0.0; sum += (v is NaN ? +0.0 : v) in fold
+ *                      order in fp32; out = sum / (float)count of the values that are not NaN, correctly rounded; count 0 gives
+ *                      NaN.  (So -0.0 alone gives +0.0.)  x and out may be columns of one table: out[r * ld_out + c].
+ *   sq_csv_format_rows : the bytes DataFrame.to_csv() (default arguments, Linux) writes for rows row_lo .. row_hi - 1 of a
+ *                      frame with the int64 index `index` [n], the int64 columns ints [n, n_int] (dense) and the float32
+ *                      columns f32 [n, n_f32] (row stride ld_f32), in that column order; the header line is the caller's.
+ *                      A row is its cells joined by ',' and ended by '\n'.  int64: plain decimal.  float32: exactly
+ *                      numpy.ndarray.astype(str) -- the shortest digits inside the value's rounding interval, the closest
+ *                      of them, a tie to the even digit (numpy's Dragon4: a bound counts as inside for an even mantissa only);
+ *                      positional for 1e-4 <= |x| < 1e16 with ".0" behind integers ("3333333500000000.0"), else scientific
+ *                      with a sign and two exponent digits ("1e-05", "3e+16"); "-0.0", "inf", "-inf"; NaN is the empty cell.
+ *                      A cell with its separator is at most SQ_CSV_MAX_CELL_BYTES bytes (csrc/fmt_core.h holds the text of
+ *                      a cell as host-and-device functions).
+ *                      Outputs: out[0 .. min(total, capacity)), row_offsets int64 [rows + 1] (row i of the call starts at
+ *                      row_offsets[i]; the last entry is the total), total int64 [1], status int32 [1]: SQ_CSV_OK, or
+ *                      SQ_CSV_OVERFLOW when total > capacity -- then `out` holds part of the text, and no byte at or behind
+ *                      `capacity` is ever written.  Three launches in stream order (cell lengths; an exclusive scan of the
+ *                      per-workgroup sums by one workgroup; the bytes), the cells of the call dealt as one flat array, so a row
+ *                      of 10^5 cells is many workgroups' work and no workgroup waits for another.  Offsets are 64-bit.
+ *                      Limits: 1 <= rows, n_int and n_f32 in 0 .. SQ_CSV_MAX_COLUMNS, rows * (1 + n_int + n_f32) <=
+ *                      SQ_CSV_MAX_CELLS; out 4-byte aligned.  Asynchronous; arguments are checked before the first launch.
+ *   sq_csv_format_workspace_bytes : workspace of sq_csv_format_rows for rows = row_hi - row_lo (one byte per cell plus the
+ *                      scan's tables); 0 for shapes outside the limits.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_CSV_OK 0
+#define SQ_CSV_OVERFLOW 1
+#define SQ_CSV_MAX_CELL_BYTES 21
+#define SQ_CSV_MAX_COLUMNS 1048576
+#define SQ_CSV_MAX_CELLS 1073741824
+#define SQ_CSV_MAX_FOLDS 64
+int sq_fold_mean_f32(const float* x, int n_folds, long long fold_stride, long long n, int cols, long long ld, float* out, long long ld_out,
+                     sq_stream_t stream);
+size_t sq_csv_format_workspace_bytes(long long rows, int n_int, int n_f32);
+int sq_csv_format_rows(const int64_t* index, const int64_t* ints, int n_int, const float* f32, int n_f32, long long ld_f32,
+                       long long row_lo, long long row_hi, uint8_t* out, long long capacity, int64_t* row_offsets, int64_t* total,
+                       int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,10 @@ resized to 256 x 256 by default; ``--resnet_input reference`` gives the extracto
 ``transforms.Resize((256, 265))`` gives it (spatial_vis/visualize.py:212-216): EVERY tile, 256 x 256 ones included, resized
 to height 256, width 265 with PIL's BILINEAR filter, byte for byte (``imgproc.resize_u8_pil``; ``--resize`` does not apply
 to it).  UNI tiles go to 224 as in the reference.  ``--valid_tiles device`` decides which grid tiles are read in one kernel launch
-(``valid_tiles_device``) instead of the scipy loop over every tile; the frame and the CSV are the same."""
+(``valid_tiles_device``) instead of the scipy loop over every tile; the frame and the CSV are the same.  ``--table device``
+keeps the fold tables on the device, takes the fold mean there and writes the CSV from text formatted on the device
+(``csvtext.write_prediction_table``): the same file byte for byte, without the per-gene dictionaries and ``to_csv``'s
+formatting; it then returns the frame only when it is small (``csvtext.SMALL_FRAME_CELLS`` cells), else ``(None, save_name)``."""
 import argparse
 import os
 import pickle
@@ -204,6 +207,10 @@ def build_parser():
     p.add_argument('--valid_tiles', default='host', choices=['host', 'device'],
                    help='where the grid of valid tiles is decided: host = the scipy loop over every grid tile (default); device = one kernel '
                         'launch on the rank\'s device (patchgen.valid_tile_grid), the same frame')
+    p.add_argument('--table', default='host', choices=['host', 'device'],
+                   help='where the prediction table is assembled and turned into CSV text: host = per-gene dictionaries, DataFrame.mean '
+                        'and to_csv (default); device = fold tables, fold mean and text on the device (csvtext.py), the same bytes; '
+                        'main() then returns the frame only when it is small, else (None, path)')
     return p
 
 
@@ -271,6 +278,27 @@ def main(argv=None):
             inds.append(gene_ids.index(g))
         else:
             print('gene not in predicted values ' + str(g))
+    table = args.table
+    if table == 'device':
+        from .. import csvtext
+        from ..spatial import sliding_window_table
+        sel = list(dict.fromkeys(inds))                 # a gene named twice is one column, as on the host
+        names = [gene_ids[i] + '_' + str(f) for f in folds for i in sel] + [gene_ids[i] for i in sel]
+        why = csvtext.frame_refusal(df, names) or ('a fold is named twice' if len(set(folds)) != len(folds) else None)
+        if why:
+            print(f'--table device: {why}; writing the table on the host')
+            table = 'host'
+    if table == 'device':
+        n, F, G = len(df), len(folds), len(sel)
+        if n > csvtext.MAX_TILES:
+            raise SystemExit(f'--table device: {n} tiles, at most {csvtext.MAX_TILES}')
+        free = torch.cuda.mem_get_info(device)[0]
+        need = (F + 2) * n * G * 4                      # the table below (F folds and the means) and one fold's table on its way into it
+        if need > free // 2:
+            raise SystemExit(f'--table device: the table of {F} folds and their mean and one fold in flight need ({F} + 2) x {n} tiles x '
+                             f'{G} genes x 4 bytes = {need} bytes, more than half of the {free} bytes free on {device}; '
+                             f'use fewer genes or --table host')
+        fold_table = torch.empty(n, (F + 1) * G, dtype=torch.float32, device=device)       # the float columns of the CSV: folds, then means
     for fold in folds:
         fold_ckpt = os.path.join(checkpoint, 'model_best_' + str(fold) + '.pt')
         if fold == 0 and args.model_type in ('vit', 'vis'):
@@ -282,14 +310,25 @@ def main(argv=None):
         else:
             model.load_state_dict(torch.load(fold_ckpt, map_location='cpu'))
         model = model.to(device).eval()
+        if table == 'device':
+            k = folds.index(fold)
+            fold_table[:, k * G:(k + 1) * G] = sliding_window_table(df, tile_features, model, sel, stride, shard=shard)
+            continue
         preds = sliding_window_method(df, tile_features, model, inds, stride, shard=shard)
         for ind_gene in inds:
             res_df[gene_ids[ind_gene] + '_' + str(fold)] = res_df.index.map(preds[ind_gene])
-    for ind_gene in inds:
-        res_df[gene_ids[ind_gene]] = res_df[[gene_ids[ind_gene] + '_' + str(i) for i in folds]].mean(axis=1)
     save_name = os.path.join(save_path, 'stride-' + str(stride) + '.csv')
-    if rank == 0:
-        res_df.to_csv(save_name)
+    if table == 'device':
+        if G and n:
+            csvtext.fold_mean(fold_table[:, :F * G].unflatten(1, (F, G)).permute(1, 0, 2), out=fold_table[:, F * G:])
+        res_df = None
+        if rank == 0:
+            res_df, _ = csvtext.write_prediction_table(save_name, df, fold_table, names)
+    else:
+        for ind_gene in inds:
+            res_df[gene_ids[ind_gene]] = res_df[[gene_ids[ind_gene] + '_' + str(i) for i in folds]].mean(axis=1)
+        if rank == 0:
+            res_df.to_csv(save_name)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

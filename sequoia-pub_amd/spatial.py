@@ -308,6 +308,31 @@ def gathered_row_of_window(w, batch_windows, world, slots):
     return torch.where(w >= 0, row, w) if torch.is_tensor(w) else (row if w >= 0 else w)
 
 
+def _selected_columns(df, tile_features, model, genes, stride, literal_2d, batch_windows, shard):
+    """What sliding_window_method and sliding_window_table share: the slide through sliding_window_all_genes_sharded and the
+    requested gene columns of every tile on the device.  Returns (sel f32 [n_tiles, len(genes)], votes int64 [n_tiles]).  Over
+    several ranks the columns of every rank's tiles are all-gathered, so every rank holds the same, complete table."""
+    rank, world, group = _shard_info(shard)
+    out, tile_ids, counts = sliding_window_all_genes_sharded(df['xcoord_tf'].values, df['ycoord_tf'].values, tile_features, model, stride,
+                                                            literal_2d=literal_2d, batch_windows=batch_windows, shard=shard)
+    n_tiles = counts.numel()
+    sel_local = out[:, torch.as_tensor(genes, device=out.device)] if genes else out[:, :0]
+    if world == 1:
+        return sel_local, counts
+    # equal-sized blocks for the collective: every rank owns at most ceil(chunks / world) head chunks
+    per = -(-(-(-n_tiles // HEAD_CHUNK)) // world) * HEAD_CHUNK
+    blk = torch.full((per, len(genes) + 1), float("nan"), dtype=torch.float32, device=out.device)
+    blk[:tile_ids.numel(), :len(genes)] = sel_local
+    blk[:tile_ids.numel(), len(genes)] = tile_ids.to(torch.float32)           # (tile ids < 2^24: exact in fp32)
+    blk[tile_ids.numel():, len(genes)] = -1
+    allb = torch.empty(world * per, len(genes) + 1, dtype=torch.float32, device=out.device)
+    torch.distributed.all_gather(list(allb.chunk(world)), blk, group=group)
+    ids = allb[:, len(genes)].to(torch.int64)
+    sel_t = torch.full((n_tiles, len(genes)), float("nan"), dtype=torch.float32, device=out.device)
+    sel_t[ids[ids >= 0]] = allb[ids >= 0, :len(genes)]
+    return sel_t, counts
+
+
 @torch.no_grad()
 def sliding_window_method(df, tile_features, model, inds_gene_of_interest, stride, literal_2d=False, batch_windows=512, shard=None):
     """visualize.py:35-102.  df: DataFrame with integer columns xcoord_tf / ycoord_tf (tile grid); tile_features:
@@ -317,26 +342,8 @@ def sliding_window_method(df, tile_features, model, inds_gene_of_interest, strid
     tiles are dealt over the ranks (sliding_window_all_genes_sharded); the requested gene columns of every rank's tiles are
     all-gathered, so every rank returns the same, complete dictionary -- bit-identical to the one-rank call."""
     genes = list(inds_gene_of_interest)
-    rank, world, group = _shard_info(shard)
-    out, tile_ids, counts = sliding_window_all_genes_sharded(df['xcoord_tf'].values, df['ycoord_tf'].values, tile_features, model, stride,
-                                                            literal_2d=literal_2d, batch_windows=batch_windows, shard=shard)
-    n_tiles = counts.numel()
-    sel_local = out[:, torch.as_tensor(genes, device=out.device)] if genes else out[:, :0]
-    if world > 1:
-        # equal-sized blocks for the collective: every rank owns at most ceil(chunks / world) head chunks
-        per = -(-(-(-n_tiles // HEAD_CHUNK)) // world) * HEAD_CHUNK
-        blk = torch.full((per, len(genes) + 1), float("nan"), dtype=torch.float32, device=out.device)
-        blk[:tile_ids.numel(), :len(genes)] = sel_local
-        blk[:tile_ids.numel(), len(genes)] = tile_ids.to(torch.float32)           # (tile ids < 2^24: exact in fp32)
-        blk[tile_ids.numel():, len(genes)] = -1
-        allb = torch.empty(world * per, len(genes) + 1, dtype=torch.float32, device=out.device)
-        torch.distributed.all_gather(list(allb.chunk(world)), blk, group=group)
-        ids = allb[:, len(genes)].to(torch.int64)
-        sel_t = torch.full((n_tiles, len(genes)), float("nan"), dtype=torch.float32, device=out.device)
-        sel_t[ids[ids >= 0]] = allb[ids >= 0, :len(genes)]
-        sel = sel_t.cpu().numpy()
-    else:
-        sel = sel_local.cpu().numpy() if genes else np.zeros((n_tiles, 0), np.float32)
+    sel, counts = _selected_columns(df, tile_features, model, genes, stride, literal_2d, batch_windows, shard)
+    sel = sel.cpu().numpy()
     cnt = counts.cpu().numpy()
     index = list(df.index)
     preds = {g: {} for g in genes}
@@ -344,6 +351,17 @@ def sliding_window_method(df, tile_features, model, inds_gene_of_interest, strid
         for gi, g in enumerate(genes):
             preds[g][index[t]] = sel[t, gi]
     return preds
+
+
+@torch.no_grad()
+def sliding_window_table(df, tile_features, model, inds_gene_of_interest, stride, literal_2d=False, batch_windows=512, shard=None):
+    """``sliding_window_method`` up to its table: f32 [n_tiles, n_sel] ON THE DEVICE, column k = gene inds_gene_of_interest[k],
+    row i = df.iloc[i]; a tile no kept window covers holds NaN in every column (the key the dictionaries lack).  The values
+    are the ones ``sliding_window_method`` puts into its dictionaries, bit for bit, ViS, ViT and HE2RNA alike; nothing is
+    downloaded.  Under ``shard`` the same all-gather is made, so every rank returns the same, complete table.  For
+    ``csvtext.write_prediction_table`` (``cli.visualize --table device``)."""
+    sel, counts = _selected_columns(df, tile_features, model, list(inds_gene_of_interest), stride, literal_2d, batch_windows, shard)
+    return torch.where((counts > 0).unsqueeze(1), sel, torch.full((), float("nan"), dtype=torch.float32, device=sel.device)).contiguous()
 
 
 @torch.no_grad()
