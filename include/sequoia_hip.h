@@ -1242,6 +1242,63 @@ int sq_j2k_decode_tiles(const uint8_t* streams, size_t streams_bytes, const int3
                         int32_t* status, void* workspace, size_t workspace_bytes, sq_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * LZW and uncompressed tiles: the tiles of a generic tiled TIFF level with Compression 5 (LZW) or 1 (none), chunky RGB of
+ * 8 bits, decoded into the planes sq_jpeg_compose_regions reads with hs = vs = 1 and transform 0 (three full-resolution
+ * uint8 planes per tile, R, G, B: sq_jpeg_planes_bytes(n, tile_w, tile_h, 1, 1)); sequoia-pub_amd/wsi.py is the caller.
+ * sequoia-pub_amd/csrc/lzw_core.h holds the code arithmetic, the serial decoder and the status rules as host-and-device
+ * functions; every byte is libtiff's.
+ *   codes       packed MSB first; behind a Clear (256) code j = 0, 1, ... is 9 bits wide for j < 254, 10 for j < 766, 11 for
+ *               j < 1790, then 12 (libtiff's early change), so the bit position of code j is a function of j; the Clear or
+ *               EOI (257) that ends a segment is read at the width of its number.  Old-style streams (LSB first, no Clear at
+ *               the start) are not read.
+ *   entries     code j >= 1 makes entry 257 + j: the string of code j - 1 and the first byte of the string of code j, which
+ *               lie next to each other in the output: an entry is (position, length), 8 bytes, and holds no bytes.  A code
+ *               above the next free entry is a bad code; one equal to it copies a range that overlaps what it writes.
+ *   overrun     as libtiff: entries past 4095 are counted though no code can name them; the data code that would make entry
+ *               5119 (the 4863rd behind a Clear) ends the tile with SQ_LZW_TABLE_FULL.  A Clear at any earlier point, after
+ *               every code included, restarts the table; consecutive Clears are one.
+ *   end         a tile is full after tile_w * tile_h * 3 bytes; a string that runs past that is cut, and bytes behind it
+ *               (libtiff's EOI and its slack bits, or anything else) are not read.  A missing EOI is no error.
+ *   predictor   2: every byte of a row is the difference to the byte three to its left, modulo 256; undone by a running sum.
+ * Device inputs of sq_lzw_decode_tiles (re-checked on the device):
+ *   scans        the tile bytes as the file holds them, scans_bytes a multiple of 16; a tile starts 4-byte aligned.
+ *   tile_table   int32 [n_tiles][SQ_LZW_TILE_WORDS]: offset, length (bytes of `scans`), zero, zero.
+ *   compression  5 or 1; predictor 1 or 2; the same for every tile of a call.
+ *   mode         SQ_LZW_MODE_WAVE: the 64 lanes of a wave on one tile -- per round they fetch 64 codes at their computed
+ *                positions, a ballot cuts the round at the first Clear, EOI, bad or missing code, the string lengths are
+ *                resolved (references into the same round by pointer jumping), a wave prefix sum gives the output positions,
+ *                strings whose source lies before the round are copied by all lanes byte-parallel and the others one after
+ *                another, each by all lanes (an overlapping range is periodic); the table is in LDS.  SQ_LZW_MODE_LANE: one
+ *                lane per tile runs the serial decoder of lzw_core.h with its table in the workspace: the in-library
+ *                reference.  Both give the same bytes and statuses for every input.  Compression 1 ignores the mode.
+ * Outputs: planes, and status int32 [n_tiles]: SQ_LZW_OK or why the tile stopped -- an offset, length outside `scans` or a
+ * length below 1 (SQ_LZW_BAD_RANGE), a stream (or an uncompressed tile) that ends before the tile is full (SQ_LZW_TRUNCATED), a
+ * code above the next free entry (SQ_LZW_BAD_CODE), first nine bits that are not the Clear code (SQ_LZW_NO_CLEAR), the table
+ * overrun (SQ_LZW_TABLE_FULL), EOI before the tile is full (SQ_LZW_EARLY_EOI).  The planes of a failing tile are zero; it
+ * touches no other tile.  Every loop is bounded by the scan length and the tile size.
+ *   sq_lzw_workspace_bytes : workspace of sq_lzw_decode_tiles (the chunky bytes of every tile and the lane mode's tables); 0
+ *               (and an sq_last_error message) for extents that are no multiples of 16 in 16..SQ_JPEG_MAX_TILE, n_tiles
+ *               outside 1..2^20 or a compression other than 1 and 5.
+ *   sq_lzw_decode_tiles : two launches on `stream` (decode -- for compression 1 the range check; then unpredict and split
+ *               into planes, a wave per row with a wave scan); arguments are checked before the first launch (SQ_ERR_ARG,
+ *               SQ_ERR_WORKSPACE); it allocates nothing and does not wait.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SQ_LZW_TILE_WORDS 4
+#define SQ_LZW_MODE_WAVE 0
+#define SQ_LZW_MODE_LANE 1
+#define SQ_LZW_OK 0
+#define SQ_LZW_BAD_RANGE 1
+#define SQ_LZW_TRUNCATED 2
+#define SQ_LZW_BAD_CODE 3
+#define SQ_LZW_NO_CLEAR 4
+#define SQ_LZW_TABLE_FULL 5
+#define SQ_LZW_EARLY_EOI 6
+size_t sq_lzw_workspace_bytes(int n_tiles, int tile_w, int tile_h, int compression);
+int sq_lzw_decode_tiles(const uint8_t* scans, size_t scans_bytes, const int32_t* tile_table, int n_tiles, int tile_w, int tile_h,
+                        int compression, int predictor, int mode, uint8_t* planes, int32_t* status, void* workspace,
+                        size_t workspace_bytes, sq_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Device-resident cohort feed: one training or inference batch gathered from tables that stay on the device.
  * It replaces, per batch, what the loader path does on the host: one store open and read per slide
  * (/root/reference/src/read_data.py:38-56), the collate that stacks the readable items (/root/reference/src/utils.py:10-18)

@@ -1,4 +1,4 @@
-"""JPEG- and JPEG 2000-tiled TIFF and Aperio SVS slides without openslide: ``TiffSlide`` is the drop-in for ``openslide.OpenSlide`` over
+"""JPEG-, JPEG 2000-, LZW-tiled and uncompressed tiled TIFF and Aperio SVS slides without openslide: ``TiffSlide`` is the drop-in for ``openslide.OpenSlide`` over
 the interface subset this package uses (``dimensions``, ``level_count``, ``level_dimensions``, ``level_downsamples``,
 ``properties``, ``read_region``, ``close``), replacing the region reads of pre_processing/patch_gen_hdf5.py:45,108 and
 spatial_vis/visualize.py:58-66,173.  The container is parsed here in Python (``struct`` + ``os.pread``, no GPU needed); the
@@ -9,7 +9,7 @@ the GPU: there is no CPU fallback.
 
 Accepted: classic TIFF (magic 42) and BigTIFF (43), little-endian; a level is an IFD with TileWidth / TileLength, levels
 ordered by decreasing width; stripped IFDs (thumbnail, label, macro of an SVS) are skipped as OpenSlide skips them.  A tiled
-IFD must have compression 7 (JPEG), 8 bits per sample, 3 samples per pixel, planar configuration 1, photometric 2 (RGB) or 6
+IFD of compression 7 (JPEG; 33003 / 33005 and 5 / 1 are described below) must have 8 bits per sample, 3 samples per pixel, planar configuration 1, photometric 2 (RGB) or 6
 (YCbCr), tile extents that are multiples of 16 in 16..1024, and baseline frames of exactly the tile extent with luma sampling
 1x1, 2x1 or 2x2 over chroma 1x1.  Everything else -- big-endian files, any other compression (34712 among them),
 progressive, arithmetic or 12-bit frames, 1 or 4 components, other samplings, a tile with byte count 0 -- is refused with a
@@ -28,6 +28,15 @@ resolution), RPCL / PCRL / CPRL with one precinct per resolution.  Refused by na
 PPM / PPT, TLM, several tiles or tile-parts, other depths and component counts, code-blocks above 64, positional progressions with
 several precincts.  Python touches marker segments only: packet headers are parsed on the device.  Against Pillow's OpenJPEG the
 bytes are equal for reversible streams with every pass present and within 1 grey level (about 1 byte in 1000) otherwise.
+
+LZW and uncompressed levels (compression 5 / 1: the lossless pyramids libvips, QuPath, Bio-Formats and tiffcp write; a level is one
+codec): a tile is chunky RGB of 8 bits, decoded by ``sq_lzw_decode_tiles`` (csrc/tifflzw.hip, csrc/lzw_core.h) into the same planes,
+every byte libtiff's.  Accepted: photometric 2 (RGB), three samples of 8 bits, planar configuration 1, FillOrder absent or 1,
+Predictor absent, 1 or 2 (horizontal differencing, undone on the device), the tile extents above; LZW streams MSB first with
+libtiff's early change, opening with the Clear code.  Refused by name: Predictor 3, ExtraSamples or four samples (RGBA), FillOrder
+2, any other photometric, an uncompressed tile whose byte count is not tile width x height x 3, old-style LZW (LSB first, no
+Clear at the start); deflate (8, 32946) and every other compression.  A stream that overruns the code table without a Clear is
+refused where libtiff refuses it, when the tile is read (``TileDecodeError``).
 
 Region semantics: ``location`` is in level-0 pixels, the level origin is ``(int(x / downsample), int(y / downsample))`` with
 ``downsample = level0_width / level_width``; pixels outside the level are (0, 0, 0, 0), inside alpha is 255.  At level 0 and
@@ -54,13 +63,22 @@ J2K_STATUS_NAMES = {_C["SQ_J2K_BAD_PARAM"]: "a parameter-set field out of range 
                     _C["SQ_J2K_TRUNCATED_HEADER"]: "a packet header runs past the end of the tile's bytes",
                     _C["SQ_J2K_BAD_LENGTH"]: "a pass count, bit-plane count or length that does not fit the code-block or the stream",
                     _C["SQ_J2K_TRUNCATED_BODY"]: "the code-block bytes of a packet run past the end of the tile's bytes"}
+LZW_TILE_WORDS = _C["SQ_LZW_TILE_WORDS"]
+LZW_STATUS_NAMES = {_C["SQ_LZW_BAD_RANGE"]: "a tile range outside the uploaded bytes",
+                    _C["SQ_LZW_TRUNCATED"]: "the tile's bytes end before the tile is full",
+                    _C["SQ_LZW_BAD_CODE"]: "an LZW code above the next free table entry",
+                    _C["SQ_LZW_NO_CLEAR"]: "an LZW stream that does not start with the Clear code",
+                    _C["SQ_LZW_TABLE_FULL"]: "an LZW stream that overruns the code table without a Clear code",
+                    _C["SQ_LZW_EARLY_EOI"]: "the LZW end-of-information code before the tile is full"}
+LZW_COMPRESSIONS = {5: "LZW", 1: "uncompressed"}
+LZW_MODE = _C["SQ_LZW_MODE_WAVE"]         # SQ_LZW_MODE_WAVE: a wave per tile; SQ_LZW_MODE_LANE: a lane per tile, the serial reference
 SCAN_BYTES_MAX = (1 << 31) - 64            # scan offsets in the tile table are int32
 DEFAULT_WORKSPACE_BUDGET = 1 << 30        # bytes of device workspace (planes, coefficients, uploaded scans) per chunk of a batch
 
 _TYPE = {1: "B", 2: "c", 3: "H", 4: "I", 5: "II", 6: "b", 7: "B", 8: "h", 9: "i", 10: "ii", 11: "f", 12: "d", 16: "Q", 17: "q", 18: "Q"}
 _TAG_NAMES = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 262: "PhotometricInterpretation",
-              270: "ImageDescription", 277: "SamplesPerPixel", 284: "PlanarConfiguration", 322: "TileWidth", 323: "TileLength",
-              324: "TileOffsets", 325: "TileByteCounts", 347: "JPEGTables", 530: "YCbCrSubSampling"}
+              266: "FillOrder", 270: "ImageDescription", 277: "SamplesPerPixel", 284: "PlanarConfiguration", 317: "Predictor", 322: "TileWidth",
+              323: "TileLength", 324: "TileOffsets", 325: "TileByteCounts", 338: "ExtraSamples", 347: "JPEGTables", 530: "YCbCrSubSampling"}
 
 
 class WsiFormatError(ValueError):
@@ -463,7 +481,7 @@ def parse_j2k(data, what="JPEG 2000 codestream"):
 
 class _Level:
     __slots__ = ("width", "height", "tile_w", "tile_h", "tiles_x", "tiles_y", "offsets", "counts", "base", "transform", "hs", "vs",
-                 "index", "info", "shared", "codec", "compression", "caps")
+                 "index", "info", "shared", "codec", "compression", "caps", "predictor")
 
 
 class TiffSlide:
@@ -472,8 +490,8 @@ class TiffSlide:
     ``entropy``: how the scans of JPEG tiles are decoded -- 'serial' (one lane per tile, ``sq_jpeg_decode_tiles``) or 'split'
     (the 64 lanes of a wave on one tile's scan, ``sq_jpeg_decode_tiles_split``: the same bytes whatever the file holds; tiles
     with restart intervals still decode on one lane).  ``sub_bytes``, an expert knob of 'split': the bytes of scan per lane and
-    round, a multiple of 4 in SQ_JPEG_SPLIT_SUB_MIN..SQ_JPEG_SPLIT_SUB_MAX, or 0 for the library's default.  JPEG 2000 levels
-    ignore both."""
+    round, a multiple of 4 in SQ_JPEG_SPLIT_SUB_MIN..SQ_JPEG_SPLIT_SUB_MAX, or 0 for the library's default.  JPEG 2000, LZW and
+    uncompressed levels ignore both."""
 
     def __init__(self, path, device="cuda:0", workspace_budget=DEFAULT_WORKSPACE_BUDGET, entropy="serial", *, sub_bytes=0):
         if entropy not in ("serial", "split"):
@@ -484,6 +502,7 @@ class TiffSlide:
                              f"for the library's default")
         self.path, self.device, self.workspace_budget = path, device, int(workspace_budget)
         self.entropy, self.sub_bytes = entropy, sub_bytes
+        self.lzw_mode = LZW_MODE                # how LZW tiles are decoded; the measurement tool and the tests switch it, no CLI does
         self._fd = os.open(path, os.O_RDONLY)
         self._pinned = None
         self.last_batch_tiles = []           # (tile_x, tile_y) of every tile decode of the last read_regions call, chunk by chunk
@@ -516,9 +535,22 @@ class TiffSlide:
                 raise WsiFormatError(f"{what}: {_TAG_NAMES[tag]} = {v if v is None or len(v) != 1 else v[0]}: {text}")
             return v
         comp = _one(tags, 259, 1)
-        if comp != 7 and comp not in J2K_COMPRESSIONS:
-            name = {1: " (uncompressed)", 5: " (LZW)", 8: " (deflate)", 34712: " (JPEG 2000)"}.get(comp, "")
-            raise WsiFormatError(f"{what}: Compression = {comp}{name} is not supported: 7 (JPEG), 33003 or 33005 (Aperio JPEG 2000) only")
+        lossless = comp in LZW_COMPRESSIONS
+        if comp != 7 and comp not in J2K_COMPRESSIONS and not lossless:
+            name = {8: " (deflate)", 32946: " (deflate)", 34712: " (JPEG 2000)"}.get(comp, "")
+            raise WsiFormatError(f"{what}: Compression = {comp}{name} is not supported: 7 (JPEG), 33003 or 33005 (Aperio JPEG 2000), 5 (LZW) or "
+                                 f"1 (uncompressed) only")
+        if lossless:                        # chunky RGB as stored: no colour transform, no subsampling, no alpha
+            what_comp = f"{what}: Compression = {comp} ({LZW_COMPRESSIONS[comp]})"
+            if _one(tags, 262) != 2:
+                raise WsiFormatError(f"{what_comp} with PhotometricInterpretation = {_one(tags, 262)}: 2 (RGB) only")
+            if 338 in tags:
+                raise WsiFormatError(f"{what_comp} with ExtraSamples = {tuple(int(x) for x in tags[338])}: three samples without alpha only")
+            if _one(tags, 266, 1) != 1:
+                raise WsiFormatError(f"{what_comp} with FillOrder = {_one(tags, 266)}: 1 (most significant bit first) only")
+            if _one(tags, 317, 1) not in (1, 2):
+                kind = " (floating point)" if _one(tags, 317) == 3 else ""
+                raise WsiFormatError(f"{what_comp} with Predictor = {_one(tags, 317)}{kind}: 1 (none) or 2 (horizontal differencing) only")
         need(258, (8,), "8 bits per sample only")
         if len(need(277, (3,), "3 samples per pixel only")) != 1 or len(tags[258]) != 3:
             raise WsiFormatError(f"{what}: BitsPerSample = {tuple(int(x) for x in tags[258])}: three samples of 8 bits only")
@@ -526,7 +558,8 @@ class TiffSlide:
             raise WsiFormatError(f"{what}: PlanarConfiguration = {_one(tags, 284)}: 1 (chunky) only")
         photometric = need(262, (2, 6), "2 (RGB) or 6 (YCbCr) only")[0] if comp == 7 else None      # not consulted for JPEG 2000
         lv = _Level()
-        lv.codec, lv.compression, lv.caps = ("jpeg" if comp == 7 else "j2k"), comp, None
+        lv.codec, lv.compression, lv.caps = ("jpeg" if comp == 7 else "lzw" if comp == 5 else "raw" if comp == 1 else "j2k"), comp, None
+        lv.predictor = _one(tags, 317, 1) if lossless else 1
         lv.index, lv.width, lv.height = index, _one(tags, 256, 0), _one(tags, 257, 0)
         lv.tile_w, lv.tile_h = _one(tags, 322, 0), _one(tags, 323, 0)
         if lv.width < 1 or lv.height < 1:
@@ -545,7 +578,11 @@ class TiffSlide:
         lv.base = parse_jpeg(bytes(tags[347]), what=f"{what} JPEGTables") if (347 in tags and comp == 7) else None
         lv.shared = table_set_bytes(lv.base) if lv.base is not None else None      # ONE object for every tile without tables of its own
         lv.info = {}
-        lv.hs, lv.vs = None, None
+        lv.hs, lv.vs = (1, 1) if lossless else (None, None)         # the planes are written at full resolution
+        if comp == 1 and (lv.counts != lv.tile_w * lv.tile_h * 3).any():
+            t = int(np.flatnonzero(lv.counts != lv.tile_w * lv.tile_h * 3)[0])
+            raise WsiFormatError(f"{what}: Compression = 1 (uncompressed) with TileByteCounts[{t}] = {int(lv.counts[t])} (tile {t % lv.tiles_x}, "
+                                 f"{t // lv.tiles_x}): tiles of {lv.tile_w} x {lv.tile_h} x 3 samples hold {lv.tile_w * lv.tile_h * 3} bytes")
         past = np.flatnonzero(lv.offsets + lv.counts > self._size)
         if past.size == 0:                  # a range past the end of the file is reported when that tile is read
             self._tile_info(lv, 0, level_name=what)
@@ -561,6 +598,13 @@ class TiffSlide:
         off, count = int(lv.offsets[t]), int(lv.counts[t])
         if off < 0 or off + count > self._size:
             raise WsiFormatError(f"{what}: TileOffsets = {off} with TileByteCounts = {count} runs past the end of the file ({self._size} bytes)")
+        if lv.codec in ("lzw", "raw"):       # the whole tile is the scan; an LZW stream must open with the Clear code (256 in 9 bits)
+            first = os.pread(self._fd, 2, off)
+            if lv.codec == "lzw" and (len(first) < 2 or first[0] != 0x80 or first[1] & 0x80):
+                raise WsiFormatError(f"IFD {lv.index}: Compression = 5 (LZW) but {what} starts with bytes {first.hex(' ')}, not with the Clear code "
+                                     f"(80 00 in nine bits): old-style LZW (least significant bit first, no Clear at the start) is not supported")
+            got = lv.info[t] = (off, count, b"", 0, 0)
+            return got
         data = os.pread(self._fd, count, off)
         if lv.codec == "j2k":
             return self._j2k_tile_info(lv, t, what, off, data)
@@ -668,7 +712,10 @@ class TiffSlide:
                            if x0 < lv.width and y0 < lv.height and x0 + w > 0 and y0 + h > 0 else [])
         L = _lib.lib()
         first = self._tile_info(lv, 0)                                      # fixes the level's sampling
-        if lv.codec == "j2k":               # the records of the first tile's parameter set stand for the level's in this estimate
+        if lv.codec in ("lzw", "raw"):
+            per_tile = L.sq_lzw_workspace_bytes(2, lv.tile_w, lv.tile_h, lv.compression) - L.sq_lzw_workspace_bytes(1, lv.tile_w, lv.tile_h, lv.compression) \
+                + L.sq_jpeg_planes_bytes(1, lv.tile_w, lv.tile_h, 1, 1) + int(lv.counts.max())
+        elif lv.codec == "j2k":             # the records of the first tile's parameter set stand for the level's in this estimate
             caps = self._j2k_caps(lv, [first[2]])
             per_tile = L.sq_j2k_workspace_bytes(2, lv.tile_w, lv.tile_h, *caps, 16) - L.sq_j2k_workspace_bytes(1, lv.tile_w, lv.tile_h, *caps, 16) \
                 + L.sq_jpeg_planes_bytes(1, lv.tile_w, lv.tile_h, 1, 1) + 2 * int(lv.counts.max())
@@ -688,7 +735,7 @@ class TiffSlide:
             failures += self._decode_chunk(lv, level, sorted(tiles), origins[start:stop], out[start:stop])
             start = stop
         if failures:
-            table = J2K_STATUS_NAMES if lv.codec == "j2k" else STATUS_NAMES
+            table = J2K_STATUS_NAMES if lv.codec == "j2k" else LZW_STATUS_NAMES if lv.codec in ("lzw", "raw") else STATUS_NAMES
             names = ", ".join(f"({tx}, {ty}): {table.get(st, st)}" for _, tx, ty, st in failures[:8])
             bad = {ty * lv.tiles_x + tx for _, tx, ty, _ in failures}
             first = min(i for i, t in enumerate(touched) if bad & set(t))
@@ -702,7 +749,7 @@ class TiffSlide:
         infos = [self._tile_info(lv, t) for t in tiles]
         order = sorted(range(len(tiles)), key=lambda i: -infos[i][1])
         set_index, sets = {}, []
-        words = J2K_TILE_WORDS if lv.codec == "j2k" else TILE_WORDS
+        words = {"j2k": J2K_TILE_WORDS, "lzw": LZW_TILE_WORDS, "raw": LZW_TILE_WORDS}.get(lv.codec, TILE_WORDS)
         table = np.zeros((len(tiles), words), dtype=np.int32)
         slot_map = np.full(lv.tiles_x * lv.tiles_y, -1, dtype=np.int32)
         at = 0
@@ -747,12 +794,16 @@ class TiffSlide:
         ``codec`` ('jpeg' or 'j2k'), ``geom`` (tile_w, tile_h, hs, vs), ``transform``, ``tiles`` (the tile number of every slot),
         ``table`` int32 [n, 8] (JPEG 2000: [n, 4]), ``sets`` (list of table-set or parameter-set byte strings) and ``scans``
         (uint8 array: the scans, or the packet bytes); JPEG 2000 adds ``caps``, the record counts the workspace is sized by.
-        Needs no GPU: the host check programs and the tests read it."""
+        LZW and uncompressed levels ('lzw', 'raw') have no sets: ``codec``, ``geom``, ``predictor``, ``tiles``, ``table`` int32
+        [n, 4] and ``scans`` (the tiles' bytes as the file holds them).  Needs no GPU: the host check programs and the tests read it."""
         lv = self._levels[level]
         tiles = list(range(lv.tiles_x * lv.tiles_y)) if tiles is None else list(tiles)
         order, table, sets, scans_bytes, _ = self._plan(lv, tiles)
         scans = np.zeros(scans_bytes, dtype=np.uint8)
         self._read_scans(lv, level, tiles, order, table, scans)
+        if lv.codec in ("lzw", "raw"):       # no table sets: the predictor is all a tile needs besides its bytes
+            return dict(codec=lv.codec, geom=(lv.tile_w, lv.tile_h, 1, 1), predictor=lv.predictor, tiles=[tiles[i] for i in order], table=table,
+                        scans=scans)
         job = dict(codec=lv.codec, geom=(lv.tile_w, lv.tile_h, lv.hs, lv.vs), transform=lv.transform, tiles=[tiles[i] for i in order], table=table,
                    sets=sets, scans=scans)
         if lv.codec == "j2k":
@@ -788,7 +839,11 @@ class TiffSlide:
         geom = (lv.tile_w, lv.tile_h, lv.hs, lv.vs)
         planes = torch.empty(_lib.need(L.sq_jpeg_planes_bytes, n, *geom), dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        if lv.codec == "j2k":
+        if lv.codec in ("lzw", "raw"):
+            need = _lib.need(L.sq_lzw_workspace_bytes, n, lv.tile_w, lv.tile_h, lv.compression)
+            _lib.call("sq_lzw_decode_tiles", dev, blob[head:], scans_bytes, blob, n, lv.tile_w, lv.tile_h, lv.compression, lv.predictor, self.lzw_mode,
+                      planes, status, workspace=need)
+        elif lv.codec == "j2k":
             caps = self._j2k_caps(lv, sets)
             need = _lib.need(L.sq_j2k_workspace_bytes, n, lv.tile_w, lv.tile_h, *caps, scans_bytes)
             _lib.call("sq_j2k_decode_tiles", dev, blob[head:], scans_bytes, blob, n, blob[o_sets:], len(sets), lv.tile_w, lv.tile_h, *caps,
@@ -816,7 +871,7 @@ class TiffSlide:
 
 MISSING_OPENSLIDE = ("openslide-python is required to read whole-slide images (pip install openslide-python); "
                      "sequoia-pub_amd.patchgen.extract_patches and embed_slide also accept any object with OpenSlide's interface.  "
-                     "JPEG-tiled TIFF and Aperio SVS files open without it: pass --reader tiff.")
+                     "JPEG-, JPEG 2000-, LZW-tiled and uncompressed tiled TIFF and Aperio SVS files open without it: pass --reader tiff.")
 
 
 def open_slide(path, reader="openslide", device="cuda:0", entropy="serial"):
