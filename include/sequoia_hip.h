@@ -1072,7 +1072,7 @@ int sq_dbg_kmeans_lloyd(const float* X, int n_slides, int n_samples, int dim, in
 /* ------------------------------------------------------------------------------------------------------------
  * JPEG tiles: the tiles of a JPEG-compressed tiled TIFF / Aperio SVS level decoded and composed into RGBA regions on the
  * device.  Replaces the host decoding behind the region reads of pre_processing/patch_gen_hdf5.py (slide.read_region at
- * :45 and :108, through OpenSlide) and of spatial_vis/visualize.py:58-66,173; sequoia-pub_amd/wsi.py (TiffSlide) is the
+ * :45 and :108, through OpenSlide) and of spatial_vis/visualize.py:58-66,173; sequoia-pub_amd/wsi/ (TiffSlide, jpeg.py) is the
  * caller.  Every output byte is libjpeg's (baseline Huffman, "islow" IDCT, "fancy" upsampling, the 16-bit fixed-point
  * YCbCr -> RGB), integer throughout; sequoia-pub_amd/csrc/jpeg_core.h holds the arithmetic as host-and-device functions:
  *   entropy     interleaved scan in MCU order; FF 00 -> FF; EXTEND(v, s) = v if v >= 2^(s-1) else v - 2^s + 1; AC symbol rs:
@@ -1182,7 +1182,7 @@ int sq_jpeg_compose_regions(const uint8_t* planes, int n_slots, int tile_w, int 
 /* ------------------------------------------------------------------------------------------------------------
  * JPEG 2000 tiles: the tiles of an Aperio SVS level with compression 33003 (YCbCr) or 33005 (RGB), each one raw codestream
  * of one tile, decoded into the planes sq_jpeg_compose_regions reads with hs = vs = 1 (three full-resolution uint8 planes
- * per tile, sq_jpeg_planes_bytes(n, tile_w, tile_h, 1, 1)); sequoia-pub_amd/wsi.py is the caller and parses the marker
+ * per tile, sq_jpeg_planes_bytes(n, tile_w, tile_h, 1, 1)); sequoia-pub_amd/wsi/j2k.py is the caller and parses the marker
  * segments, the library parses the packets.  sequoia-pub_amd/csrc/j2k_core.h holds the arithmetic as host-and-device functions:
  *   packets     LRCP, RLCP, and RPCL / PCRL / CPRL with one precinct per resolution; per packet one non-empty bit, then per
  *               band (LL; HL, LH, HH) and code-block in raster order inclusion (tag tree against layer + 1, later one bit),
@@ -1244,7 +1244,7 @@ int sq_j2k_decode_tiles(const uint8_t* streams, size_t streams_bytes, const int3
 /* ------------------------------------------------------------------------------------------------------------
  * LZW and uncompressed tiles: the tiles of a generic tiled TIFF level with Compression 5 (LZW) or 1 (none), chunky RGB of
  * 8 bits, decoded into the planes sq_jpeg_compose_regions reads with hs = vs = 1 and transform 0 (three full-resolution
- * uint8 planes per tile, R, G, B: sq_jpeg_planes_bytes(n, tile_w, tile_h, 1, 1)); sequoia-pub_amd/wsi.py is the caller.
+ * uint8 planes per tile, R, G, B: sq_jpeg_planes_bytes(n, tile_w, tile_h, 1, 1)); sequoia-pub_amd/wsi/lzw.py is the caller.
  * sequoia-pub_amd/csrc/lzw_core.h holds the code arithmetic, the serial decoder and the status rules as host-and-device
  * functions; every byte is libtiff's.
  *   codes       packed MSB first; behind a Clear (256) code j = 0, 1, ... is 9 bits wide for j < 254, 10 for j < 766, 11 for

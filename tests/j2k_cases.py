@@ -247,21 +247,7 @@ def read_out(path, job, n=None):
 def build_hostcheck(directory, sanitize):
     """tools/j2k_hostcheck.cpp built with the host compiler into `directory`; returns a runner over a job directory that
     asserts a clean exit (and, with `sanitize`, a clean address / undefined-behaviour sanitizer run) and gives the output."""
-    import shutil
-    import subprocess
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx is not None, "no host C++ compiler (c++, g++ or clang++) to build tools/j2k_hostcheck.cpp"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(str(directory), "j2k_hostcheck")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", exe, os.path.join(root, "tools", "j2k_hostcheck.cpp")],
-                   check=True)
-
-    def run(jobs):
-        r = subprocess.run([exe, str(jobs)], capture_output=True, text=True)
-        assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
-        return r.stdout
-    return run
+    return wc.build_hostcheck("j2k_hostcheck.cpp", directory, sanitize, extra_flags=("-ffp-contract=off",))
 
 
 # ---- damaged streams --------------------------------------------------------------------------------------------------------

@@ -4,9 +4,7 @@ the decode core of csrc/jpeg_core.h compiled for the host with the address and u
 (tools/jpegdec_hostcheck.cpp, a stand-alone program) on every fixture and on damaged streams, and the parser's refusals."""
 import io
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ import wsi_cases as wc
 from sequoia_pub_amd import wsi
 from sequoia_pub_amd._abi import CONSTANTS as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL = list(wc.CASES) + ["pipeline"]
 
 
@@ -150,6 +147,21 @@ def test_generic_tiff_without_description_gives_the_default_magnification(tmp_pa
         assert float(slide.properties.get("aperio.AppMag", 20)) == 20.0
 
 
+def test_the_upload_of_every_fixture_level_equals_the_recorded_jobs():
+    """Slot order (ties included), table rows, padding, set de-duplication and scans of every level of every slide fixture --
+    JPEG, JPEG 2000, LZW and uncompressed -- against tests/golden/wsi_jobs.json (tests/golden/make_wsi_jobs_golden.py)."""
+    import json
+    with open(wc.JOBS_GOLDEN) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(wc.job_fixtures())
+    for name in wc.job_fixtures():
+        with wsi.TiffSlide(os.path.join(os.path.dirname(wc.GOLDEN_DIR), name + ".tif")) as slide:
+            got = wc.job_records(slide)
+        assert len(got) == len(want[name]), name
+        for level, (g, w) in enumerate(zip(got, want[name])):
+            assert g == w, (name, level, {k: (g[k], w[k]) for k in w if g.get(k) != w[k]})
+
+
 # ---- the decode core on the host, under the sanitizers -----------------------------------------------------------------------
 def write_job(path, job, table=None, sets=None, scans=None):
     table = job["table"] if table is None else table
@@ -247,19 +259,7 @@ def damaged_jobs():
 @pytest.fixture(scope="module")
 def hostcheck(tmp_path_factory):
     """The stand-alone program built with the host compiler and the sanitizers, and a runner over a job directory."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler (c++, g++ or clang++) to build tools/jpegdec_hostcheck.cpp")
-    build = tmp_path_factory.mktemp("hostcheck")
-    exe = str(build / "jpegdec_hostcheck")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tools", "jpegdec_hostcheck.cpp")], check=True)
-
-    def run(directory):
-        r = subprocess.run([exe, str(directory)], capture_output=True, text=True)
-        assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
-        return r.stdout
-    return run
+    return wc.build_hostcheck("jpegdec_hostcheck.cpp", tmp_path_factory.mktemp("hostcheck"), sanitize=True)
 
 
 def test_host_build_of_the_core_equals_the_goldens_under_sanitizers(hostcheck, golden, tmp_path):

@@ -6,7 +6,6 @@ the Python layer that need no GPU."""
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,9 +16,6 @@ from test_wsi_host import damaged_jobs, read_out, write_job
 from sequoia_pub_amd import wsi
 from sequoia_pub_amd._abi import CONSTANTS as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-
 
 @pytest.fixture(scope="module")
 def golden():
@@ -29,18 +25,9 @@ def golden():
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
     """Both stand-alone programs built with the host compiler and the sanitizers: run(which, directory, *args) -> stdout."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler (c++, g++ or clang++) to build tools/jpegsplit_hostcheck.cpp")
     build = tmp_path_factory.mktemp("splitcheck")
-    for name in ("jpegsplit_hostcheck", "jpegdec_hostcheck"):
-        subprocess.run([cxx, *SAN, "-o", str(build / name), os.path.join(ROOT, "tools", f"{name}.cpp")], check=True)
-
-    def run(which, directory, *args):
-        r = subprocess.run([str(build / which), str(directory), *map(str, args)], capture_output=True, text=True)
-        assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
-        return r.stdout
-    return run
+    runners = {name: wc.build_hostcheck(f"{name}.cpp", build, sanitize=True) for name in ("jpegsplit_hostcheck", "jpegdec_hostcheck")}
+    return lambda which, directory, *args: runners[which](directory, *args)
 
 
 @pytest.fixture(scope="module")

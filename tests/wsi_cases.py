@@ -327,3 +327,65 @@ def decode_tile(stream, transform, events=None):
 def join_tables(tables, tile):
     """An abbreviated table stream and an image-only stream as one full stream."""
     return tile if tables is None else tables[:-2] + tile[2:]
+
+
+# ---- the stand-alone host programs of the slide codecs (tools/*_hostcheck.cpp) ------------------------------------------------
+def build_hostcheck(source, directory, sanitize, extra_flags=()):
+    """tools/`source` built with the host compiler into `directory`; returns a runner ``run(jobs, *args)`` over a job directory
+    that asserts a clean exit (and, with `sanitize`, a clean address / undefined-behaviour sanitizer run) and gives the output."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx is not None, f"no host C++ compiler (c++, g++ or clang++) to build tools/{source}"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(str(directory), os.path.splitext(source)[0] + ("_san" if sanitize else ""))
+    flags = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", *extra_flags, *flags, "-o", exe, os.path.join(root, "tools", source)], check=True)
+
+    def run(jobs, *args):
+        r = subprocess.run([exe, str(jobs), *map(str, args)], capture_output=True, text=True)
+        assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
+        return r.stdout
+    return run
+
+
+# ---- what read_regions uploads, as recorded results (tests/golden/wsi_jobs.json) -----------------------------------------------
+JOBS_GOLDEN = os.path.join(os.path.dirname(GOLDEN_DIR), "wsi_jobs.json")
+JOBS_GOLDEN_DIRS = ("wsi", "j2k", "tiffz")
+
+
+def job_fixtures():
+    """'<directory>/<name>' of every slide fixture whose upload is recorded."""
+    root = os.path.dirname(GOLDEN_DIR)
+    return [f"{d}/{f[:-4]}" for d in JOBS_GOLDEN_DIRS for f in sorted(os.listdir(os.path.join(root, d))) if f.endswith(".tif")]
+
+
+def job_records(slide):
+    """Per level of an open slide: the SHA-256 of its tile ranges, and ``tile_job`` of the whole level ('all') and of every
+    second tile in descending order ('half') -- the plain values as they are, the table, the sets and the scans as SHA-256."""
+    import hashlib
+
+    def sha(data):
+        return hashlib.sha256(data).hexdigest()
+
+    def record(job):
+        out = dict(codec=job["codec"], geom=[int(v) for v in job["geom"]], tiles=[int(t) for t in job["tiles"]])
+        for key in ("transform", "predictor"):
+            if key in job:
+                out[key] = int(job[key])
+        if "caps" in job:
+            out["caps"] = [int(v) for v in job["caps"]]
+        out["table_shape"] = list(job["table"].shape)
+        out["table"] = sha(job["table"].tobytes())
+        if "sets" in job:
+            out["sets_count"] = len(job["sets"])
+            out["sets"] = sha(b"".join(job["sets"]))
+        out["scans"] = sha(job["scans"].tobytes())
+        return out
+    levels = []
+    for level in range(slide.level_count):
+        offsets, counts = slide.tile_ranges(level)
+        half = sorted(range(0, len(offsets), 2), reverse=True)
+        levels.append(dict(tile_ranges=sha(offsets.astype("<i8").tobytes() + counts.astype("<i8").tobytes()),
+                           all=record(slide.tile_job(level)), half=record(slide.tile_job(level, tiles=half))))
+    return levels

@@ -116,7 +116,7 @@ def measure(slides_dir, rounds, lines):
         t0 = time.perf_counter()
         s["slide"]._plan(lv, tiles)
         plan_ms = (time.perf_counter() - t0) * 1e3
-        job_bytes = int(sum(s["slide"]._tile_info(lv, t)[1] for t in tiles)) + len(tiles) * 16 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
+        job_bytes = int(sum(s["slide"]._tile_info(lv, t).length for t in tiles)) + len(tiles) * lv.codec.tile_words * 4 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
         pinned = torch.empty(job_bytes, dtype=torch.uint8).pin_memory()
         ups = []
         for _ in range(rounds + 1):

@@ -145,7 +145,7 @@ def measure(slides_dir, rounds, lines):
         slide = s["slides"]["serial"]
         lv = slide._levels[0]
         tiles = sorted({ty * lv.tiles_x + tx for tx, ty in slide.last_batch_tiles})
-        job_bytes = int(sum(slide._tile_info(lv, t)[1] for t in tiles)) + len(tiles) * 32 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
+        job_bytes = int(sum(slide._tile_info(lv, t).length for t in tiles)) + len(tiles) * lv.codec.tile_words * 4 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
         pinned = torch.empty(job_bytes, dtype=torch.uint8).pin_memory()
         ups = []
         for _ in range(rounds + 1):

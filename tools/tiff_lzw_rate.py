@@ -137,7 +137,7 @@ def measure(slides_dir, rounds, lines):
         t0 = time.perf_counter()
         s["slide"]._plan(lv, tiles)
         plan_ms = (time.perf_counter() - t0) * 1e3
-        job_bytes = int(sum(s["slide"]._tile_info(lv, t)[1] for t in tiles)) + len(tiles) * 16 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
+        job_bytes = int(sum(s["slide"]._tile_info(lv, t).length for t in tiles)) + len(tiles) * lv.codec.tile_words * 4 + lv.tiles_x * lv.tiles_y * 4 + s["k"] * 8
         pinned = torch.empty(job_bytes, dtype=torch.uint8).pin_memory()
         ups = []
         for _ in range(rounds + 1):
@@ -153,7 +153,7 @@ def measure(slides_dir, rounds, lines):
         if host:
             offsets, counts = s["slide"].tile_ranges(0)
             sample = tiles[::max(1, len(tiles) // 48)]      # the batch's tiles, about 48 of them timed and scaled
-            files = [tz.strip_tiff(os.pread(s["slide"]._fd, int(counts[t]), int(offsets[t])), TILE, TILE, lv.compression, s["predictor"]) for t in sample]
+            files = [tz.strip_tiff(os.pread(s["slide"]._fd, int(counts[t]), int(offsets[t])), TILE, TILE, lv.codec.compression, s["predictor"]) for t in sample]
             Image.open(io.BytesIO(files[0])).load()
             t0 = time.perf_counter()
             for f in files:
